@@ -14,6 +14,12 @@ step, and the step time is the max over ranks.  --weak keeps 16384 chunks per ra
 An optional payload gather (every rank's frames into one contiguous image on rank 0,
 RCCL all-gather of the padded frame slots) is timed separately (--payload-gather).
 
+A plain run (--gpus N --steps K --warmup W) sets up, warms up, times the K steps, writes the
+last step's outputs when --dump-outputs DIR is given (dump_outputs below), and prints the line.
+Everything else -- the libzstd decode of every frame, the GPU decompression leg, the libzstd CPU
+baselines and the extra legs -- takes runs of its own and is behind --full; the --no-* options
+trim a --full run.
+
 Prints one JSON line (driver contract).  roofline = the dominant kernel's algorithmic
 bytes (input + compressed output) per launch / its average HIP-event
 duration on the launch stream, plus the measured issue-rate fraction of that kernel from
@@ -27,7 +33,7 @@ the measured thread count, one thread and all cores (the north star's ">= 10x al
 also the line's `vs_cpu_all_core`): all-core is measured when the process may use every core,
 otherwise the larger of the measured rate and the 1-thread rate x physical cores x the measured
 parallel efficiency (the conservative denominator).
-Extra legs at N=1 (not `value`): C3 on uniform random bytes, C3 at levels 1 and 2, C2 (one 64 MiB frame through
+Extra legs at N=1 with --full (not `value`): C3 on uniform random bytes, C3 at levels 1 and 2, C2 (one 64 MiB frame through
 ZstdManager::compress) and C5 (level 9 with a COVER dictionary on 4,096 x 16 KiB JSON records),
 each with its roofline and libzstd beside it, and GPU decompression of the C3 frames.
 """
@@ -56,6 +62,8 @@ VALU_CYCLES_PIPE = 2   # the SIMD-32 pipe takes a wave64 VALU in 2 cycles when s
 METRIC = "compress GB/s + ratio, 1 GB @ level 3, 64 KB chunks; libzstd round-trip OK"
 SEEDS = {"mix": 0x5EED0003, "random": 0x5EED0004}
 C2_BYTES, C2_SEED = 64 << 20, 0x5EED0002
+DUMP_SAMPLE, DUMP_SEED = 128, 0x5EED0D01  # --dump-outputs: frames written whole, and the seed that picks them
+DUMP_SAMPLE_BYTES = 48 << 20            # cap on the float32 frame sample (the whole dump stays under 64 MB)
 
 
 def gen_chunks(kind, n, first):
@@ -547,6 +555,40 @@ def cpu_decompress_baseline(b, threads, gpu_gbs=None):
     return res
 
 
+# ----------------------------------------------------------------------------- outputs
+def dump_outputs(outdir, b, all_sizes, offs, rank):
+    """--dump-outputs: what the last timed step handed its caller, as outdir/<name>.npy (rank 0;
+    <name>_rank<r>.npy on the other ranks), so that two builds can be compared output for output:
+      out_sizes, status       per-chunk compressed size / status of this rank (float64)
+      all_sizes, frame_offsets  ShardPlan.gather_offsets' result, global chunk order (float64)
+      frame_checksums         per chunk, sum over the frame's bytes of byte[j] * (j % 251 + 1):
+                              exact in float64, covers every byte of every frame
+      frames_sample_index     DUMP_SAMPLE chunk indices drawn with DUMP_SEED (float64)
+      frames_sample           those chunks' frames, one row per chunk, zero past the frame's
+                              size (float32)
+    Bytes of an output slot past its frame's size are not output and are left out of both."""
+    os.makedirs(outdir, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    n, slot, dev = b.n, b.slot, b.dev
+    slots = b.d_out[: n * slot].view(n, slot)
+    col = torch.arange(slot, dtype=torch.int64, device=dev)
+    weight = col % 251 + 1
+    sums = torch.zeros(n, dtype=torch.float64, device=dev)
+    for lo in range(0, n, 1024):
+        hi = min(n, lo + 1024)
+        live = col[None, :] < b.out_sizes[lo:hi, None]
+        sums[lo:hi] = (slots[lo:hi].to(torch.int64) * live * weight).sum(1).to(torch.float64)
+    k = min(n, DUMP_SAMPLE, DUMP_SAMPLE_BYTES // (4 * slot))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False)) if k else np.zeros(0, np.int64)
+    d_idx = torch.from_numpy(idx).to(dev)
+    sample = (slots[d_idx] * (col[None, :] < b.out_sizes[d_idx, None])).to(torch.float32)
+    arrays = {"out_sizes": b.out_sizes.to(torch.float64), "status": b.status.to(torch.float64),
+              "all_sizes": all_sizes.to(torch.float64), "frame_offsets": offs.to(torch.float64),
+              "frame_checksums": sums, "frames_sample_index": d_idx.to(torch.float64), "frames_sample": sample}
+    for name, t in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{sfx}.npy"), t.cpu().numpy())
+
+
 # ----------------------------------------------------------------------------- profiles
 def _newest(pattern):
     import glob
@@ -591,10 +633,15 @@ def main():
     ap.add_argument("--chunks", type=int, default=CHUNKS, help="chunks in the batch (per GPU with --weak)")
     ap.add_argument("--weak", action="store_true", help="weak scaling: every rank compresses --chunks chunks of its own")
     ap.add_argument("--payload-gather", action="store_true", help="also time an RCCL gather of every rank's frames (N>1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the libzstd decode of every rank-0 frame after timing")
-    ap.add_argument("--no-decompress", action="store_true", help="skip the GPU decompression leg")
-    ap.add_argument("--no-legs", action="store_true", help="skip the C3-random, C2 and C5 legs (N=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the libzstd decode of every rank-0 frame, the GPU "
+                         "decompression leg, the libzstd CPU baselines and the extra legs (each can be dropped with its --no-* option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the libzstd CPU baselines")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the libzstd decode of every rank-0 frame after timing")
+    ap.add_argument("--no-decompress", action="store_true", help="with --full: skip the GPU decompression leg")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the C3-random, level 1/2, C2 and C5 legs (N=1)")
     ap.add_argument("--cpu-threads", default=None,
                     help="libzstd baseline threads: a number, or 'all' (the process affinity); default: every thread the "
                          "process may keep busy (affinity, capped by the cgroup quota and the pool share OMP_NUM_THREADS)")
@@ -604,6 +651,13 @@ def main():
 
     if args.gpus < 1:
         sys.exit(f"bench.py: --gpus must be >= 1 (got {args.gpus})")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
+    # a plain run stops after the timed steps (and the output dump); the rest needs --full
+    do_verify = args.full and not args.no_verify
+    do_decompress = args.full and not args.no_decompress
+    do_legs = args.full and not args.no_legs
+    do_cpu = args.full and not args.no_cpu_baseline
     if not launch.rank_env_present():
         if args.gpus > 1:
             # C4 without a launcher around us: start one rank per GPU as child processes (before
@@ -671,6 +725,8 @@ def main():
     else:
         comp_all, k1, k2 = float(comp), stats[2].item(), stats[3].item()
     gathered_total = int(all_sizes.sum().item())  # == sum of every rank's frame bytes
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, b, all_sizes, offs, rank)
 
     gather = None
     if args.payload_gather and world > 1:
@@ -691,11 +747,11 @@ def main():
         del pad, img
 
     verified = None
-    if not args.no_verify and rank == 0:
+    if do_verify and rank == 0:
         verified = libzstd_roundtrip(b.d_out.cpu().numpy(), b.out_sizes.cpu().numpy(), b.slot, host)
 
     dec = None
-    if not args.no_decompress:
+    if do_decompress:
         dec = decompress_leg(b, min(args.steps, 5), world)
 
     aff = len(os.sched_getaffinity(0))
@@ -706,8 +762,8 @@ def main():
     else:
         threads = host_share()
     legs = {}
-    if world == 1 and not args.no_legs and args.dataset == "mix" and args.chunks == CHUNKS:
-        leg_threads = None if args.no_cpu_baseline else threads
+    if world == 1 and do_legs and args.dataset == "mix" and args.chunks == CHUNKS:
+        leg_threads = threads if do_cpu else None
         legs["c3_random"] = random_leg(dev, 5, leg_threads)
         for lv in (1, 2):
             legs[f"c3_level{lv}"] = level_leg(host, dev, lv, 5, leg_threads)
@@ -761,12 +817,12 @@ def main():
         if gather:
             line["payload_gather"] = gather
         if dec is not None:
-            if not args.no_cpu_baseline and world == 1:
+            if do_cpu and world == 1:
                 dec["cpu_baseline"] = cpu_decompress_baseline(b, threads, dec["value"])
             line["decompress"] = dec
         if legs:
             line["legs"] = legs
-        if not args.no_cpu_baseline and world == 1:
+        if do_cpu and world == 1:
             cb = cpu_baseline(host, threads, gbs)
             line["cpu_baseline"] = cb
             # vs_baseline stays null: BASELINE.md publishes no number for this metric (the driver

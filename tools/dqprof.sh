@@ -1,8 +1,9 @@
 # decoder kernel trace (gpurun): bench decompress leg under rocprofv3 --kernel-trace --stats
 set -o pipefail
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${ZH_OUT:-$R/bench_out}  # where the logs and result lines go
 TAG=${1:-dqp}
-mkdir -p $R/gpurun_out/$TAG
+mkdir -p $OUT/$TAG
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/$TAG/trace -o run --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-legs > $R/gpurun_out/$TAG/trace.log 2>&1 || exit 2
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/$TAG/trace -o run --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-legs > $OUT/$TAG/trace.log 2>&1 || exit 2
 echo prof-done

@@ -19,6 +19,8 @@
 set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=$1; shift
+BOUT=${ZH_OUT:-$R/bench_out}  # the bench and fullbench result lines go here
+mkdir -p $BOUT
 mkdir -p $R/gpurun_out
 for s in "$@"; do
   case $s in
@@ -30,8 +32,8 @@ for s in "$@"; do
     trace)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${TAG}_trace -o run --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-verify --no-legs --no-decompress > $R/gpurun_out/${TAG}_trace.log 2>&1) ;;
     tests) timeout -k 10 500 python3 -u -m pytest $R/tests -m gpu -x -q --timeout 120 --timeout-method thread > $R/gpurun_out/${TAG}_gpu_tests.log 2>&1 || { tail -30 $R/gpurun_out/${TAG}_gpu_tests.log; exit 1; } ;;
-    bench) timeout -k 10 300 python3 $R/bench.py --no-cpu-baseline > $R/gpurun_out/${TAG}_bench.json 2> $R/gpurun_out/${TAG}_bench.err ;;
-    fullbench) timeout -k 10 400 python3 $R/bench.py > $R/gpurun_out/${TAG}_fullbench.json 2> $R/gpurun_out/${TAG}_fullbench.err ;;
+    bench) timeout -k 10 300 python3 $R/bench.py --full --no-cpu-baseline > $BOUT/${TAG}_bench.json 2> $BOUT/${TAG}_bench.err ;;
+    fullbench) timeout -k 10 400 python3 $R/bench.py --full > $BOUT/${TAG}_fullbench.json 2> $BOUT/${TAG}_fullbench.err ;;
     dstamps) timeout -k 10 200 python3 $R/tools/deep_stamps.py > $R/gpurun_out/${TAG}_deep_stamps.log 2>&1 ;;
     k1tests) timeout -k 10 300 python3 -u -m pytest $R/tests/test_gpu_k1.py $R/tests/test_gpu_parity.py -x -q --timeout 120 --timeout-method thread > $R/gpurun_out/${TAG}_k1_tests.log 2>&1 || { tail -30 $R/gpurun_out/${TAG}_k1_tests.log; exit 1; }; tail -1 $R/gpurun_out/${TAG}_k1_tests.log ;;
     rstamps) timeout -k 10 200 python3 $R/tools/stamps.py random 4096 > $R/gpurun_out/${TAG}_rstamps.log 2>&1 ;;

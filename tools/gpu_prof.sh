@@ -5,5 +5,7 @@ set -o pipefail
 TAG=${TAG:-r02h}
 bash tools/profile.sh $TAG || exit 1
 bash tools/profile_sq.sh $TAG || exit 2
-timeout -k 10 300 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 3
+OUT=${ZH_OUT:-bench_out}  # where the result line goes
+mkdir -p $OUT
+timeout -k 10 300 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 3
 echo all-done

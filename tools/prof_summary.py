@@ -41,7 +41,7 @@ for k in stats:
     stats[k]["write_bytes"] = w
     stats[k]["hbm_bytes"] = (2 * f + w) if (f is not None and w is not None) else None
 out = {"tag": tag, "workload": "bench.py defaults: C3 16384 x 64 KiB mix chunks, 1 MI355X",
-       "commands": ["rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline",
+       "commands": ["rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline",
                     "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline",
                     "rocprofv3 --pmc WRITE_SIZE --kernel-trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline"],
        "kernels": stats}
