@@ -32,6 +32,7 @@
 #include "cuda_zstd_nvcomp.h"
 #include "zh_dict.h"
 #include "zh_launch.h"
+#include "zh_seek.h"
 
 namespace cuda_zstd {
 
@@ -2318,6 +2319,116 @@ int cuda_zstd_extract_metadata(const void *src, size_t size, unsigned int *level
     if (has_ck) *has_ck = m.checksum_policy != ChecksumPolicy::NO_COMPUTE_NO_VERIFY;
   }
   return c_err(s);
+}
+
+// ---- seekable streams (zh_seek.hip; format in zh_seek_format.h) -------------------------------
+size_t cuda_zstd_seekable_max_size(size_t num_frames, size_t max_compressed_chunk_bytes, int with_checksums) {
+  return num_frames * max_compressed_chunk_bytes + (size_t)zh_seek_table_bytes(num_frames, with_checksums);
+}
+size_t cuda_zstd_seekable_pack_get_temp_size(size_t num_frames) { return zh::seek_pack_temp_bytes(num_frames); }
+
+int cuda_zstd_seekable_pack_async(const void *const *d_frame_ptrs, const size_t *d_frame_sizes, const int *d_frame_statuses,
+                                  const void *const *d_uncompressed_ptrs, const size_t *d_uncompressed_sizes, size_t num_frames,
+                                  size_t max_compressed_chunk_bytes, int with_checksums, void *d_out, size_t out_capacity, size_t *d_out_size,
+                                  int *d_status, void *d_temp, size_t temp_bytes, hipStream_t stream) {
+  if (!d_out || !d_out_size || !d_status || num_frames > ZH_SEEK_MAX_FRAMES) return c_err(Status::ERROR_INVALID_PARAMETER);
+  if (num_frames && (!d_frame_ptrs || !d_frame_sizes || !d_uncompressed_sizes || max_compressed_chunk_bytes == 0 ||
+                     (with_checksums && !d_uncompressed_ptrs)))
+    return c_err(Status::ERROR_INVALID_PARAMETER);
+  if (!d_temp || temp_bytes < zh::seek_pack_temp_bytes(num_frames)) return c_err(Status::ERROR_BUFFER_TOO_SMALL);
+  hipError_t const e = zh::seek_pack_launch(d_frame_ptrs, d_frame_sizes, d_frame_statuses, d_uncompressed_ptrs, d_uncompressed_sizes, num_frames,
+                                            max_compressed_chunk_bytes, with_checksums != 0, d_out, out_capacity, d_out_size, d_status, d_temp,
+                                            stream);
+  return e == hipSuccess ? 0 : c_err(Status::ERROR_CUDA_ERROR);
+}
+
+// The last 9 bytes of a stream in host or device memory, parsed on the host (the one small word
+// the read and info calls fetch; the table itself stays where it is).
+static int seek_fetch_footer(const void *buf, size_t size, bool dev, ZhSeekFooter &f, hipStream_t stream) {
+  if (!buf) return 2;
+  if (size < ZH_SEEK_OVERHEAD) return 6;
+  u8 foot[ZH_SEEK_FOOTER];
+  if (dev) {
+    if (hipMemcpyAsync(foot, (const u8 *)buf + size - ZH_SEEK_FOOTER, ZH_SEEK_FOOTER, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess)
+      return 4;
+  } else {
+    memcpy(foot, (const u8 *)buf + size - ZH_SEEK_FOOTER, ZH_SEEK_FOOTER);
+  }
+  return (int)zh_seek_parse_footer(foot, size, &f);
+}
+
+int cuda_zstd_seekable_info(const void *stream_buf, size_t size, size_t *num_frames, unsigned long long *total_uncompressed,
+                            unsigned int *max_frame_uncompressed, int *has_checksums) {
+  bool const dev = stream_buf && is_device_ptr(stream_buf);
+  ZhSeekFooter f;
+  int rc = seek_fetch_footer(stream_buf, size, dev, f, 0);
+  if (rc) return rc;
+  zh::SeekInfoRes r{};
+  if (dev) {
+    zh::SeekInfoRes *d_res = nullptr;
+    if (hipMalloc((void **)&d_res, sizeof(r)) != hipSuccess) return 3;
+    bool ok = hipMemsetAsync(d_res, 0, sizeof(r), 0) == hipSuccess && zh::seek_info_launch(stream_buf, size, (size_t)f.n, d_res, 0) == hipSuccess &&
+              hipMemcpy(&r, d_res, sizeof(r), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d_res);
+    if (!ok) return 4;
+  } else {
+    const u8 *const table = (const u8 *)stream_buf + (size - f.table);
+    if (zh_seek_check_header(table, &f) != ZH_SEEK_OK) r.bad = 1;
+    for (u64 i = 0; i < f.n; i++) {
+      u64 const c = zh_seek_ld32(table + 8 + i * f.entry), d = zh_seek_ld32(table + 8 + i * f.entry + 4);
+      if (!zh_seek_field_ok(c) || !zh_seek_field_ok(d)) { r.bad = 1; break; }
+      r.total_c += c;
+      r.total_u += d;
+      r.max_d = std::max(r.max_d, (u32)d);
+    }
+  }
+  if (r.bad || r.total_c + f.table != size) return 6;
+  if (num_frames) *num_frames = (size_t)f.n;
+  if (total_uncompressed) *total_uncompressed = r.total_u;
+  if (max_frame_uncompressed) *max_frame_uncompressed = r.max_d;
+  if (has_checksums) *has_checksums = (int)f.checksums;
+  return 0;
+}
+
+// Temp of a read that decodes at most max_jobs frames (max_jobs = num_frames always suffices)
+size_t cuda_zstd_seekable_read_get_temp_size_jobs(size_t num_frames, size_t max_jobs, size_t max_frame_uncompressed) {
+  return zh::seek_read_fixed_bytes(num_frames) + zh::seek_read_bounce_bytes(max_frame_uncompressed) +
+         ZstdBatchManager::get_batch_device_decompress_temp_size(std::min(max_jobs, num_frames), std::max<size_t>(max_frame_uncompressed, 1)) + 256;
+}
+size_t cuda_zstd_seekable_read_get_temp_size(size_t num_frames, size_t max_frame_uncompressed) {
+  return cuda_zstd_seekable_read_get_temp_size_jobs(num_frames, num_frames, max_frame_uncompressed);
+}
+
+int cuda_zstd_seekable_read(nvcomp_zstd_batch_manager_t *mgr, const void *d_stream, size_t size, unsigned long long offset, size_t length,
+                            void *d_out, size_t *written, int verify_checksums, void *d_temp, size_t temp_bytes, hipStream_t stream) {
+  if (written) *written = 0;
+  if (!mgr || !mgr->mgr || !d_stream || (length && !d_out)) return c_err(Status::ERROR_INVALID_PARAMETER);
+  ZhSeekFooter f;
+  int rc = seek_fetch_footer(d_stream, size, true, f, stream);
+  if (rc) return rc;
+  size_t const n = (size_t)f.n, fixed = zh::seek_read_fixed_bytes(n);
+  if (!d_temp || temp_bytes < fixed + 256) return 7;  // nothing launched
+  u8 *const base = (u8 *)(((uintptr_t)d_temp + 255) & ~(uintptr_t)255);
+  size_t const avail = temp_bytes - (size_t)(base - (u8 *)d_temp);
+  if (zh::seek_index_launch(d_stream, size, n, f.entry, offset, length, d_out, base, stream) != hipSuccess) return 4;
+  zh::SeekReadCtl ctl;
+  if (hipMemcpyAsync(&ctl, base, sizeof(ctl), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return 4;
+  if (ctl.status) return (int)ctl.status;
+  if (ctl.njobs == 0) return 0;  // length 0 (a valid table, nothing to decode)
+  // the decoder's workspace follows the bounce slots; sized now that the job count is known
+  size_t const bounce = zh::seek_read_bounce_bytes(ctl.max_d), max_out = std::max<size_t>(ctl.max_d, 1);
+  size_t const dec = ZstdBatchManager::get_batch_device_decompress_temp_size(ctl.njobs, max_out);
+  if (ctl.njobs > n || avail < fixed + bounce + dec) return 7;  // the decoder is not launched
+  zh::SeekJobs const j = zh::seek_read_jobs(base, n);
+  Status const s = mgr->mgr->batch_manager().decompress_batch_device(j.in_ptrs, j.in_sizes, j.out_caps, max_out, ctl.njobs, j.out_ptrs, j.out_sizes,
+                                                                     j.statuses, base + fixed + bounce, dec, stream);
+  if (s != Status::SUCCESS) return c_err(s);
+  if (zh::seek_trim_launch(d_stream, size, n, f.entry, ctl.njobs, offset, length, d_out, verify_checksums, base, stream) != hipSuccess) return 4;
+  if (hipMemcpyAsync(&ctl, base, sizeof(ctl), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return 4;
+  if (ctl.errkey != ~0ull) return (int)(ctl.errkey & 0xFFu);
+  if (written) *written = length;
+  return 0;
 }
 
 const char *cuda_zstd_hip_version(void) { return "cuda_zstd_hip 0.2.0 (gfx950)"; }

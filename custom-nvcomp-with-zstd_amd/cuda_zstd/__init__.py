@@ -96,6 +96,13 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_hip_profile_enable": (None, [i]),
             "cuda_zstd_hip_profile_collect": (i, [ctypes.POINTER(ctypes.c_double)]),
             "cuda_zstd_hip_kernel_lds_bytes": (ctypes.c_uint, [i]),
+            "cuda_zstd_seekable_max_size": (sz, [sz, sz, i]),
+            "cuda_zstd_seekable_pack_get_temp_size": (sz, [sz]),
+            "cuda_zstd_seekable_pack_async": (i, [vp, vp, vp, vp, vp, sz, sz, i, vp, sz, vp, vp, vp, sz, vp]),
+            "cuda_zstd_seekable_info": (i, [vp, sz, psz, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_uint), pi]),
+            "cuda_zstd_seekable_read_get_temp_size": (sz, [sz, sz]),
+            "cuda_zstd_seekable_read_get_temp_size_jobs": (sz, [sz, sz, sz]),
+            "cuda_zstd_seekable_read": (i, [vp, vp, sz, ctypes.c_ulonglong, sz, vp, psz, i, vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -459,6 +466,28 @@ class BatchedCompressor:
         if rc:
             raise ZstdError(rc, "nvcomp_zstd_batched_compress_async_v5")
 
+    @staticmethod
+    def seekable_max_size(num_frames: int, max_compressed_chunk: int, checksums: bool = False) -> int:
+        return lib().cuda_zstd_seekable_max_size(num_frames, max_compressed_chunk, 1 if checksums else 0)
+
+    @staticmethod
+    def pack_temp_size(num_frames: int) -> int:
+        return lib().cuda_zstd_seekable_pack_get_temp_size(num_frames)
+
+    def pack_seekable_async(self, d_frame_ptrs, d_frame_sizes, d_frame_status, d_in_ptrs, d_in_sizes, max_compressed_chunk, out, d_out_size,
+                            d_status, temp, checksums: bool = False, stream=None):
+        """Stream-ordered pack of compress_async's frames into one seekable stream in `out`
+        (cuda_zstd_seekable_pack_async): the frames back to back, then the seek table.  Every
+        argument is a device tensor; d_out_size (int64[1]) and d_status (int32[1]) receive the
+        stream's size and an nvcomp-style code.  d_in_ptrs is only read with checksums."""
+        n = d_frame_ptrs.numel()
+        rc = lib().cuda_zstd_seekable_pack_async(
+            d_frame_ptrs.data_ptr(), d_frame_sizes.data_ptr(), d_frame_status.data_ptr() if d_frame_status is not None else None,
+            d_in_ptrs.data_ptr() if d_in_ptrs is not None else None, d_in_sizes.data_ptr(), n, max_compressed_chunk, 1 if checksums else 0,
+            out.data_ptr(), out.numel(), d_out_size.data_ptr(), d_status.data_ptr(), temp.data_ptr(), temp.numel(), _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_seekable_pack_async")
+
 
 class StreamingManager:
     """ZstdStreamingManager over the C ABI (cuda_zstd_stream_*; reference
@@ -632,6 +661,97 @@ def decompress(frame, capacity: int = None, stream=None):
 
 def decompress_batch(frames, capacities=None, stream=None):
     return Manager(3).decompress_batch(frames, capacities, stream)
+
+
+def seekable_compress(data, frame_size: int = 65536, level: int = 3, checksums: bool = False, stream=None):
+    """Compress `data` as a Zstandard seekable stream: independent frames of `frame_size` bytes
+    of content, then the seek table.  compress_async and pack_seekable_async are enqueued on one
+    stream with no synchronisation between them; the only wait is for the stream's size, to
+    trim the returned device tensor.  Host bytes / numpy in -> bytes out."""
+    if _is_host(data):
+        return _host_bytes(seekable_compress(_to_device(data), frame_size, level, checksums, stream))
+    torch = _torch()
+    if frame_size <= 0:
+        raise ZstdError(INVALID, "seekable_compress frame_size")
+    data = data.contiguous().view(torch.uint8).reshape(-1)
+    total = data.numel()
+    n = (total + frame_size - 1) // frame_size
+    dev = data.device
+    comp = BatchedCompressor(level, frame_size)
+    slot = (comp.max_out(frame_size) + 255) // 256 * 256
+    cap = BatchedCompressor.seekable_max_size(n, slot, checksums)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    out_size = torch.zeros(1, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    s = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(s):
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        in_ptrs = data.data_ptr() + idx * frame_size
+        in_sizes = torch.clamp(total - idx * frame_size, max=frame_size)
+        slots = torch.empty(max(n * slot, 1), dtype=torch.uint8, device=dev)
+        f_ptrs = slots.data_ptr() + idx * slot
+        f_sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+        f_status = torch.zeros(n, dtype=torch.int32, device=dev)
+        temp = torch.empty(max(comp.temp_size(n, frame_size), BatchedCompressor.pack_temp_size(n), 256), dtype=torch.uint8, device=dev)
+        if n:
+            comp.compress_async(in_ptrs, in_sizes, frame_size, f_ptrs, f_sizes, f_status, temp, s)
+        comp.pack_seekable_async(f_ptrs, f_sizes, f_status, in_ptrs, in_sizes, slot, out, out_size, status, temp, checksums, s)
+        for t in (data, slots, temp, out):
+            t.record_stream(s)
+        res = torch.stack([out_size[0], status[0].to(torch.int64)]).cpu()  # waits for the stream
+    if int(res[1]):
+        raise ZstdError(int(res[1]), "seekable_compress")
+    return out[: int(res[0])]
+
+
+class SeekableReader:
+    """Random access into a Zstandard seekable stream held in device memory (host bytes are
+    uploaded once, and reads then give bytes back).  `manager`: a BatchedCompressor /
+    BatchedDecompressor whose handle (and dictionary) decodes the frames."""
+
+    def __init__(self, buf, manager=None):
+        torch = _torch()
+        self._host = _is_host(buf)
+        self._buf = _to_device(buf) if self._host else buf.contiguous().view(torch.uint8).reshape(-1)
+        self._mgr = manager if manager is not None else BatchedDecompressor()
+        n, tot, mx, ck = ctypes.c_size_t(0), ctypes.c_ulonglong(0), ctypes.c_uint(0), ctypes.c_int(0)
+        rc = lib().cuda_zstd_seekable_info(self._buf.data_ptr() if self._buf.numel() else None, self._buf.numel(), ctypes.byref(n), ctypes.byref(tot),
+                                           ctypes.byref(mx), ctypes.byref(ck))
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_seekable_info")
+        self.num_frames, self.size, self.max_frame, self.has_checksums = n.value, tot.value, mx.value, bool(ck.value)
+        self._temp = None
+
+    def _read(self, offset: int, length: int, verify: bool, jobs: int, stream):
+        torch = _torch()
+        need = lib().cuda_zstd_seekable_read_get_temp_size_jobs(self.num_frames, jobs, self.max_frame)
+        if self._temp is None or self._temp.numel() < need:
+            self._temp = None
+            self._temp = torch.empty(need, dtype=torch.uint8, device=self._buf.device)
+        out = torch.empty(max(length, 1), dtype=torch.uint8, device=self._buf.device)
+        written = ctypes.c_size_t(0)
+        rc = lib().cuda_zstd_seekable_read(self._mgr._h, self._buf.data_ptr(), self._buf.numel(), offset, length, out.data_ptr(),
+                                           ctypes.byref(written), 1 if verify else 0, self._temp.data_ptr(), self._temp.numel(),
+                                           _stream_ptr(stream))
+        return rc, out[: written.value]
+
+    def read(self, offset: int, length: int, verify: bool = False, stream=None):
+        """Bytes [offset, offset + length) of the content.  Only the frames that cover the range
+        are decoded; verify=True checks them against the table's checksums (when it has them)."""
+        if offset < 0 or length < 0:
+            raise ZstdError(INVALID, "SeekableReader.read")
+        # temp for the frames an evenly split stream would touch; the full table's on TOO_SMALL
+        avg = max(1, self.size // max(self.num_frames, 1))
+        jobs = min(self.num_frames, 4 * (length // avg + 2))
+        rc, out = self._read(offset, length, verify, jobs, stream)
+        if rc == TOO_SMALL and jobs < self.num_frames:
+            rc, out = self._read(offset, length, verify, self.num_frames, stream)
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_seekable_read")
+        return _host_bytes(out) if self._host else out
+
+    def read_all(self, verify: bool = False, stream=None):
+        return self.read(0, self.size, verify, stream)
 
 
 def hybrid_compress(data, level: int = 3) -> bytes:

@@ -198,6 +198,44 @@ int cuda_zstd_write_metadata_frame(void *dst, size_t capacity, int compression_l
 int cuda_zstd_extract_metadata(const void *src, size_t size, unsigned int *compression_level, unsigned long long *uncompressed_size,
                                unsigned int *dictionary_id, int *has_checksum);
 
+/* ---------------- seekable streams ----------------
+ * The Zstandard seekable format: frame_0 .. frame_{N-1}, then one skippable frame holding the
+ * seek table (all little-endian):
+ *   u32 0x184D2A5E | u32 Frame_Size = N*E + 9 | N x { u32 Compressed_Size; u32 Decompressed_Size;
+ *   [u32 Checksum] } | u32 N | u8 descriptor (bit 7: checksums; bits 6..2 reserved, 0) | u32 0x8F92EAB1
+ * E = 8 without checksums, 12 with; Checksum = low 32 bits of XXH64 (seed 0) of the frame's
+ * decompressed bytes.  Stock zstd decoders decode the whole stream and skip the table.
+ * Limits: N <= 0x8000000, each size field <= 0x40000000.
+ *
+ * pack_async: stream-ordered, every array a device array (what
+ * nvcomp_zstd_batched_compress_async_v5 leaves behind plus the chunks' uncompressed sizes;
+ * d_uncompressed_ptrs only with checksums).  *d_out_size = bytes of the stream and *d_status = 0,
+ * or *d_out_size = 0 and *d_status = the first failing item's status, 2 for an item size of 0 or
+ * over max_compressed_chunk_bytes or the format's limits, 7 when out_capacity is too small.
+ * Nothing of d_out is written on failure, and nothing past *d_out_size on success.
+ *
+ * info: stream_buf in host or device memory; 6 for a damaged table.
+ * read: decodes [offset, offset + length) of the stream's content into d_out through the batched
+ * GPU decoder (with the handle's dictionary, if set); the table is parsed and validated on the
+ * device.  Blocking.  *written (host) = length on success, else 0.  Codes: 2 a range past the
+ * content (d_out untouched), 6 a damaged table, 7 a temp buffer too small (below the table-sized
+ * part: nothing is launched; below the part sized by the frames the range covers: no decode is
+ * launched), 10 a checksum mismatch with verify_checksums on a checksummed stream, or the first
+ * failing frame's decoder code.  read_get_temp_size covers any range; _jobs covers ranges that
+ * touch at most max_jobs frames with content. */
+size_t cuda_zstd_seekable_max_size(size_t num_frames, size_t max_compressed_chunk_bytes, int with_checksums);
+size_t cuda_zstd_seekable_pack_get_temp_size(size_t num_frames);
+int cuda_zstd_seekable_pack_async(const void *const *d_frame_ptrs, const size_t *d_frame_sizes, const int *d_frame_statuses,
+                                  const void *const *d_uncompressed_ptrs, const size_t *d_uncompressed_sizes, size_t num_frames,
+                                  size_t max_compressed_chunk_bytes, int with_checksums, void *d_out, size_t out_capacity, size_t *d_out_size,
+                                  int *d_status, void *d_temp, size_t temp_bytes, hipStream_t stream);
+int cuda_zstd_seekable_info(const void *stream_buf, size_t size, size_t *num_frames, unsigned long long *total_uncompressed,
+                            unsigned int *max_frame_uncompressed, int *has_checksums);
+size_t cuda_zstd_seekable_read_get_temp_size(size_t num_frames, size_t max_frame_uncompressed);
+size_t cuda_zstd_seekable_read_get_temp_size_jobs(size_t num_frames, size_t max_jobs, size_t max_frame_uncompressed);
+int cuda_zstd_seekable_read(nvcomp_zstd_batch_manager_t *mgr, const void *d_stream, size_t size, unsigned long long offset, size_t length,
+                            void *d_out, size_t *written, int verify_checksums, void *d_temp, size_t temp_bytes, hipStream_t stream);
+
 /* ---------------- library info ---------------- */
 const char *cuda_zstd_hip_version(void);
 /* Per-kernel timing with HIP events recorded on the launch stream (bench.py roofline).
