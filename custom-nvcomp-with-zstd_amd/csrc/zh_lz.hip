@@ -34,9 +34,11 @@
 //                 the walk meets the previous one -- exactly the serial parse; then the
 //                 window's match list.
 //   wave 1        after its lengths: window k-2's catch-up and sequence records.
-//   after X       span-top take decisions (each wave its own); window k-2's literals.
+//   waves 14, 15  after their insertion: window k-3's literal bytes, a lane = one dword of the
+//                 window (lit_rounds; zh_litpack.h).
 #include "zh_common.h"
 #include "zh_hash.h"
+#include "zh_litpack.h"
 
 #include <algorithm>
 #include <vector>
@@ -115,17 +117,13 @@ __device__ __forceinline__ u32 cidx(u32 i) { return i; }
 // two cinfo buffers: window k's candidates / match info in buffer k & 1 (the parse of window k
 // overlaps the lengths of window k + 1)
 constexpr u32 OFF_HM = OFF_CI + 2 * 4 * CI_WORDS;    // per buffer u64 per round: take masks (see span_lengths)
-// The literal bytes of a window are extracted (ZH_LIT_INS = 0) by the worker waves after barrier X
-// of the step that wrote its records, or (1) one step later by the inserter waves, before X, once
-// they have built the next window's tables (the step's post-X phase shrinks to the span tops).
-// Round 6 (profiles/r06i_lit_ins_ab.json): level 3 K1 10.36 -> 10.12 ms, level 1 8.02 -> 7.52 ms;
-// the step 11.66 k -> 10.95 k cycles (tools/timeline.py).
-#ifndef ZH_LIT_INS
-#define ZH_LIT_INS 1
-#endif
-constexpr u32 LM_BUFS = ZH_LIT_INS ? 3 : 2;         // windows whose literal bits are alive at once
-constexpr u32 LB_BUFS = ZH_LIT_INS ? 2 : 1;         // literal prefix-count buffers
-constexpr u32 STEPS_EXTRA = ZH_LIT_INS ? 3 : 2;     // loop steps per block: windows + STEPS_EXTRA
+// The literal bytes of a window are extracted by the inserter waves, one step after the step that
+// wrote its records, once they have built the next window's tables (lit_rounds below).  The worker
+// waves did it after the records until round 6 (profiles/r06i_lit_ins_ab.json: level 3 K1 10.36 ->
+// 10.12 ms, level 1 8.02 -> 7.52 ms; the step 11.66 k -> 10.95 k cycles, tools/timeline.py).
+constexpr u32 LM_BUFS = 3;          // windows whose literal bits are alive at once
+constexpr u32 LB_BUFS = 2;          // literal prefix-count buffers
+constexpr u32 STEPS_EXTRA = 3;      // loop steps per block: windows + STEPS_EXTRA
 constexpr u32 OFF_SEGM = OFF_HM + 2 * 8 * NROUND;    // per window (mod LM_BUFS), per walk segment (u32 each):
 // the literal bits left after catch-up
 __device__ __forceinline__ u32 segm(u32 par) { return par * NSEG; }
@@ -139,7 +137,7 @@ constexpr u32 OFF_MISC = OFF_XQ + 2 * XQ_CAP * NWW;  // [2 par + 0] matches, [2 
 constexpr u32 OFF_LB = OFF_MISC + 4 * 16;            // window k - 2's literal prefix counts per walk
                                                      // segment (+ the window's total), for the literal phase
 constexpr u32 LB_WORDS = NSEG + 4;
-// One barrier per window step (ZH_ONE_BARRIER, needs ZH_LIT_INS): the take bits at the worker
+// One barrier per window step (ZH_ONE_BARRIER): the take bits at the worker
 // waves' span tops (lazy rule: they need the next span's first info) are decided by wave 0 at the
 // start of the window's parse in the next step (and by every wave in the probe step), and the
 // inserters dump the next window's candidates once wave 0 has read the previous window's match info
@@ -149,7 +147,6 @@ constexpr u32 LB_WORDS = NSEG + 4;
 #ifndef ZH_ONE_BARRIER
 #define ZH_ONE_BARRIER 1
 #endif
-static_assert(!ZH_ONE_BARRIER || ZH_LIT_INS, "one barrier per step needs the literals on the inserters");
 constexpr u32 K1_LDS = OFF_LB + 4 * LB_WORDS * LB_BUFS;
 constexpr u32 ML_LO = 11, ML_LEN = 22, ML_OFF = 29, ML_CUM = 45;  // match-list entry: start [0, 11) | ...
 constexpr u32 MISC_WNM = 0;   // misc[par]: matches of the window of that parity (its match list's length)
@@ -1034,27 +1031,75 @@ constexpr u32 WIN_BARRIERS = 1;  // X
 // The long table's wave in modes 1, 2 (the short table only): no insertion, only the step's two
 // barriers (P, X) and the probe exit, so the workgroup's barrier sequence stays the same.
 // Returns whether the loop ended at the incompressibility probe.
-// Literal bytes of the window at staged position wsj (ZH_LIT_INS): rounds r = r0, r0 + rs, ... of
-// 64 positions; lm = its literal bits per walk segment, lb = their exclusive prefix counts (+ the
-// window's total at lb[NSEG]); nlit = the literals before the window.  Four rounds' LDS reads per
-// round trip.
-__device__ __forceinline__ void lit_rounds(const u8 *in, const u32 *lm, const u32 *lb, u8 *lit_out, u32 nlit, u32 wsj, u32 r0, u32 rs, u32 lane) {
+// Literal bytes of the window at staged position wsj: literal rounds [r0, r0 + nr) of LIT_RP
+// positions, a lane = one dword of the window (window starts are multiples of ZH_WINDOW in staged
+// coordinates, so the dword is aligned whatever `pre` is).  lm = the window's literal bits per walk
+// segment, lb = their exclusive prefix counts (+ the window's total at lb[NSEG]); nlit = the
+// literals before the window.  The eight lanes of a segment read its two words from one LDS address
+// (a broadcast); a lane's four bits and its output offset (the segment's count + the bits below its
+// own) are per-lane values, so the round needs no cross-lane operation.  The lane's 0-4 literal
+// bytes are compacted with one v_perm_b32 (zh_litpack.h) and leave as byte stores.  Positions
+// below `pre` and at or past n have no literal bit (in[n .. n + 15] is zero padding; a window's
+// last rounds may read table bytes past it, never stored).  LIT_B rounds' LDS reads per round trip.
+// Against one byte per lane and round (lit_rounds_pos below): the inserters' literal phase 2.6 k ->
+// 1.4 k cycles per step, K1 9.71 -> 9.54 ms at level 3; staging the compacted bytes in an LDS strip
+// for dword stores measured 10.43 ms (profiles/k1_lit_dword_ab.json).
+constexpr u32 LIT_RP = 256;                    // positions per literal round: 64 lanes x 4
+constexpr u32 LIT_ROUNDS = ZH_WINDOW / LIT_RP;  // literal rounds per window
+constexpr u32 LIT_B = 4;
+static_assert(LIT_RP == 8 * SEGP && ZH_WINDOW % 4 == 0 && (LIT_ROUNDS / 2) % LIT_B == 0, "literal rounds: 8 lanes per segment, whole batches per half window");
+__device__ __forceinline__ void lit_rounds(const u32 *in32, const u32 *lm, const u32 *lb, u8 *lit_out, u32 nlit, u32 wsj, u32 r0, u32 nr, u32 lane) {
+  u32 const sh = 4u * (lane & 7u), below = (1u << sh) - 1u;
+  const u32 *const src = in32 + (wsj >> 2) + lane;
+  const u32 *const lms = lm + (lane >> 3), *const lbs = lb + (lane >> 3);
+  for (u32 rb = r0; rb < r0 + nr; rb += LIT_B) {
+    u32 sw[LIT_B], lbr[LIT_B], dw[LIT_B];
+#pragma unroll
+    for (u32 j = 0; j < LIT_B; j++) {
+      sw[j] = lms[8 * (rb + j)];
+      lbr[j] = lbs[8 * (rb + j)];
+      dw[j] = src[64 * (rb + j)];  // (every lane: the loads leave before the masks are tested)
+    }
+#pragma unroll
+    for (u32 j = 0; j < LIT_B; j++) __asm__ volatile("" : "+v"(dw[j]));  // (not sunk into the branches)
+#pragma unroll
+    for (u32 j = 0; j < LIT_B; j++) {
+      u32 const m4 = (sw[j] >> sh) & 15u, cnt = (u32)__popc(m4);
+      u32 const pk = zh_litpack(dw[j], m4);
+      u8 *const q = lit_out + (nlit + lbr[j] + (u32)__popc(sw[j] & below));
+      if (cnt >= 1) {
+        q[0] = (u8)pk;
+        if (cnt >= 2) {
+          q[1] = (u8)(pk >> 8);
+          if (cnt >= 3) {
+            q[2] = (u8)(pk >> 16);
+            if (cnt >= 4) q[3] = (u8)(pk >> 24);
+          }
+        }
+      }
+    }
+  }
+}
+// The same rounds with lanes = positions, four 64-position rounds per literal round: the round's
+// mask and prefix count are wave-uniform (readfirstlane), a lane's rank comes from mbcnt, one byte
+// store per round.  Modes 1 and 2 keep this form: there the idle long-table wave extracts whole
+// windows beside the parse wave, which sets the step, and with the dword form level 1 measured
+// slower (K1 7.21 -> 7.29 ms, profiles/k1_lit_dword_ab.json) although the extraction itself is shorter.
+__device__ __forceinline__ void lit_rounds_pos(const u8 *in, const u32 *lm, const u32 *lb, u8 *lit_out, u32 nlit, u32 wsj, u32 r0, u32 nr, u32 lane) {
   constexpr u32 B = 4;
-  for (u32 rb = r0; rb < NROUND; rb += B * rs) {
+  for (u32 rb = 4 * r0; rb < 4 * (r0 + nr); rb += B) {
     u64 mw[B];
     u32 lbr[B], by[B];
 #pragma unroll
     for (u32 j = 0; j < B; j++) {
-      u32 const r = min(rb + rs * j, NROUND - 1u);
-      mw[j] = *(const u64 *)&lm[2 * r];
-      lbr[j] = (u32)__builtin_amdgcn_readfirstlane(lb[2 * r]);
-      by[j] = in[wsj + 64 * r + lane];
+      mw[j] = *(const u64 *)&lm[2 * (rb + j)];
+      lbr[j] = (u32)__builtin_amdgcn_readfirstlane(lb[2 * (rb + j)]);
+      by[j] = in[wsj + 64 * (rb + j) + lane];
     }
 #pragma unroll
     for (u32 j = 0; j < B; j++) __asm__ volatile("" : "+v"(by[j]));
 #pragma unroll
     for (u32 j = 0; j < B; j++) {
-      if (rb + rs * j >= NROUND) continue;
       u64 const m = ((u64)(u32)__builtin_amdgcn_readfirstlane((u32)(mw[j] >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((u32)mw[j]);
       if ((m >> lane) & 1ull) {
         u32 const rank = __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
@@ -1063,26 +1108,30 @@ __device__ __forceinline__ void lit_rounds(const u8 *in, const u32 *lm, const u3
     }
   }
 }
-// The literal work of an inserter wave in step k (ZH_LIT_INS): window k - 3's rounds r0, r0 + rs, ...
+// The literal work of an inserter wave in step k: window k - 3's literal rounds [r0, r0 + nr), a
+// lane a dword (DW, mode 0) or a position
+template <bool DW>
 struct LitJob {
-  const u8 *in;
+  const u32 *in32;
   u32 *sgm, *lbx;
   u8 *lit_out;
-  u32 wstart, n, pre, r0, rs;
+  u32 wstart, n, pre, r0, nr;
   u32 nlit;  // literals of the windows before the next one (running; every inserter keeps the total)
   __device__ __forceinline__ void step(u32 k, u32 lane) {
-    if constexpr (ZH_LIT_INS) {
-      if (k < 3) return;
-      u32 const j = k - 3, wsj = wstart + j * ZH_WINDOW;
-      if (wsj >= n || min(wsj + ZH_WINDOW, n) <= pre) return;
-      const u32 *const lm = sgm + segm(j % LM_BUFS);
-      const u32 *const lb = lbx + (j & 1u) * LB_WORDS;
-      if (rs) lit_rounds(in, lm, lb, lit_out, nlit, wsj, r0, rs, lane);
-      nlit += (u32)__builtin_amdgcn_readfirstlane(lb[NSEG]);
+    if (k < 3) return;
+    u32 const j = k - 3, wsj = wstart + j * ZH_WINDOW;
+    if (wsj >= n || min(wsj + ZH_WINDOW, n) <= pre) return;
+    const u32 *const lm = sgm + segm(j % LM_BUFS);
+    const u32 *const lb = lbx + (j & 1u) * LB_WORDS;
+    if (nr) {
+      if constexpr (DW) lit_rounds(in32, lm, lb, lit_out, nlit, wsj, r0, nr, lane);
+      else lit_rounds_pos((const u8 *)in32, lm, lb, lit_out, nlit, wsj, r0, nr, lane);
     }
+    nlit += (u32)__builtin_amdgcn_readfirstlane(lb[NSEG]);
   }
 };
-__device__ __forceinline__ bool idle_inserter_loop(u32 *misc_, u32 n, u32 wstart, u32 kprobe, u32 e0p, LitJob &lj, u32 lane, bool lazy) {
+template <class LJ>
+__device__ __forceinline__ bool idle_inserter_loop(u32 *misc_, u32 n, u32 wstart, u32 kprobe, u32 e0p, LJ &lj, u32 lane, bool lazy) {
   u32 const nwin = (n - wstart + ZH_WINDOW - 1) / ZH_WINDOW;
   for (u32 k = 0; k < nwin + STEPS_EXTRA; k++) {
     if (probe_dead(misc_, k, kprobe)) return true;
@@ -1094,9 +1143,9 @@ __device__ __forceinline__ bool idle_inserter_loop(u32 *misc_, u32 n, u32 wstart
   }
   return false;
 }
-template <bool LONG, bool TWO>
+template <bool LONG, bool TWO, class LJ>
 __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, u32 *misc_, u32 n, u32 lim, u32 lane, u32 *dbg, u32 wstart,
-                                              u32 pmin, u32 span_s, u32 span_e, u32 kskip0, u32 kprobe, u32 e0p, LitJob &lj, bool lazy) {
+                                              u32 pmin, u32 span_s, u32 span_e, u32 kskip0, u32 kprobe, u32 e0p, LJ &lj, bool lazy) {
   u32 creg[NCR];
   if (span_s < span_e) insert_span<LONG>(in32, T, span_s, span_e, lane);
   // (the first window: its own instantiation, with pmin and no barriers to take)
@@ -1519,10 +1568,11 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
     // is arbitrated ... by priority, then age").
     // (priority 0 or 1 measured the same, profiles/r05l_k1_priority_ab.json)
     __builtin_amdgcn_s_setprio(2);
-    // literal rounds (ZH_LIT_INS): both inserters half each in mode 0, else the idle long-table wave all
+    // literal rounds: in mode 0 each inserter a contiguous half of the window, else the idle
+    // long-table wave all of it
     bool const lw = tid < INS_TID + 64;
-    LitJob lj{in, (u32 *)(smem + OFF_SEGM), (u32 *)(smem + OFF_LB), ws.lits(b), wstart, n, pre,
-              two_tables<MODE>() ? (lw ? 0u : 1u) : 0u, two_tables<MODE>() ? 2u : (lw ? 1u : 0u), 0u};
+    LitJob<two_tables<MODE>()> lj{in32, (u32 *)(smem + OFF_SEGM), (u32 *)(smem + OFF_LB), ws.lits(b), wstart, n, pre,
+              two_tables<MODE>() && !lw ? LIT_ROUNDS / 2 : 0u, two_tables<MODE>() ? LIT_ROUNDS / 2 : (lw ? LIT_ROUNDS : 0u), 0u};
     if (tid >= INS_TID + 64)
       dead = inserter_loop<false, two_tables<MODE>()>(in32, TS, ci8, misc, n, lim, lane, ws.dbg(b), wstart, pmin, span_s, span_e, kskip0, kprobe, e0p, lj,
                                                       MODE != 2);
@@ -1534,7 +1584,6 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
     if (!dead) return next_b;
   } else {
   u64 *const seq_out = ws.seq(b);
-  u8 *const lit_out = ws.lits(b);
   u32 nseq_tot = 0, nlit_tot = 0, e_in = pre;
   u32 const tid_ = tid;
   u32 const wave = tid >> 6;
@@ -1552,8 +1601,7 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
   // Step k (window j at wstart + j * ZH_WINDOW, parity j & 1):
   //   phase A  lengths of window k (waves 1..13) | span-top take decisions and parse of window
   //            k - 1 (wave 0) | catch-up and sequence records of window k - 2 (REC_WAVE)
-  //   (ZH_ONE_BARRIER=0 only: X, then the take decisions at window k's span tops, each wave its
-  //   own, and without ZH_LIT_INS the literals of window k - 2, lanes = positions)
+  //   (ZH_ONE_BARRIER=0 only: X, then the take decisions at window k's span tops, each wave its own)
   u32 m3 = 0;  // k mod LM_BUFS
   bool skp_prev = false;  // (ZH_ONE_BARRIER) window k - 1 was a miss-skip window (its span tops)
   for (u32 k = 0; k < nwin + STEPS_EXTRA; k++, m3 = m3 + 1 == LM_BUFS ? 0u : m3 + 1) {
@@ -1577,9 +1625,10 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
     u32 *const ciK = ci0 + kb * CI_WORDS, *const ciP = ci0 + (kb ^ 1u) * CI_WORDS;
     u64 *const tmK = hm + kb * NROUND, *const tmP = hm + (kb ^ 1u) * NROUND;
     // window k - 1's literal bits (the walk's), window k - 2's (after its catch-up)
-    u32 *const lmP = sgm + segm(LM_BUFS == 2 ? (kb ^ 1u) : (m3 == 0 ? 2u : m3 - 1u));
-    u32 *const lmQ = sgm + segm(LM_BUFS == 2 ? kb : (m3 == 0 ? 1u : m3 == 1 ? 2u : 0u));
-    u32 *const lbxq = lbx + (LB_BUFS == 2 ? kb : 0u) * LB_WORDS;  // window k - 2's prefix counts
+    static_assert(LM_BUFS == 3 && LB_BUFS == 2, "literal buffer rotation");
+    u32 *const lmP = sgm + segm(m3 == 0 ? 2u : m3 - 1u);
+    u32 *const lmQ = sgm + segm(m3 == 0 ? 1u : m3 == 1 ? 2u : 0u);
+    u32 *const lbxq = lbx + kb * LB_WORDS;  // window k - 2's prefix counts
     u64 *const mlP = mlist + (kb ^ 1u) * ML_CAP, *const mlQ = mlist + kb * ML_CAP;
     k1_barrier();  // P: candidates of window k in buffer k & 1
     TL_MARK(0);
@@ -1753,45 +1802,10 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
     }
     if (ZH_ONE_BARRIER) {
       // (the records wave keeps the totals)
-    } else if (ZH_LIT_INS && prev2) {
+    } else if (prev2) {
       // (the inserters extract window k - 2's literals in step k + 1)
       nlit_tot += (u32)__builtin_amdgcn_readfirstlane(lbxq[NSEG]);
       nseq_tot += __builtin_amdgcn_readfirstlane(misc[MISC_WNM + kb]);
-    } else if (prev2) {
-      // ---- literals of window k - 2, lanes = positions (round r = segments 2r, 2r + 1)
-      u32 const nm = __builtin_amdgcn_readfirstlane(misc[MISC_WNM + kb]);
-#ifdef ZH_EXP_NOLITPHASE
-      if (true) { nseq_tot += nm; } else  // (experiment: the literal phase's upper bound; output wrong)
-#endif
-      {
-      // the wave's rounds r = wave + NWW j: every LDS read of them issued first (one round trip)
-      constexpr u32 LR = (NROUND + NWW - 1) / NWW;
-      u64 mw[LR];
-      u32 lbr[LR], by[LR];
-#pragma unroll
-      for (u32 j = 0; j < LR; j++) {
-        u32 const r = min(wave + NWW * j, NROUND - 1u);
-        mw[j] = *(const u64 *)&lmQ[2 * r];
-        lbr[j] = (u32)__builtin_amdgcn_readfirstlane(lbx[2 * r]);
-        by[j] = in[wsq + 64 * r + lane];  // (every lane: the loads leave before the masks are tested)
-      }
-#pragma unroll
-      for (u32 j = 0; j < LR; j++) __asm__ volatile("" : "+v"(by[j]));  // (not sunk into the branches)
-#pragma unroll
-      for (u32 j = 0; j < LR; j++) {
-        if (wave + NWW * j >= NROUND) continue;
-        u64 const lm = ((u64)(u32)__builtin_amdgcn_readfirstlane((u32)(mw[j] >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((u32)mw[j]);
-        if ((lm >> lane) & 1ull) {
-          u32 const rank = __builtin_amdgcn_mbcnt_hi((u32)(lm >> 32), __builtin_amdgcn_mbcnt_lo((u32)lm, 0u));
-#ifndef ZH_EXP_NOLIT
-          lit_out[nlit_tot + lbr[j] + rank] = (u8)by[j];
-#endif
-        }
-      }
-      vpad<ZH_PAD_L>(nm);
-      nlit_tot += (u32)__builtin_amdgcn_readfirstlane(lbx[NSEG]);
-      nseq_tot += nm;
-      }
     }
     ZH_STAMP(st_E);
     TL_MARK(4);
