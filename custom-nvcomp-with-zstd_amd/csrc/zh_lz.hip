@@ -620,7 +620,8 @@ __device__ __forceinline__ u32 ld4_before(const u32 *in32, u32 a) {
 // ---- match lengths, lanes = positions -------------------------------------------------------
 // A worker wave takes a span of consecutive 64-position rounds in three passes:
 //  A  (rounds high to low) per position and candidate the common prefix of the first 8 bytes
-//     and whether p+1's candidate continues p's (then lcp(p) = 1 + lcp(p+1)); chain ends
+//     (long table: only whether all 8 are equal) and whether p+1's candidate continues p's
+//     (then lcp(p) = 1 + lcp(p+1)), as lane masks combined on the scalar unit; chain ends
 //     with 8 matching bytes go to the wave's extension queue (flushed 64 at a time);
 //  B  the queued chain ends extended, lanes = queue entries, results into their cinfo byte;
 //  C  (rounds high to low) lengths from the chain structure -> match info in place.
@@ -634,7 +635,9 @@ constexpr u32 MAX_RW = 3;   // rounds per worker wave
 // 9/9/7/7 11.86, 8/9/8/7 11.73, 8/8/8/8 11.61, 8/7/8/9 12.29 (round 4).  Round 5, SIMD 1's waves
 // 1/5/9/13 (13 also computes the window's lookahead): 2/2/2/2 10.69 ms, 2/3/2/1 10.38, 1/3/3/1
 // 10.37, 2/2/3/1 10.37; moving rounds between SIMDs or 4-round waves (a larger unrolled span)
-// measured slower (`profiles/r05z_round_table_ab.json`).
+// measured slower (`profiles/r05z_round_table_ab.json`).  With the shorter length phase
+// (`profiles/k1_length_phase_diet_ab.json`, K1 9.02 ms): a round moved onto SIMD 2 or 3 9.38 ms,
+// off them onto SIMD 1 or 0 9.13 / 9.19 ms.
 __device__ __forceinline__ u32 rounds_of(u32 w) {
 #ifdef ZH_RTAB
   return (u32)(((unsigned long long)(ZH_RTAB) >> (2 * w)) & 3u);
@@ -654,81 +657,128 @@ __device__ __forceinline__ void xq_flush(const u32 *in32, u32 *ci, const u16 *xq
   if (act) ((u8 *)ci)[4 * cidx(i) + (sh >> 3)] = (u8)x;
 }
 
-// Flags of a position after pass A
-enum : u32 { LF_FL = 1u << 8, LF_FS = 1u << 9, LF_XL = 1u << 10, LF_XS = 1u << 11, LF_SL = 1u << 12 };
+// Flags of a position after pass A (level 1, span_lengths_l1)
+enum : u32 { LF_FS = 1u << 9, LF_XS = 1u << 11 };
 
-// The match lengths of rounds [r_lo, r_hi) (r_hi - r_lo <= MAX_RW): candidates in cinfo ->
-// match info (off << 8 | len, 0 = none) in place.  Semantics of oracle/zstd_oracle.c
-// orc_lz_match_info: lcp capped at ZH_MAX_MATCH and at the block end, long candidates from 8
+// The lanes where b holds, as a mask (from the compare's own SGPR pair: no 0/1 VGPR between)
+__device__ __forceinline__ u64 mask_of(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+// ... and back: a lane mask as a per-lane predicate (used from its SGPR pair, no per-lane bit test)
+__device__ __forceinline__ bool lane_of(u64 m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+// Both 16-bit halves of a - b, each mod 2^16 (v_pk_sub_u16)
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32 pk_sub16(u32 a, u32 b) {
+  return __builtin_bit_cast(u32, (u16x2)(__builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)));
+}
+
+// The match lengths of rounds [r_lo, r_hi) (r_hi - r_lo <= NR, the most rounds the call site
+// has): candidates in cinfo -> match info (off << 8 | len, 0 = none) in place.  Semantics of
+// oracle/zstd_oracle.c orc_lz_match_info: lcp capped at ZH_MAX_MATCH and at the block end, long candidates from 8
 // bytes, short from 5, the longer (long on ties).  Then per position whether the parse takes its
 // match if it gets there (take_rule on the next positions' info: DPP within the round, the
 // round above by carry; la1 = the position above the span when it is the window's
 // top one) -> the rounds' take masks tm.  At the top of a span that is not the window's top the next positions
 // belong to another wave: those take bits stay clear until the wave decides them after barrier X.
-template <u32 MODE>
-__device__ __forceinline__ void span_lengths(const u32 *in32, u32 *ci, u64 *tm, u16 *xq, u32 r_lo, u32 r_hi, u32 wsb, u32 we, u32 n, u32 lim,
+template <u32 MODE, u32 NR = MAX_RW>
+__device__ __forceinline__ void span_lengths(const u32 *in32, u32 *ci, u64 *tm, u16 *xq, u32 r_lo_, u32 r_hi_, u32 wsb, u32 we, u32 n, u32 lim,
                                              u32 lane, bool top, u32 la1) {
   constexpr bool TWO = two_tables<MODE>();
-  u32 cwr[MAX_RW], flg[MAX_RW];
+  // the span is the wave's: as scalars, so that the rounds' branches are scalar and what crosses
+  // them (lane masks, carries, the queue count) stays in SGPRs
+  // (the count on its own: the miss-skip call's single round stays a constant)
+  u32 const r_lo = (u32)__builtin_amdgcn_readfirstlane(r_lo_), r_hi = r_lo + (u32)__builtin_amdgcn_readfirstlane(r_hi_ - r_lo_);
+  // whether round k of the span exists, opaque at each use: tests the compiler can correlate make
+  // it clone the whole phase per round count
+  auto has_round = [&](u32 k) {
+    u32 h = r_hi;
+    __asm__ volatile("" : "+s"(h));
+    return r_lo + k < h;
+  };
+  static_assert(ZH_MIN_MATCH_LONG == 8 && ZH_MAX_MATCH <= 255, "pass A: the long side keeps only `8 bytes equal`");
+  // Per round, pass A -> pass C: the candidate word, its halves minus one (the candidates'
+  // positions), pp = 7 | pS << 16 (below) and the v_perm_b32 selector that picks each table's
+  // chain-end length from pp or from the flushed extension bytes; the lanes that continue into
+  // the position above (fL, fS) as lane masks.
+  u32 cwr[NR], cm1[NR], pp[NR], sel[NR];
+  u64 mFL[NR], mFS[NR];
   // pass A, rounds high to low: a round's candidates, own bytes and candidate bytes are loaded
   // at the top of the round (hoisting every round's loads to the top of the pass was slower:
   // the longer LDS bursts delay the inserter waves, which are on the step's critical path)
-  u32 olo[MAX_RW], ohi[MAX_RW], Lw[MAX_RW][3], Sw[MAX_RW][3];
+  u32 olo[NR], ohi[NR], Lw[NR][3], Sw[NR][3];
   auto loadA = [&](u32 k) {
     u32 const r = r_hi - 1 - min(k, r_hi - 1 - r_lo), i = 64 * r + lane, p = wsb + i;  // (rounds past the span: repeat the last)
     // (positions at or past lim -- which covers we -- have no candidates: the inserters left 0)
     u32 const cw = ci[cidx(i)];
     cwr[k] = cw;
     ld64u(in32, p, olo[k], ohi[k]);
-    // the candidates' positions (c - 1) mod 2^16, without a select: an empty candidate reads
-    // position 65535's bytes (inside the staging area and its pad), and its prefix is never used --
-    // a match needs a nonempty candidate, and no chain passes through an empty one (its successor
-    // would need candidate 0 + 1 to continue it ... from a candidate of -1)
-    u32 const aL = ((cw - 1u) & 0xFFFFu) >> 2, aS = ((cw >> 16) + 0xFFFFu) >> 2 & 0x3FFFu;
+    // the candidates' positions (c - 1) mod 2^16, both halves at once and without a select: an
+    // empty candidate reads position 65535's bytes (inside the staging area and its pad), and its
+    // prefix is never used -- a match needs a nonempty candidate, and no chain passes through an
+    // empty one (its successor would need candidate 0 + 1 to continue it ... from a candidate of -1)
+    u32 const t = pk_sub16(cw, 0x00010001u);
+    cm1[k] = t;
+    const u8 *const in8 = (const u8 *)in32;
+    const u32 *const wL = (const u32 *)(in8 + (t & 0xFFFCu)), *const wS = (const u32 *)(in8 + ((t >> 16) & 0xFFFCu));
 #pragma unroll
-    for (u32 t = 0; t < 3; t++) {
-      if constexpr (TWO) Lw[k][t] = in32[aL + t];
-      Sw[k][t] = in32[aS + t];
+    for (u32 j = 0; j < 3; j++) {
+      if constexpr (TWO) Lw[k][j] = wL[j];
+      Sw[k][j] = wS[j];
     }
   };
-  u32 ccL = 0, ccS = 0;  // candidates of the position above the round being processed
-  u32 nq = 0;            // queued entries (wave-uniform)
+  u32 ccw = 0;  // candidate word of the position above the round being processed
+  u32 nq = 0;   // queued entries (wave-uniform, scalar)
 #pragma unroll
-  for (u32 k = 0; k < MAX_RW; k++) {
-    flg[k] = 0;
-    if (r_lo + k >= r_hi) { cwr[k] = 0; continue; }
+  for (u32 k = 0; k < NR; k++) {
+    mFL[k] = mFS[k] = 0;
+    pp[k] = sel[k] = 0;
+    if (!has_round(k)) continue;
     loadA(k);
     u32 const r = r_hi - 1 - k, i = 64 * r + lane;
-    u32 const cw = cwr[k];
-    u32 const cL = TWO ? cw & 0xFFFFu : 0u, cS = cw >> 16;
-    // common prefix (0..8) of the position's 8 bytes with the candidate's; for an empty candidate
-    // any value (see loadA): ctz64 of the difference as min(ffbl(x), min(ffbl(y), 32) + 32)
-    auto pref = [&](u32 c, const u32 (&w)[3]) {
-      u32 const sh = (c - 1u) & 3u;
-      u32 const x = olo[k] ^ __builtin_amdgcn_alignbyte(w[1], w[0], sh), y = ohi[k] ^ __builtin_amdgcn_alignbyte(w[2], w[1], sh);
-      return min(ffbl_raw(x), min(ffbl_raw(y), 32u) + 32u) >> 3;
+    u32 const cw = cwr[k], t = cm1[k];
+    // the difference of the position's 8 bytes and the candidate's; for an empty candidate any
+    // value (see loadA)
+    auto diff = [&](u32 sh, const u32 (&w)[3], u32 &x, u32 &y) {
+      x = olo[k] ^ __builtin_amdgcn_alignbyte(w[1], w[0], sh & 3u);
+      y = ohi[k] ^ __builtin_amdgcn_alignbyte(w[2], w[1], sh & 3u);
     };
-    u32 const pL = TWO ? pref(cL, Lw[k]) : 0u, pS = pref(cS, Sw[k]);
+    // short: the common prefix 0..8 (5..7 are matches): ctz64 of the difference as
+    // min(ffbl(x), min(ffbl(y), 32) + 32).  long: only whether all 8 are equal -- a long match
+    // counts from 8 bytes, and a chain end that is not extended either has no continuing
+    // predecessor (its length is its own prefix, < 8: no match) or is reached from one whose 8
+    // equal bytes cover its first 7 (its prefix is exactly 7): 7 stands for every prefix < 8
+    u32 xs, ys, xl = 1, yl = 0;
+    diff(t >> 16, Sw[k], xs, ys);
+    if constexpr (TWO) diff(t, Lw[k], xl, yl);
+    u32 const pS = min(ffbl_raw(xs), min(ffbl_raw(ys), 32u) + 32u) >> 3;
     vpad<ZH_PAD_A>(pS);
-    u32 cLn = wave_shl1(cL), cSn = wave_shl1(cS);
-    cLn = lane == 63 ? ccL : cLn;
-    cSn = lane == 63 ? ccS : cSn;
-    bool const fL = pL == 8 && cLn == cL + 1u, fS = pS == 8 && cSn == cS + 1u;
-    bool const xL = pL == 8 && !fL;
-    bool const sL = cS == cL && xL && pS == 8 && !fS;  // S takes L's extension
-    bool const xS = pS == 8 && !fS && !sL;
-    flg[k] = pL | (pS << 4) | (fL ? LF_FL : 0u) | (fS ? LF_FS : 0u) | (xL ? LF_XL : 0u) | (xS ? LF_XS : 0u) | (sL ? LF_SL : 0u);
-    ccL = lane_value(cL, 0);
-    ccS = lane_value(cS, 0);
+    // p + 1's candidates (lane 63: the round above's lane 0) minus p's, both halves at once: a
+    // half of 1 continues p's candidate
+    u32 const cwn = (u32)__builtin_amdgcn_update_dpp((int)ccw, (int)cw, 0x130, 0xf, 0xf, false);  // wave_shl:1
+    u32 const d = pk_sub16(cwn, cw);
+    // the predicates as lane masks, each straight from one compare and combined on the scalar
+    // unit: 8 bytes equal (8L, 8S), p + 1 continues (nL, nS); f = continues a chain, x = a chain
+    // end to extend, sL = S takes L's extension (the same candidate)
+    u64 const m8L = TWO ? mask_of(xl == 0) & mask_of(yl == 0) : 0ull, m8S = mask_of(pS == 8);
+    u64 const mnL = TWO ? mask_of((d & 0xFFFFu) == 1u) : 0ull, mnS = mask_of((d >> 16) == 1u);
+    u64 const bL = m8L & ~mnL, eS8 = m8S & ~mnS;
+    u64 const mSL = TWO ? mask_of((cw >> 16) == (cw & 0xFFFFu)) & bL & eS8 : 0ull;
+    u64 const bS = eS8 & ~mSL;
+    mFL[k] = m8L & mnL;
+    mFS[k] = m8S & mnS;
+    bool const xL = lane_of(bL), xS = lane_of(bS), sL = lane_of(mSL);
+    // chain-end lengths for pass C: v_perm_b32(cinfo word, pp, sel) = eL | eS << 16 with
+    // eL = xL ? byte 0 of the word (the flushed extension) : 7, eS = xS ? byte 2 : sL ? byte 0 : pS
+    pp[k] = 7u | pS << 16;
+    sel[k] = (xL ? 0x0C020C04u : 0x0C020C00u) + (xS ? 0x40000u : sL ? 0x20000u : 0u);
+    ccw = lane_value(cw, 0);
     // queue the chain ends to extend (L then S), flushing 64 at a time from the top
-    u64 const bL = TWO ? __ballot(xL) : 0ull, bS = __ballot(xS);
     u32 const rL = __builtin_amdgcn_mbcnt_hi((u32)(bL >> 32), __builtin_amdgcn_mbcnt_lo((u32)bL, 0u));
     u32 const rS = __builtin_amdgcn_mbcnt_hi((u32)(bS >> 32), __builtin_amdgcn_mbcnt_lo((u32)bS, 0u));
-    u32 const nL = (u32)__popcll(bL);
+    u32 const nqL = nq + (u32)__popcll(bL);
     // branch-free stores: lanes without an entry write the wave's spare slot (never read)
     xq[xL ? nq + rL : XQ_CAP - 1] = (u16)i;
-    xq[xS ? nq + nL + rS : XQ_CAP - 1] = (u16)(i | 0x8000u);
-    nq = (u32)__builtin_amdgcn_readfirstlane(nq + nL + (u32)__popcll(bS));
+    xq[xS ? nqL + rS : XQ_CAP - 1] = (u16)(i | 0x8000u);
+    nq = nqL + (u32)__popcll(bS);
+#pragma nounroll
     while (nq >= 64) {
       nq -= 64;
       xq_flush(in32, ci, xq + nq, 64, wsb, lane);
@@ -738,41 +788,38 @@ __device__ __forceinline__ void span_lengths(const u32 *in32, u32 *ci, u64 *tm, 
   // pass C.  C1: every round's chain lengths without the carry (the ds_bpermutes of all rounds
   // in flight together); C2, rounds high to low: lanes whose chain runs past the round take the
   // carry, then the match info and the take decision.
-  u32 lLr[MAX_RW], lSr[MAX_RW], runs[MAX_RW];
+  // C1 treats lane 63 as a chain end whatever it is: a lane whose chain runs past the round then
+  // gets 63 - lane plus lane 63's own value, which for a continuing lane 63 is its not-extended
+  // prefix -- 8 (short) or the stand-in 7 (long); C2 swaps that for 1 + the lcp of the position above.
+  u32 lLr[NR], lSr[NR];
   auto c1 = [&](u32 k) {
     u32 const r = r_hi - 1 - min(k, r_hi - 1 - r_lo), i = 64 * r + lane;
-    u32 const f = flg[k];
-    u32 const ce = ci[cidx(i)];
-    u32 const pL = f & 15u, pS = (f >> 4) & 15u;
-    u32 const eL = (f & LF_XL) ? (ce & 255u) : pL;
-    u32 const eS = (f & LF_XS) ? ((ce >> 16) & 255u) : ((f & LF_SL) ? eL : pS);
-    u64 const RS = __ballot(!(f & LF_FS)) >> lane;
-    u32 const qS = RS ? ctz64(RS) : 64u - lane;
-    u32 const vS = bperm(eS, min(lane + qS, 63u));
-    lSr[k] = RS ? min((u32)ZH_MAX_MATCH, qS + vS) : qS;  // (a chain running past: + carry in C2)
-    runs[k] = RS ? 0u : 2u;
+    u32 const e = __builtin_amdgcn_perm(ci[cidx(i)], pp[k], sel[k]);
+    u32 const qS = ctz64((~mFS[k] | 1ull << 63) >> lane);
+    lSr[k] = qS + (bperm(e, lane + qS) >> 16);
     if constexpr (TWO) {
-      u64 const RL = __ballot(!(f & LF_FL)) >> lane;
-      u32 const qL = RL ? ctz64(RL) : 64u - lane;
-      u32 const vL = bperm(eL, min(lane + qL, 63u));
-      lLr[k] = RL ? min((u32)ZH_MAX_MATCH, qL + vL) : qL;
-      runs[k] |= RL ? 0u : 1u;
+      u32 const qL = ctz64((~mFL[k] | 1ull << 63) >> lane);
+      lLr[k] = qL + (bperm(e, lane + qL) & 255u);
     } else {
       lLr[k] = 0;
     }
   };
 #pragma unroll
-  for (u32 k = 0; k < MAX_RW; k++) c1(k);
+  for (u32 k = 0; k < NR; k++) c1(k);
   u32 clL = 0, clS = 0;  // lcps of the position above the round
   u32 cv1 = la1;         // info of the position above the round
 #pragma unroll
-  for (u32 k = 0; k < MAX_RW; k++) {
-    if (r_lo + k >= r_hi) continue;
+  for (u32 k = 0; k < NR; k++) {
+    if (!has_round(k)) continue;
     u32 const r = r_hi - 1 - k, i = 64 * r + lane, p = wsb + i;
     u32 const cw = cwr[k];
     u32 const cL = TWO ? cw & 0xFFFFu : 0u, cS = cw >> 16;
-    u32 const lL = (runs[k] & 1u) ? min((u32)ZH_MAX_MATCH, lLr[k] + clL) : lLr[k];
-    u32 const lS = (runs[k] & 2u) ? min((u32)ZH_MAX_MATCH, lSr[k] + clS) : lSr[k];
+    // the lanes above the round's last chain end run past it (scalar: the first such lane; 64
+    // when lane 63 is a chain end); a carry wraps below zero only where no lane takes it (the
+    // position above continues a chain of 8 equal bytes: its lcp is at least 7)
+    auto first_run = [](u64 f) { return ~f ? 64u - (u32)__builtin_clzll(~f) : 0u; };
+    u32 const lL = min((u32)ZH_MAX_MATCH, lLr[k] + (lane >= first_run(mFL[k]) ? clL - 6u : 0u));
+    u32 const lS = min((u32)ZH_MAX_MATCH, lSr[k] + (lane >= first_run(mFS[k]) ? clS - 7u : 0u));
     vpad<ZH_PAD_C>(lS);
     clL = lane_value(lL, 0);
     clS = lane_value(lS, 0);
@@ -786,10 +833,9 @@ __device__ __forceinline__ void span_lengths(const u32 *in32, u32 *ci, u64 *tm, 
     u32 v1 = wave_shl1(v);
     v1 = lane == 63 ? cv1 : v1;
     cv1 = lane_value(v, 0);
-    bool const unk = MODE != 2 && k == 0 && !top && lane == 63;
-    bool const tk = v != 0 && !unk && take_rule<MODE>(v, v1);
+    u64 const unk = MODE != 2 && k == 0 && !top ? 1ull << 63 : 0ull;
     ci[cidx(i)] = v;
-    u64 const tb = __ballot(tk);
+    u64 const tb = mask_of(v != 0) & mask_of(take_rule<MODE>(v, v1)) & ~unk;
     if (lane == 0) tm[r] = tb;
   }
 }
@@ -1648,7 +1694,7 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
       if constexpr (MODE == 2) {
         if (wave <= RS / L1_S) span_lengths_l1(in32, ciK, tmK, xq, wave - 1, wave, wsb, n, lane);
       } else {
-        if (wave <= RS) span_lengths<MODE>(in32, ciK, tmK, xq, wave - 1, wave, wsb, we, n, lim, lane, wave == RS, 0u);
+        if (wave <= RS) span_lengths<MODE, 1>(in32, ciK, tmK, xq, wave - 1, wave, wsb, we, n, lim, lane, wave == RS, 0u);
       }
       for (u32 r = RS + wave - 1; r < NROUND; r += NWW - 1) {
         ciK[cidx(64 * r + lane)] = 0;

@@ -41,6 +41,13 @@ def lib() -> ctypes.CDLL:
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} not found: build it with __graft_entry__.build() (make -C custom-nvcomp-with-zstd_amd)")
+        # PyTorch brings its own HIP runtime.  Loaded after this library it is a second runtime in
+        # the process, and the library's calls on torch's device pointers fail (HIP runtime error);
+        # loaded first, the library binds to the same one.
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            pass
         L = ctypes.CDLL(LIB_PATH)
         vp, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
         psz, pvp, pi = ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(i)
