@@ -31,6 +31,7 @@
 #include "cuda_zstd_manager.h"
 #include "cuda_zstd_nvcomp.h"
 #include "zh_dict.h"
+#include "zh_dict_train.h"
 #include "zh_launch.h"
 #include "zh_seek.h"
 
@@ -1303,33 +1304,123 @@ bool ZstdStreamingManager::is_decompression_initialized() const { return pimpl_-
 // byte-frequency / 4-gram fill, same validation and buffer contract
 // ============================================================================
 namespace dictionary {
+namespace {
+bool g_train_profile = false;  // cuda_zstd_hip_dict_train_profile: HIP events around the device trainer's kernel groups
+float g_train_phase_ms[3] = {0.f, 0.f, 0.f};
+
+// The device trainer (zh_dict_train.hip) over samples back to back at d_corpus; sizes is a host
+// array.  temp == nullptr: the function's own hipMalloc.  content = zh::cover_train's bytes.
+Status train_device(const u8 *d_corpus, const size_t *sizes, size_t n, size_t dict_size, u32 k, u32 d, void *temp, size_t temp_bytes,
+                    bool own_temp, hipStream_t stream, std::vector<u8> &content) {
+  content.clear();
+  if (!d_corpus || !sizes || n == 0 || n >= (1ull << 32)) return Status::ERROR_INVALID_PARAMETER;
+  k = k ? k : zh::kCoverDefaultK;
+  d = d ? d : zh::kCoverDefaultD;
+  std::vector<u32> ends(n);
+  u64 total = 0;
+  for (size_t i = 0; i < n; i++) {
+    total += sizes[i];
+    if (sizes[i] >= (1ull << 32) || total >= (1ull << 32) - 64) return Status::ERROR_INVALID_PARAMETER;  // positions are u32
+    ends[i] = (u32)total;
+  }
+  if (total == 0) return Status::ERROR_INVALID_PARAMETER;
+  zh::CoverPlan const plan = zh::cover_plan((size_t)total, dict_size, k, d);
+  if (plan.k > zh::kCoverMaxK) return Status::ERROR_INVALID_PARAMETER;  // prevdist is a u16
+  size_t const need = zh::cover_temp_bytes((size_t)total, n, dict_size, k);
+  if (!own_temp && (!temp || temp_bytes < need)) return Status::ERROR_BUFFER_TOO_SMALL;
+  if (plan.empty) return Status::SUCCESS;  // fewer than k bytes: the host trainer's empty result
+  void *mine = nullptr;
+  if (own_temp) {
+    if (hipMalloc(&mine, need) != hipSuccess) { (void)hipGetLastError(); return Status::ERROR_OUT_OF_MEMORY; }
+    temp = mine;
+  }
+  hipError_t const e = zh::cover_train_device(d_corpus, ends.data(), n, plan, dict_size, temp, stream, content,
+                                              g_train_profile ? g_train_phase_ms : nullptr);
+  if (mine) (void)hipFree(mine);
+  if (e != hipSuccess) { (void)hipGetLastError(); return Status::ERROR_CUDA_ERROR; }
+  return Status::SUCCESS;
+}
+
+// trained content -> the dict_size bytes of dict_buffer (host or device memory)
+Status place_content(const std::vector<u8> &c, void *dict_buffer, size_t dict_size, hipStream_t stream) {
+  if (c.empty() || c.size() > dict_size) return Status::ERROR_DICTIONARY_FAILED;
+  // the buffer holds dict_size bytes: the trained content at its end (the most useful segments
+  // nearest the data, as ZDICT lays them out), zeros before it when the samples gave less
+  if (!is_device_ptr(dict_buffer)) {
+    u8 *const out = (u8 *)dict_buffer;
+    memset(out, 0, dict_size - c.size());
+    memcpy(out + dict_size - c.size(), c.data(), c.size());
+    return Status::SUCCESS;
+  }
+  std::vector<u8> full(dict_size, 0);
+  memcpy(full.data() + dict_size - c.size(), c.data(), c.size());
+  return copy_any(dict_buffer, full.data(), dict_size, stream);
+}
+}  // namespace
+
 Status train_dictionary(const std::vector<const void *> &samples, const std::vector<size_t> &sample_sizes, void *dict_buffer,
                         size_t dict_size, const DictionaryTrainingParams *params, hipStream_t stream) {
-  (void)params;
-  (void)stream;
   if (samples.empty() || sample_sizes.empty() || !dict_buffer || samples.size() != sample_sizes.size()) return Status::ERROR_INVALID_PARAMETER;
   if (!is_valid_dictionary_size(dict_size)) return Status::ERROR_INVALID_PARAMETER;
   std::vector<std::pair<const u8 *, size_t>> s;
   size_t total = 0;
+  const void *first = nullptr;
   for (size_t i = 0; i < samples.size(); i++) {
     if (!samples[i] && sample_sizes[i]) return Status::ERROR_INVALID_PARAMETER;
     s.emplace_back((const u8 *)samples[i], sample_sizes[i]);
     total += sample_sizes[i];
+    if (!first && sample_sizes[i]) first = samples[i];
   }
   if (total == 0) return Status::ERROR_INVALID_PARAMETER;
   std::vector<u8> c;
   try {
-    c = zh::cover_train(s, dict_size);
+    if (is_device_ptr(first)) {  // device samples (all of them): trained in place, or on the host when use_gpu is off
+      bool const on_gpu = !params || params->use_gpu;
+      bool contiguous = true;
+      const u8 *at = (const u8 *)first;
+      for (auto const &p : s) {
+        if (!p.second) continue;
+        contiguous = contiguous && p.first == at;
+        at += p.second;
+      }
+      if (on_gpu && contiguous) {
+        Status const st = train_device((const u8 *)first, sample_sizes.data(), samples.size(), dict_size, 0, 0, nullptr, 0, true, stream, c);
+        if (st != Status::SUCCESS) return st;
+      } else if (on_gpu) {
+        u8 *gathered = nullptr;
+        if (hipMalloc((void **)&gathered, total) != hipSuccess) { (void)hipGetLastError(); return Status::ERROR_OUT_OF_MEMORY; }
+        size_t o = 0;
+        hipError_t e = hipSuccess;
+        for (auto const &p : s) {
+          if (p.second && e == hipSuccess) e = hipMemcpyAsync(gathered + o, p.first, p.second, hipMemcpyDeviceToDevice, stream);
+          o += p.second;
+        }
+        Status st = e == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
+        if (st == Status::SUCCESS) st = train_device(gathered, sample_sizes.data(), samples.size(), dict_size, 0, 0, nullptr, 0, true, stream, c);
+        else (void)hipStreamSynchronize(stream);
+        (void)hipFree(gathered);
+        if (st != Status::SUCCESS) return st;
+      } else {
+        std::vector<u8> host(total);
+        size_t o = 0;
+        for (auto &p : s) {
+          if (p.second && hipMemcpyAsync(host.data() + o, p.first, p.second, hipMemcpyDeviceToHost, stream) != hipSuccess) {
+            (void)hipStreamSynchronize(stream);
+            return Status::ERROR_CUDA_ERROR;
+          }
+          p.first = host.data() + o;
+          o += p.second;
+        }
+        if (hipStreamSynchronize(stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+        c = zh::cover_train(s, dict_size);
+      }
+    } else {
+      c = zh::cover_train(s, dict_size);  // host samples, whatever use_gpu says
+    }
   } catch (...) {
     return Status::ERROR_OUT_OF_MEMORY;
   }
-  if (c.empty() || c.size() > dict_size) return Status::ERROR_DICTIONARY_FAILED;
-  // the buffer holds dict_size bytes: the trained content at its end (the most useful segments
-  // nearest the data, as ZDICT lays them out), zeros before it when the samples gave less
-  u8 *const out = (u8 *)dict_buffer;
-  memset(out, 0, dict_size - c.size());
-  memcpy(out + dict_size - c.size(), c.data(), c.size());
-  return Status::SUCCESS;
+  return place_content(c, dict_buffer, dict_size, stream);
 }
 Status create_dictionary_from_samples(const void *samples_buffer, const size_t *sample_offsets, size_t num_samples, void *dict_buffer,
                                       size_t dict_size, const DictionaryTrainingParams *params, hipStream_t stream) {
@@ -2024,7 +2115,8 @@ size_t cuda_zstd_get_compress_workspace_size(cuda_zstd_manager_t *m, size_t n) {
 size_t cuda_zstd_get_decompress_workspace_size(cuda_zstd_manager_t *m, size_t n) { return (m && m->manager) ? m->manager->get_decompress_temp_size(n) : 0; }
 size_t cuda_zstd_get_max_compressed_size(cuda_zstd_manager_t *m, size_t n) { return (m && m->manager) ? m->manager->get_max_compressed_size(n) : 0; }
 
-cuda_zstd_dict_t *cuda_zstd_train_dictionary(const void **samples, const size_t *sizes, size_t num, size_t dict_size) {
+cuda_zstd_dict_t *cuda_zstd_train_dictionary_params(const void **samples, const size_t *sizes, size_t num, size_t dict_size, unsigned k,
+                                                    unsigned d) {
   if (!samples || !sizes || num == 0 || dict_size == 0) return nullptr;
   try {
     // COVER-trained raw content (zh_dict.cpp), replacing the reference's n-gram fill
@@ -2034,14 +2126,45 @@ cuda_zstd_dict_t *cuda_zstd_train_dictionary(const void **samples, const size_t 
       if (!samples[i] || sizes[i] == 0) return nullptr;  // (reference src/cuda_zstd_c_api.cpp:142-145)
       s.emplace_back((const u8 *)samples[i], sizes[i]);
     }
-    std::vector<u8> c = zh::cover_train(s, std::min(dict_size, zh::kDictMaxBytes));
+    std::vector<u8> c = zh::cover_train(s, std::min(dict_size, zh::kDictMaxBytes), k ? k : zh::kCoverDefaultK, d ? d : zh::kCoverDefaultD);
     if (c.size() < dictionary::MIN_DICT_SIZE) return nullptr;  // (set_dictionary would refuse it)
-    auto *d = new cuda_zstd_dict_t;
-    d->set(std::move(c), 0);
-    return d;
+    auto *h = new cuda_zstd_dict_t;
+    h->set(std::move(c), 0);
+    return h;
   } catch (...) {
     return nullptr;
   }
+}
+cuda_zstd_dict_t *cuda_zstd_train_dictionary(const void **samples, const size_t *sizes, size_t num, size_t dict_size) {
+  return cuda_zstd_train_dictionary_params(samples, sizes, num, dict_size, 0, 0);
+}
+size_t cuda_zstd_train_dictionary_device_get_temp_size(size_t total_sample_bytes, size_t num_samples, size_t dict_size, unsigned k) {
+  return zh::cover_temp_bytes(total_sample_bytes, num_samples, dict_size, k);
+}
+int cuda_zstd_train_dictionary_device(const void *d_samples, const size_t *sizes, size_t num, size_t dict_size, unsigned k, unsigned d,
+                                      void *d_temp, size_t temp_bytes, hipStream_t stream, cuda_zstd_dict_t **dict_out) {
+  if (!dict_out) return c_err(Status::ERROR_INVALID_PARAMETER);
+  *dict_out = nullptr;
+  if (!d_samples || !sizes || num == 0 || !dictionary::is_valid_dictionary_size(dict_size)) return c_err(Status::ERROR_INVALID_PARAMETER);
+  try {
+    std::vector<u8> c;
+    Status const st = dictionary::train_device((const u8 *)d_samples, sizes, num, dict_size, k, d, d_temp, temp_bytes, false, stream, c);
+    if (st != Status::SUCCESS) return c_err(st);
+    if (c.size() < dictionary::MIN_DICT_SIZE) return c_err(Status::ERROR_COMPRESSION);  // (where the host entry returns NULL)
+    auto *h = new cuda_zstd_dict_t;
+    h->set(std::move(c), 0);
+    *dict_out = h;
+    return 0;
+  } catch (...) {
+    return c_err(Status::ERROR_OUT_OF_MEMORY);
+  }
+}
+// on != 0: later device trainings time their kernel groups with HIP events; ms3 (optional): the
+// last such call's ids + freq, prevdist and step-loop milliseconds
+void cuda_zstd_hip_dict_train_profile(int on, double *ms3) {
+  dictionary::g_train_profile = on != 0;
+  if (ms3)
+    for (int i = 0; i < 3; i++) ms3[i] = dictionary::g_train_phase_ms[i];
 }
 void cuda_zstd_destroy_dictionary(cuda_zstd_dict_t *d) { delete d; }
 // reference DictionaryManager::load_dictionary (include/cuda_zstd_dictionary.h:292-310): a host

@@ -12,6 +12,7 @@
 // Read: the table is parsed, validated and scanned on the device, and turned into the job
 // arrays of the batched decoder; a last kernel checks the decodes and trims the edge frames.
 #include "zh_common.h"
+#include "zh_scan.h"
 #include "zh_seek.h"
 #include "zh_xxh64.h"
 
@@ -19,7 +20,7 @@
 
 namespace {
 
-constexpr u32 SK_THREADS = 256;
+constexpr u32 SK_THREADS = ZH_SCAN_THREADS;
 constexpr u32 SK_PER_THREAD = 4;
 constexpr u32 SK_TILE = SK_THREADS * SK_PER_THREAD;  // items per scan tile
 constexpr u32 SK_PIECE = 16384;                      // bytes per copy workgroup: 256 lanes x 16 B x 4
@@ -38,35 +39,6 @@ struct JobMeta {
   u32 flags;  // bit 0: bounced; bit 1: the bounce slot
   u64 dstart;
 };
-
-__device__ __forceinline__ u64 wave_scan_incl64(u64 v) {
-  u32 const lane = threadIdx.x & 63u;
-#pragma unroll
-  for (u32 o = 1; o < 64; o <<= 1) {
-    u64 const t = __shfl_up((unsigned long long)v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// Exclusive scan of one u64 per thread over a 256-thread workgroup; total = the workgroup's sum.
-// lds: 4 u64 (reusable after the call returns).
-__device__ __forceinline__ u64 block_scan_excl64(u64 v, u64 *lds, u64 &total) {
-  u32 const tid = threadIdx.x, w = tid >> 6;
-  u64 const inc = wave_scan_incl64(v);
-  __syncthreads();
-  if ((tid & 63u) == 63u) lds[w] = inc;
-  __syncthreads();
-  u64 base = 0, tot = 0;
-#pragma unroll
-  for (u32 k = 0; k < SK_THREADS / 64; k++) {
-    u64 const s = lds[k];
-    base += k < w ? s : 0ull;
-    tot += s;
-  }
-  total = tot;
-  return base + inc - v;
-}
 
 __device__ __forceinline__ u64 block_min64(u64 v, u64 *lds) {
   u32 const tid = threadIdx.x;

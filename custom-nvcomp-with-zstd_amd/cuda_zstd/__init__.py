@@ -64,6 +64,10 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_get_error_string": (ctypes.c_char_p, [i]),
             "cuda_zstd_is_error": (i, [i]),
             "cuda_zstd_train_dictionary": (vp, [pvp, psz, sz, sz]),
+            "cuda_zstd_train_dictionary_params": (vp, [pvp, psz, sz, sz, ctypes.c_uint, ctypes.c_uint]),
+            "cuda_zstd_train_dictionary_device_get_temp_size": (sz, [sz, sz, sz, ctypes.c_uint]),
+            "cuda_zstd_train_dictionary_device": (i, [vp, psz, sz, sz, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, pvp]),
+            "cuda_zstd_hip_dict_train_profile": (None, [i, ctypes.POINTER(ctypes.c_double)]),
             "cuda_zstd_load_dictionary": (vp, [vp, sz]),
             "cuda_zstd_destroy_dictionary": (None, [vp]),
             "cuda_zstd_set_dictionary": (i, [vp, vp]),
@@ -149,6 +153,10 @@ __version__ = "0.2.0"
 
 def _is_host(x) -> bool:
     return isinstance(x, (bytes, bytearray, memoryview)) or type(x).__module__.startswith("numpy")
+
+
+def _is_cuda_tensor(x) -> bool:
+    return type(x).__module__ == "torch" and bool(getattr(x, "is_cuda", False))
 
 
 def _to_device(x):
@@ -351,14 +359,46 @@ class Dictionary:
         self._h = handle
 
     @classmethod
-    def train(cls, samples, dict_size: int) -> "Dictionary":
-        """COVER training over host samples (bytes-like / uint8 arrays) -> raw content."""
+    def train(cls, samples, dict_size: int, k: int = 0, d: int = 0, stream=None) -> "Dictionary":
+        """COVER training -> raw content; k = segment bytes, d = d-mer bytes (0: 1024 / 8).
+        Host samples (bytes-like / uint8 arrays) train on the host.  Torch CUDA tensors -- a list
+        or tuple of them, or one 2-D uint8 tensor with a sample per row -- train on the device
+        (cuda_zstd_train_dictionary_device), ordered on `stream`; the bytes are the same."""
+        if _is_cuda_tensor(samples) or (isinstance(samples, (list, tuple)) and len(samples) and all(_is_cuda_tensor(t) for t in samples)):
+            return cls._train_device(samples, dict_size, k, d, stream)
         raw = [bytes(s) for s in samples]
         bufs = [ctypes.create_string_buffer(b, max(len(b), 1)) for b in raw]
         n = len(raw)
         ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in bufs])
         sizes = (ctypes.c_size_t * n)(*[len(b) for b in raw])
+        if k or d:
+            return cls(lib().cuda_zstd_train_dictionary_params(ptrs, sizes, n, dict_size, k, d), "cuda_zstd_train_dictionary_params")
         return cls(lib().cuda_zstd_train_dictionary(ptrs, sizes, n, dict_size), "cuda_zstd_train_dictionary")
+
+    @classmethod
+    def _train_device(cls, samples, dict_size, k, d, stream):
+        torch = _torch()
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):  # the concatenation and the temp buffer are ordered on the same stream
+            if _is_cuda_tensor(samples):
+                if samples.dim() != 2 or samples.dtype != torch.uint8:
+                    raise TypeError("Dictionary.train: a single tensor must be 2-D uint8, one sample per row")
+                sizes = [samples.shape[1]] * samples.shape[0]
+                flat = samples.contiguous().view(-1)
+            else:
+                views = [t.contiguous().view(torch.uint8).view(-1) for t in samples]
+                sizes = [v.numel() for v in views]
+                flat = torch.cat(views) if len(views) > 1 else views[0]
+            n = len(sizes)
+            csz = (ctypes.c_size_t * max(n, 1))(*sizes)
+            temp = torch.empty(max(lib().cuda_zstd_train_dictionary_device_get_temp_size(flat.numel(), n, dict_size, k), 256),
+                               dtype=torch.uint8, device=flat.device)
+            h = ctypes.c_void_p()
+            rc = lib().cuda_zstd_train_dictionary_device(flat.data_ptr(), csz, n, dict_size, k, d, temp.data_ptr(), temp.numel(),
+                                                         s.cuda_stream, ctypes.byref(h))
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_train_dictionary_device")
+        return cls(h.value, "cuda_zstd_train_dictionary_device")
 
     @classmethod
     def load(cls, buf) -> "Dictionary":

@@ -40,6 +40,21 @@ int cuda_zstd_decompress(cuda_zstd_manager_t *manager, const void *src, size_t s
 size_t cuda_zstd_get_compress_workspace_size(cuda_zstd_manager_t *manager, size_t src_size);
 size_t cuda_zstd_get_decompress_workspace_size(cuda_zstd_manager_t *manager, size_t compressed_size);
 cuda_zstd_dict_t *cuda_zstd_train_dictionary(const void **samples, const size_t *sample_sizes, size_t num_samples, size_t dict_size);
+/* host trainer with explicit COVER parameters (0 = default k 1024 / d 8); otherwise cuda_zstd_train_dictionary */
+cuda_zstd_dict_t *cuda_zstd_train_dictionary_params(const void **samples, const size_t *sample_sizes, size_t num_samples,
+                                                    size_t dict_size, unsigned k, unsigned d);
+/* device trainer: d_samples = the samples back to back in device memory, sample_sizes a HOST array
+ * (zero sizes allowed).  Stream-ordered on `stream` for its reads of d_samples; blocking on return
+ * (the handle holds host bytes).  *dict_out = a handle whose content equals the host trainer's
+ * for the same samples, or NULL.  Returns 0; 2 for bad arguments, a dict_size outside 256 B ..
+ * 128 KiB, k > 65535 or 2^32 - 64 or more sample bytes; 7 when temp_bytes is below what
+ * _get_temp_size reports (nothing is launched); 12 when training gave fewer than 256 bytes
+ * (where the host entry returns NULL); 4 on a HIP error.  Window scores are kept in 64 bits, so
+ * num_samples * k is not limited. */
+size_t cuda_zstd_train_dictionary_device_get_temp_size(size_t total_sample_bytes, size_t num_samples, size_t dict_size, unsigned k);
+int cuda_zstd_train_dictionary_device(const void *d_samples, const size_t *sample_sizes, size_t num_samples, size_t dict_size,
+                                      unsigned k, unsigned d, void *d_temp, size_t temp_bytes, hipStream_t stream,
+                                      cuda_zstd_dict_t **dict_out);
 void cuda_zstd_destroy_dictionary(cuda_zstd_dict_t *dict);
 int cuda_zstd_set_dictionary(cuda_zstd_manager_t *manager, cuda_zstd_dict_t *dict);
 /* dictionaries: cuda_zstd_train_dictionary is COVER training (raw content);
@@ -245,6 +260,10 @@ const char *cuda_zstd_hip_version(void);
  * zh_checksum_kernel). */
 void cuda_zstd_hip_profile_enable(int on);
 int cuda_zstd_hip_profile_collect(double *ms3);
+/* on != 0: later cuda_zstd_train_dictionary_device calls time their kernel groups with HIP events;
+ * ms3 (optional) receives the last such call's milliseconds: d-mer ids + frequencies, prevdist,
+ * the epoch-step loop. */
+void cuda_zstd_hip_dict_train_profile(int on, double *ms3);
 /* LDS bytes requested by K1 (which = 0) and the entropy kernel (1), for launch-bound checks. */
 unsigned int cuda_zstd_hip_kernel_lds_bytes(int which);
 

@@ -12,7 +12,8 @@
 //   compat::DictionaryTrainerWrapper / DictionaryManagerWrapper  :216-310, and their aliases
 //
 // What differs (documented, not an ABI change): training is COVER (Liao et al., libzstd's
-// ZDICT_trainFromBuffer_cover algorithm, csrc/zh_dict.cpp) producing raw content, where the
+// ZDICT_trainFromBuffer_cover algorithm, csrc/zh_dict.cpp on the host and csrc/zh_dict_train.hip
+// for samples in device memory, same bytes) producing raw content, where the
 // reference fills the buffer with a byte-frequency / 4-gram heuristic
 // (src/cuda_zstd_dictionary.cu:179-415); a manager copies the bytes at set_dictionary (the
 // reference keeps the caller's pointer, src/cuda_zstd_manager.cu:3743-3745), and frames name the
@@ -37,7 +38,8 @@ constexpr u32 MAX_DICT_SIZE = 128 * 1024;
 
 struct DictionaryTrainingParams {
   u32 optimization_level = 0;  // accepted for source compatibility; COVER's own parameters apply
-  bool use_gpu = true;
+  bool use_gpu = true;  // samples in device memory: true trains on the device (csrc/zh_dict_train.hip), false copies
+                        // them to the host trainer; host samples always train on the host; same bytes either way
   u32 max_threads = 256;
   u32 reserved[5] = {0};
 };
@@ -98,9 +100,13 @@ struct Dictionary {
   }
 };
 
-// COVER training over host samples into dict_buffer (dict_size bytes, MIN..MAX_DICT_SIZE); the
+// COVER training into dict_buffer (dict_size bytes, MIN..MAX_DICT_SIZE, host or device memory); the
 // trained content fills the buffer from its end (ZDICT's layout: the most useful segments last)
-// and any unused head is zero.
+// and any unused head is zero.  The samples are all host or all device pointers (probed with
+// hipPointerGetAttributes).  Device samples are trained on the device unless params->use_gpu is
+// false (in place when they lie back to back, else gathered into one internal device buffer;
+// temp memory is the function's own hipMalloc; reads are ordered on `stream`); the result is
+// byte-identical to the host trainer's.  The call blocks until the dictionary is written.
 Status train_dictionary(const std::vector<const void *> &samples, const std::vector<size_t> &sample_sizes, void *dict_buffer,
                         size_t dict_size, const DictionaryTrainingParams *params = nullptr, hipStream_t stream = 0);
 // samples as one buffer with start offsets; sample i ends where i + 1 starts, the last one after
