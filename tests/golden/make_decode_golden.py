@@ -20,6 +20,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+import zh_edge_inputs as E  # noqa: E402
 import zh_testlib as T  # noqa: E402
 
 REF_CANONICAL = ("28b52ffd60f4009d0600869e3107f00d9999399f7b2e002e002e003f1a151d22554454020037c5446ca9322305"
@@ -42,13 +43,48 @@ CASES = [
     # shapes found with tests/zh_frames.py to reach the remaining decoder paths
     ("zeros_then_rand_l3_rle_block", "rand_then_zeros", 1, 0, dict(level=3)),
     ("sym16_2k_l1_no_sequences", "sym16_small", 1, 2000, dict(level=1)),
-    ("sym16_2k_l3_ml_rle", "sym16_small", 1, 2000, dict(level=3)),
+    ("sym16_2k_l3_predefined_tables", "sym16_small", 1, 2000, dict(level=3)),
     ("runs_l3_direct_weights", "runs_small", 1, 0, dict(level=3)),
-    ("rows_l1_ll_of_rle_repeat", "rows", 2, 0, dict(level=1)),
-    ("rows_l3_ml_rle_repeat", "rows", 2, 0, dict(level=3)),
+    ("rows_l1_of_rle", "rows", 2, 0, dict(level=1)),
+    ("rows_l3_of_rle", "rows", 2, 0, dict(level=3)),
     ("slices_l19_rle_literals", "slices_q", 3, 0, dict(level=19)),
     ("rows_l9_ml_repeat", "rows", 2, 0, dict(level=9)),
     ("json_300k_l9_treeless_ml_repeat", "json", 5, 300000, dict(level=9)),
+    # zh_edge_inputs builders ("edge:<case>": the case's builder at this seed) for the RLE-mode
+    # LL / ML tables, the 3-byte raw-literals header and a single Huffman stream with direct
+    # weights; a second block after 128 KiB of JSON for the three repeat modes
+    ("edge_a24_l3_ll_rle", "edge:ll_rle_a24", 27, 0, dict(level=3)),
+    ("edge_a24_l1_ml_rle", "edge:ml_rle_a24", 21, 0, dict(level=1)),
+    ("edge_code64_l1_ll_of_ml_rle", "edge:all_rle_b", 104, 0, dict(level=1)),
+    ("edge_lits4096_l19_raw_h3", "edge:lits_4096_a256", 1, 0, dict(level=19)),
+    ("edge_lits64_l1_1stream_direct_weights", "edge:lits_64_a8", 1, 0, dict(level=1)),
+    ("json_132k_l9_ll_of_ml_repeat", "json_two_blocks", 1, 0, dict(level=9)),
+]
+
+
+def _frame(*blocks):
+    """A frame without content size (window 128 KiB) of (type, content[, regenerated size]) blocks."""
+    out = bytes.fromhex("28b52ffd0038")
+    for k, b in enumerate(blocks):
+        t, body = b[0], b[1]
+        size = b[2] if t == 1 else len(body)
+        out += ((k == len(blocks) - 1) | (t << 1) | (size << 3)).to_bytes(3, "little") + body
+    return out
+
+
+# Frames libzstd does not produce at these sizes, assembled by hand (RFC 8878 §3.1.1.3);
+# libzstd decodes them and its output is what the fixture records.
+HAND = [
+    # a raw block "abcdefgh", then a compressed block: no literals, 0x7F00 sequences (the 3-byte
+    # count), the three tables in RLE mode with code 0 (literal length 0, repeat offset, match
+    # length 3) and a bitstream that is its padding bit alone: 8 + 32,512 x 3 = 97,544 bytes
+    ("hand_nseq_3_bytes_all_rle", _frame((0, b"abcdefgh"), (2, bytes.fromhex("00" "ff0000" "54" "000000" "01")))),
+    # RLE literals with every header size (Size_Format 00, 10: 1 byte; 01: 2 bytes; 11: 3 bytes)
+    # and raw literals with Size_Format 10, each in a block without sequences
+    ("hand_rle_literals_h1_h2_h3", _frame((2, bytes([1 | 0 << 2 | 20 << 3, 0x61, 0])), (2, bytes([1 | 2 << 2 | 31 << 3, 0x62, 0])),
+                                          (2, (1 | 1 << 2 | 300 << 4).to_bytes(2, "little") + b"c\0"),
+                                          (2, (1 | 3 << 2 | 70000 << 4).to_bytes(3, "little") + b"d\0"),
+                                          (2, bytes([0 | 2 << 2 | 5 << 3]) + b"hello\0"))),
 ]
 
 
@@ -74,6 +110,11 @@ def make_input(kind, seed, size):
             s = rng.integers(0, 131072 - 80)
             parts += [base[s:s + rng.integers(20, 70)], np.array([1], np.uint8)]
         return np.concatenate(parts)
+    if kind.startswith("edge:"):
+        fn, kw = next((fn, kw) for n, fn, _, kw in E.CASES if n == kind[5:])
+        return fn(seed, **kw)
+    if kind == "json_two_blocks":  # libzstd's blocks hold 128 KiB: a second block of 4 KiB
+        return np.concatenate([T.gen(T.DG_JSON, 1, seed, 131072), T.gen(T.DG_JSON, 1, seed + 50, 4096)])
     if kind == "iota":
         return (np.arange(size) % 256).astype(np.uint8)
     if kind == "zeros":
@@ -100,6 +141,9 @@ def main():
         assert T.zstd_decompress(frame, max(len(data), 1)) == data.tobytes()
         out["vectors"].append({"name": name, "kind": kind, "seed": seed, "size": len(data), "params": kw, "frame": frame.hex(),
                                "sha256": hashlib.sha256(data.tobytes()).hexdigest()})
+    for name, frame in HAND:
+        data = T.zstd_decompress(frame, 1 << 20)
+        out["vectors"].append({"name": name, "kind": "hand", "size": len(data), "frame": frame.hex(), "sha256": hashlib.sha256(data).hexdigest()})
     with open(os.path.join(HERE, "decode_frames.json"), "w") as f:
         json.dump(out, f, indent=0)
     print(sum(len(v["frame"]) // 2 for v in out["vectors"]), "frame bytes")

@@ -2,8 +2,10 @@
 (tests/golden/decode_frames.json, made by tests/golden/make_decode_golden.py) decode with
 libzstd to the recorded digests, and together they reach every decoder path of
 zh_decode.hip (block types, literal types, stream counts, weight encodings, the four
-sequence-table modes for each table, checksum, frames without content size, window
-descriptors).  The GPU test (test_gpu_decode.py) decodes the same frames."""
+sequence-table modes for each table, every size of the literals header and of the sequence
+count, checksum, frames without content size, window descriptors).  Two vectors are assembled
+by hand where libzstd produces no such frame at these sizes (the 3-byte sequence count, RLE
+literals with the 1- and 3-byte headers); libzstd decodes them like the others.  The GPU test (test_gpu_decode.py) decodes the same frames."""
 import ctypes
 import hashlib
 import json
@@ -18,7 +20,11 @@ FIX = os.path.join(T.GOLDEN, "decode_frames.json")
 
 ALL_PATHS = {"block_compressed", "block_raw", "block_rle", "checksum", "huf_1stream", "huf_4stream", "lit_huffman", "lit_raw", "lit_rle",
              "lit_treeless", "ll_fse", "ll_predefined", "ll_repeat", "ll_rle", "ml_fse", "ml_predefined", "ml_repeat", "ml_rle", "no_fcs",
-             "no_sequences", "of_fse", "of_predefined", "of_repeat", "of_rle", "weights_direct", "weights_fse", "window_descriptor"}
+             "no_sequences", "of_fse", "of_predefined", "of_repeat", "of_rle", "weights_direct", "weights_fse", "window_descriptor",
+             # every size of the literals header and of the sequence count, each stream count with each weight encoding
+             "lit_raw_h1", "lit_raw_h2", "lit_raw_h3", "lit_rle_h1", "lit_rle_h2", "lit_rle_h3", "lit_huf_h3", "lit_huf_h4", "lit_huf_h5",
+             "lit_treeless_h3", "lit_treeless_h4", "nseq_bytes1", "nseq_bytes2", "nseq_bytes3", "huf_1stream_weights_direct",
+             "huf_1stream_weights_fse", "huf_4stream_weights_direct", "huf_4stream_weights_fse"}
 
 
 def vectors():
