@@ -54,25 +54,15 @@ enum : u32 {
 // segments' runs are adjacent.
 // ZH_K3_W waves run one block's chains (21 segments per table and wave): the batch row of a
 // layout holds ZH_K3_SLOTS = 64 ZH_K3_W segment slots.
-#ifndef ZH_K3_W
 #define ZH_K3_W 1u
-#endif
 #define ZH_K3_SEGS (21u * ZH_K3_W)
 #define ZH_K3_SLOTS (64u * ZH_K3_W)
 #define ZH_K3_RUN 16u
-// Slot of (table t, segment g) in a batch row.  Segment-major (3 g + t, the default): a step's LL,
-// OF and ML runs are adjacent, so the packing kernel's loads of one segment's 16 steps touch one or
-// two 128-B lines instead of three (table-major t * SEGS + g: three lines, each used for 32 B)
-#ifndef ZH_K3_SEGMAJOR
-#define ZH_K3_SEGMAJOR 1
-#endif
-#if ZH_K3_SEGMAJOR
+// Slot of (table t, segment g) in a batch row.  Segment-major (3 g + t): a step's LL, OF and ML
+// runs are adjacent, so the packing kernel's loads of one segment's 16 steps touch one or two
+// 128-B lines (tried table-major, t * SEGS + g: three lines, each used for 32 B)
 #define ZH_K3_SLOT(t, g) (3u * (g) + (t))
 #define ZH_K3_TSTRIDE ZH_K3_RUN  // elements between a step's LL, OF and ML entries
-#else
-#define ZH_K3_SLOT(t, g) ((t) * ZH_K3_SEGS + (g))
-#define ZH_K3_TSTRIDE (ZH_K3_SEGS * ZH_K3_RUN)
-#endif
 #define ZH_K3_SEGLEN(nbseq) ((((nbseq) + ZH_K3_SEGS - 1u) / ZH_K3_SEGS + ZH_K3_RUN - 1u) & ~(ZH_K3_RUN - 1u))
 #define ZH_K3_CODES(L) (2u * ZH_K3_SLOTS * (L))  // byte offset of the codes (after the u16 states)
 #define ZH_K3_BYTES(nbseq) (3u * ZH_K3_SLOTS * ZH_K3_SEGLEN(nbseq))

@@ -10,8 +10,8 @@
 //
 // Per input buffer (frames + skippable frames, concatenated), per block:
 //   literals   raw / RLE are used in place; Huffman (direct or FSE-compressed weights,
-//              1 or 4 streams, treeless reuse) decoded by lanes 0..3 into the item's
-//              workspace slot
+//              1 or 4 streams, treeless reuse) decoded segment-parallel by the 64 lanes
+//              (huf_streams_par) into the item's workspace slot
 //   sequences  NCount / RLE / predefined / repeat tables (LDS), the interleaved FSE
 //              bitstream decoded serially (the format has one state chain per table),
 //              repcodes resolved on the fly, records (ll | ml-3 | offset) to the slot
@@ -42,28 +42,11 @@
 
 typedef int64_t s64;
 
-// 1: the quad sequence kernel (four lanes per buffer); 0: the one-lane-per-buffer kernel
-#ifndef ZH_EXEC_CHASE
-#define ZH_EXEC_CHASE 1  // (with the start bitmap) in-window sources followed in pass A; no pass B
-#endif
-#ifndef ZH_DEC_HUFPAR
-#define ZH_DEC_HUFPAR 1  // segment-parallel Huffman literal streams (0: one lane per stream)
-#endif
-#ifndef ZH_DEC_QUAD
-#define ZH_DEC_QUAD 1
-#endif
-
 namespace {
 
 constexpr u32 DEC_THREADS = 64;
-#ifndef ZH_DEC_STAGE
-#define ZH_DEC_STAGE 8192
-#endif
-#ifndef ZH_HSTAGE
-#define ZH_HSTAGE 1024
-#endif
-constexpr u32 DEC_STAGE = ZH_DEC_STAGE;  // output window (LDS)
-constexpr u32 HSTAGE = ZH_HSTAGE;        // per-stream LDS stage of a Huffman stream
+constexpr u32 DEC_STAGE = 8192;   // output window (LDS)
+constexpr u32 HSTAGE = 1024;      // per-stream LDS stage of a Huffman stream
 constexpr u32 SSTAGE = 4096;      // LDS stage of the sequence bitstream
 constexpr u32 HUF_LOG_MAX = 11;   // RFC 8878 §4.2.1: Max_Number_of_Bits <= 11
 constexpr u32 BLOCKSIZE_MAX = 128u * 1024u;
@@ -102,7 +85,6 @@ constexpr u32 TAB_NONE = 0xFFFFu, TAB_PREDEF = 0xFFFEu;  // tkind; else RLE symb
 // workgroups per CU).
 template <bool TAB>
 struct DecLdsT {
-  static constexpr bool kLitStage = false;
   static constexpr bool kStartMap = false;
   static constexpr bool kTablesOnly = TAB;
   u32 fse[1280];  // LL [0,512) OF [512,768) ML [768,1280): sym | nbBits << 8 | newState << 16
@@ -585,7 +567,6 @@ __device__ void wave_fill(u8 *dst, u32 v, u32 n) {
 }
 
 // Literals section (RFC 8878 §3.1.1.3.1).  Returns section bytes, 0 on error (status in st).
-#if ZH_DEC_HUFPAR
 // ---- segment-parallel Huffman streams --------------------------------------------------------
 // One lane per stream (the libzstd decoder's shape) makes a block's literals a chain of
 // n / 4 dependent table reads.  A Huffman code resynchronises within a few symbols when
@@ -602,32 +583,19 @@ __device__ void wave_fill(u8 *dst, u32 v, u32 n) {
 //           prefix sum of the counts before it.
 // The symbols and the stream verdict equal the serial decode's: a stream is valid when the
 // counts add up to its symbol count and the last segment ends exactly at bit 0.
-#ifndef ZH_HP_TRAJ
-#define ZH_HP_TRAJ 32
-#endif
-constexpr u32 HP_TRAJ = ZH_HP_TRAJ;
+constexpr u32 HP_TRAJ = 32;
 static_assert(HP_TRAJ * 64 * 2 <= 4 * (HSTAGE + 16), "trajectory records fit the stream stages");
 
 // A lane's reader over one stream: dwords from the 4-aligned base ab (dwords holding no stream
 // byte read as 0, so no load leaves the pages the stream touches), a 4-dword window w0..w3 at
-// dword index wi and the two dwords below it prefetched.  Bits below the stream's bit 0 read
-// as zeros (the serial reader's rule).
-#ifndef ZH_HUF_PF2
-#define ZH_HUF_PF2 1  // prefetch two slides ahead (4 dwords) instead of one
-#endif
-#ifndef ZH_HUF_PF3
-#define ZH_HUF_PF3 0  // (with PF2) three slides ahead
-#endif
+// dword index wi and the four dwords below it (two slides ahead) prefetched.  Bits below the
+// stream's bit 0 read as zeros (the serial reader's rule).  (Tried one slide ahead: decode 115.9
+// against 119.1 GB/s, DESIGN.md "Decoder"; three ahead was not kept either.)
 struct HufReader {
   const u32 *ab;
   s32 da8, lastw, wi, p;
   u32 w0, w1, w2, w3, q0, q1;
-#if ZH_HUF_PF2
   u32 q2, q3;  // dwords wi-2, wi-1 (q0, q1: wi-4, wi-3)
-#endif
-#if ZH_HUF_PF3
-  u32 r0, r1;  // dwords wi-6, wi-5 (a third slide ahead)
-#endif
   __device__ __forceinline__ u32 ld(s32 i) const { return (i >= 0 && i <= lastw) ? ab[i] : 0u; }
   __device__ __forceinline__ void init(const u8 *sp, u32 n) {
     ab = (const u32 *)((uintptr_t)sp & ~(uintptr_t)3);
@@ -638,40 +606,19 @@ struct HufReader {
     p = pos;
     wi = ((pos + da8 + 31) >> 5) - 4;  // bit pos lies in (96, 128] of the window
     w0 = ld(wi); w1 = ld(wi + 1); w2 = ld(wi + 2); w3 = ld(wi + 3);
-#if ZH_HUF_PF2
     q2 = ld(wi - 2); q3 = ld(wi - 1);
     q0 = ld(wi - 4); q1 = ld(wi - 3);
-#if ZH_HUF_PF3
-    r0 = ld(wi - 6); r1 = ld(wi - 5);
-#endif
-#else
-    q0 = ld(wi - 2); q1 = ld(wi - 1);
-#endif
   }
   // decode one symbol: sym | nbBits << 8
   __device__ __forceinline__ u32 next(const u16 *dt, u32 tlog) {
     s32 v = p + da8 - 32 * wi - (s32)tlog;  // window bit of the peek's lowest bit
     if (v < 32) {  // slide down two dwords (v >= 21: a step consumes <= 11 bits)
-#if ZH_HUF_PF2
       w3 = w1; w2 = w0; w1 = q3; w0 = q2;
       q3 = q1; q2 = q0;
       wi -= 2;
       v += 64;
-#if ZH_HUF_PF3
-      q1 = r1; q0 = r0;
-      r0 = ld(wi - 6);
-      r1 = ld(wi - 5);
-#else
       q0 = ld(wi - 4);
       q1 = ld(wi - 3);
-#endif
-#else
-      w3 = w1; w2 = w0; w1 = q1; w0 = q0;
-      wi -= 2;
-      v += 64;
-      q0 = ld(wi - 2);
-      q1 = ld(wi - 1);
-#endif
     }
     u32 const k = (u32)v >> 5;  // 1..3
     // (mask selects: the compiler turns a select chain on k into a scratch-indexed array)
@@ -780,7 +727,6 @@ __device__ __forceinline__ bool huf_streams_par(DecLds &L, u32 ns, const u8 *msp
   }
   return true;
 }
-#endif
 
 // The literals section's size without decoding it (the split pipeline's tables pass); 0 when
 // its header is corrupt -- the literals pass then finds and reports the same error.
@@ -871,21 +817,12 @@ __device__ u32 decode_literals(DecLds &L, const u8 *bp, u32 bsz, const Slot &sl,
   if (lane == 0) L.lst_t[0] = __builtin_amdgcn_s_memtime();
 #endif
   if (lt == 2) {
-    // the tree description (<= 128 bytes) staged in LDS first: lane 0's weight decode is a
-    // serial FSE chain whose every byte read was a dependent global load
-#ifndef ZH_DEC_WSTAGE
-#define ZH_DEC_WSTAGE 0  // (1: 117.7 GB/s vs 119.1 without; profiles/r06u_dec_p5_reader_ab.json)
-#endif
-    const u8 *wp = p;
-    if (ZH_DEC_WSTAGE) {
-      u32 const wn = min(rem, 128u);
-      u8 *const ws = L.u.h.hs[0];
-      for (u32 k = lane; k < wn; k += 64) ws[k] = p[k];
-      __syncthreads();
-      wp = ws;
-    }
+    // (tried staging the tree description, <= 128 bytes, in LDS first, lane 0's weight decode being
+    // a serial chain of dependent global byte loads: 117.7 GB/s against 119.1 without;
+    // profiles/r06u_dec_p5_reader_ab.json)
+    const u8 *const wp = p;  // (a copy: reading through p itself changes the kernel's register allocation)
     if (lane == 0) {
-      u32 const used = huf_read_weights(L, wp, ZH_DEC_WSTAGE ? min(rem, 128u) : rem);
+      u32 const used = huf_read_weights(L, wp, rem);
       L.err = used ? 0u : 1u;
       L.hvalid = used ? 1u : 0u;
       L.used = used;
@@ -936,7 +873,6 @@ __device__ u32 decode_literals(DecLds &L, const u8 *bp, u32 bsz, const Slot &sl,
       off[k] = k * seg;
     }
   }
-#if ZH_DEC_HUFPAR
   {
     u32 const k = lane / (64u / ns);
     const u8 *msp = sp[0];
@@ -945,48 +881,6 @@ __device__ u32 decode_literals(DecLds &L, const u8 *bp, u32 bsz, const Slot &sl,
       if (k == t) { msp = sp[t]; mn = ssz[t]; mc = cnt[t]; mo = off[t]; }
     if (!huf_streams_par(L, ns, msp, mn, mc, mo, sl.lit, tlog)) { st = ST_CORRUPT; return 0; }
   }
-#else
-  // lanes 0..ns-1 decode one stream each, reading it from an LDS stage; a lane whose
-  // stage runs out stops, and the wave restages every such stream in one burst per round
-  const u8 *mp = sp[0];
-  u32 msz = ssz[0], mc = cnt[0], mo = off[0];
-  for (u32 k = 1; k < 4; k++)
-    if (lane == k) { mp = sp[k]; msz = ssz[k]; mc = cnt[k]; mo = off[k]; }
-  bool const act = lane < ns;
-  BitRevS r;
-  bool bad = !r.start(mp, act ? msz : 0u) && act;
-  u32 const mcnt = act && !bad ? mc : 0u;
-  u8 *const o = sl.lit + mo;
-  u8 *const stg = L.u.h.hs[lane & 3u];
-  u32 i = 0;
-  for (;;) {
-    bool need = false;
-    while (i < mcnt) {
-      // one container check per 4 symbols: a refill leaves >= 57 bits and 4 x 11 fit
-      if (!r.ensure(stg, 4 * tlog)) { need = true; break; }
-      u32 const k4 = min(4u, mcnt - i);
-      for (u32 u = 0; u < k4; u++) {
-        u32 const e = L.u.h.dt[(u32)r.bits(tlog)];
-        o[i + u] = (u8)e;
-        r.pos -= (s32)(e >> 8);
-      }
-      i += k4;
-    }
-    u64 const nm = __ballot(need);
-    if (!nm) break;
-    u32 lo, hi;
-    r.stage_range(HSTAGE, lo, hi);
-    for (u32 k = 0; k < 4; k++) {
-      if (!((nm >> k) & 1u)) continue;
-      u32 const lk = __builtin_amdgcn_readlane(lo, k), hk = __builtin_amdgcn_readlane(hi, k);
-      stage_copy(L.u.h.hs[k], sp[k], lk, hk);
-      if (lane == k) r.slo = (s32)lk;
-    }
-    __syncthreads();
-  }
-  bad |= act && r.pos != 0;
-  if (__ballot(bad)) { st = ST_CORRUPT; return 0; }
-#endif
   lits.g = sl.lit;
   lits.rle = 0;
   lits.n = n;
@@ -1188,24 +1082,6 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
     L.wll[lane] = ll;
     L.wlit[lane] = lit0;
     L.woff[lane] = off;
-    // the window's literal bytes, lits [lfirst, lfirst + wlen), staged with 16-byte loads
-    u32 lbase = 0, lfirst = 0;
-    if constexpr (LDS::kLitStage) {
-      if (lits.g) {
-        lfirst = lcur + min(qd, (u32)__builtin_amdgcn_readlane(ll, 0));
-        u32 const nlw = lits.n > lfirst ? min(wlen, lits.n - lfirst) : 0u;
-        if (nlw) {
-          uintptr_t const s0 = (uintptr_t)lits.g + lfirst, a0 = s0 & ~(uintptr_t)15;
-          uintptr_t const alast = ((uintptr_t)lits.g + lits.n - 1) & ~(uintptr_t)15;  // (no chunk past the literals)
-          u32 const nch = (u32)((s0 + nlw - 1 - a0) >> 4) + 1u;
-          for (u32 c = lane; c < nch; c += 64) {
-            uintptr_t const a = min(a0 + 16u * c, alast);
-            *(uint4 *)(L.lst + 16 * c) = *(const uint4 *)a;
-          }
-          lbase = (u32)(s0 - a0);
-        }
-      }
-    }
     if constexpr (LDS::kStartMap) {
       // the sequence of window byte x is the number of sequence starts at or below x, less one:
       // a start bitmap (lane 0's sequence starts at 0 or before) and its per-word prefix counts
@@ -1224,18 +1100,14 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
     __syncthreads();
     XSTAMP(2);
     // pass A
-#ifndef ZH_EXEC_UA
-#define ZH_EXEC_UA 4  // bytes per lane per pass-A round (8: 92.8, 16: 89.2, 4: 93.6 GB/s)
-#endif
-    constexpr u32 UA = ZH_EXEC_UA;
+    constexpr u32 UA = 4;  // bytes per lane per pass-A round (8: 92.8, 16: 89.2, 4: 93.6 GB/s)
     for (u32 x0 = 0; x0 < wlen; x0 += 64 * UA) {
       const u8 *ad[UA];
       bool w[UA];
-      u32 li[UA];  // (staged literals: the byte's stage index, else ~0)
 #pragma unroll
       for (u32 t = 0; t < UA; t++) {
         u32 const x = x0 + 64 * t + lane;
-        if constexpr (LDS::kStartMap && ZH_EXEC_CHASE) {
+        if constexpr (LDS::kStartMap) {
           // every byte here: an in-window source is followed back (sequence by sequence, each
           // step to an earlier one or into a literal run) to a literal or a byte already in HBM
           u32 y = x < wlen ? x : 0u;
@@ -1261,7 +1133,6 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
             }
             y = (u32)sw;
           }
-          li[t] = ~0u;
           w[t] = x < wlen;
           if (lit) {
             ad[t] = lits.g ? lits.g + litidx : nullptr;
@@ -1271,25 +1142,14 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
           }
           continue;
         }
+        // (no start map: the sequence of byte x by binary search on the starts)
         u32 j = 0;
-        if constexpr (LDS::kStartMap) {
-          u64 const e = ((const u64 *)L.bm)[min(x >> 5, 63u)];
-          u32 const m = (u32)e & (0xFFFFFFFFu >> (31u - (x & 31u)));
-          j = min((u32)(e >> 32) + (u32)__popc(m) - 1u, 63u);  // (bytes past wlen: any j, unused)
-        } else {
 #pragma unroll
-          for (u32 stp = 32; stp; stp >>= 1) j += L.wvs[j + stp] <= (s32)x ? stp : 0u;
-        }
+        for (u32 stp = 32; stp; stp >>= 1) j += L.wvs[j + stp] <= (s32)x ? stp : 0u;
         u32 const d = (u32)((s32)x - L.wvs[j]);
         u32 const llj = L.wll[j];
-        li[t] = ~0u;
         if (d < llj) {
-          if (LDS::kLitStage && lits.g) {
-            li[t] = lbase + L.wlit[j] + d - lfirst;
-            ad[t] = nullptr;
-          } else {
-            ad[t] = lits.g ? lits.g + L.wlit[j] + d : nullptr;
-          }
+          ad[t] = lits.g ? lits.g + L.wlit[j] + d : nullptr;
           w[t] = x < wlen;
         } else {
           u32 const m = d - llj, offj = L.woff[j];
@@ -1301,13 +1161,7 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
       }
       u8 v[UA];
 #pragma unroll
-      for (u32 t = 0; t < UA; t++) {
-        if constexpr (LDS::kLitStage) {
-          v[t] = !w[t] ? (u8)0 : li[t] != ~0u ? L.lst[min(li[t], (u32)sizeof(L.lst) - 1u)] : ad[t] ? *ad[t] : (u8)lits.rle;
-        } else {
-          v[t] = w[t] ? (ad[t] ? *ad[t] : (u8)lits.rle) : (u8)0;
-        }
-      }
+      for (u32 t = 0; t < UA; t++) v[t] = w[t] ? (ad[t] ? *ad[t] : (u8)lits.rle) : (u8)0;
 #pragma unroll
       for (u32 t = 0; t < UA; t++)
         if (w[t]) L.u.out[x0 + 64 * t + lane] = v[t];
@@ -1316,7 +1170,7 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
     // pass B: matches with a source inside the window, in order
     s32 const mlo = ms < 0 ? -ms : 0;
     s32 const mhi = min((s32)ml, (s32)wlen - ms);
-    bool const nearp = !(LDS::kStartMap && ZH_EXEC_CHASE) && valid && mhi > mlo && ms - (s32)off + (s32)min(off, (u32)mhi) - 1 >= 0;
+    bool const nearp = !LDS::kStartMap && valid && mhi > mlo && ms - (s32)off + (s32)min(off, (u32)mhi) - 1 >= 0;
     u64 nm = __ballot(nearp);
     while (nm) {
       u32 const j = (u32)__builtin_ctzll(nm);
@@ -1364,8 +1218,8 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
 // ---- split pipeline.  A buffer holding one frame of one compressed block (every chunk
 // of a batch) is decoded by three kernels: phase 1 (this kernel) does the headers, the
 // literals and the sequence tables and leaves a hand-off record; zh_dec_seq_kernel runs
-// the sequence bitstreams of 64 such buffers at once, one lane each (the serial FSE chains
-// of 64 blocks interleave in one wave instead of one chain per wave); zh_dec_exec_kernel
+// the sequence bitstreams of 16 such buffers per wave, four lanes each (the serial FSE chains
+// of 16 blocks interleave in one wave instead of one chain per wave); zh_dec_exec_kernel
 // (phase 3) executes the block and finishes the frame.  Anything else is decoded in phase 1.
 struct DecHandoff {
   u32 tabs[1280];  // DecLds::fse of the block
@@ -1602,17 +1456,12 @@ __device__ __forceinline__ void decode_body(LDS &L, ZhDecArgs a) {
           if (modes & 3u) { st = ST_CORRUPT; break; }
           // the table descriptions staged in LDS with one wave load: lane 0's NCount parse was a
           // chain of dependent global byte loads (three descriptions take <= ~240 bytes)
-#ifndef ZH_DEC_TSTAGE
-#define ZH_DEC_TSTAGE 320u
-#endif
-          u32 const tb = min(rem, (u32)ZH_DEC_TSTAGE);
-          const u8 *tsrc = sp;
-          if (ZH_DEC_TSTAGE) {
-            for (u32 k = lane; k < tb; k += 64) L.u.sstage[k] = sp[k];
-            __syncthreads();
-            tsrc = L.u.sstage;
-          }
-          u32 const tavail = ZH_DEC_TSTAGE ? tb : rem;
+          constexpr u32 DEC_TSTAGE = 320;
+          u32 const tb = min(rem, DEC_TSTAGE);
+          for (u32 k = lane; k < tb; k += 64) L.u.sstage[k] = sp[k];
+          __syncthreads();
+          const u8 *const tsrc = L.u.sstage;
+          u32 const tavail = tb;
           if (lane == 0) {
             u32 e = 0, used = 0;
             u32 const md[3] = {modes >> 6, (modes >> 4) & 3u, (modes >> 2) & 3u};
@@ -1645,7 +1494,6 @@ __device__ __forceinline__ void decode_body(LDS &L, ZhDecArgs a) {
           if ((a.phase == 1 || a.phase == 4) && produced == 0 && last && ip + bsz + (chk ? 4ull : 0ull) == srcn) {
             // the buffer's only block: hand the sequence bitstream to zh_dec_seq_kernel
             DecHandoff *const ho = handoff(a, item);
-#if ZH_DEC_QUAD
             // the quad sequence kernel's entries: newState | symbol << 9 | extra bits << 16 |
             // state bits << 24 (the extra bits of a code: LL / ML from the code tables, OF = code)
             for (u32 w = lane; w < 1280; w += 64) {
@@ -1653,9 +1501,6 @@ __device__ __forceinline__ void decode_body(LDS &L, ZhDecArgs a) {
               u32 const xb = w < 512 ? L.info[0][sym] >> 24 : w < 768 ? sym : L.info[1][sym] >> 24;
               ho->tabs[w] = (e >> 16) | sym << 9 | xb << 16 | ((e >> 8) & 0xFFu) << 24;
             }
-#else
-            for (u32 w = lane; w < 1280; w += 64) ho->tabs[w] = L.fse[w];
-#endif
             if (lane == 0) {
               ho->sp = (u64)sp;
               ho->rem = rem;
@@ -1792,30 +1637,16 @@ extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_tables_kernel(Z
 // Phase 3: execute the block of a buffer deferred by phase 1 (its sequence records are in
 // the slot) and finish the frame.  Its own kernel with only the execution window in LDS
 // (ExecLds, ~9 KB against DecLds' ~16 KB), so twice as many buffers execute per CU.
-#ifndef ZH_EXEC_STAGE
-#define ZH_EXEC_STAGE 2048  // (8192: 87.8 GB/s, 1024: 92.9, 2048: 92.8, 3072: 92.4; profiles/r06o_dec_exec_ab.json)
-#endif
-#ifndef ZH_EXEC_LSTAGE
-#define ZH_EXEC_LSTAGE 0
-#endif
-#ifndef ZH_EXEC_BM
-#define ZH_EXEC_BM 1
-#endif
+constexpr u32 EXEC_STAGE = 2048;  // (8192: 87.8 GB/s, 1024: 92.9, 2048: 92.8, 3072: 92.4; profiles/r06o_dec_exec_ab.json)
 struct ExecLds {
-  static constexpr bool kLitStage = ZH_EXEC_LSTAGE != 0;
-  static constexpr bool kStartMap = ZH_EXEC_BM != 0;
+  static constexpr bool kStartMap = true;
   union {
-    u8 out[ZH_EXEC_STAGE + 16];
+    u8 out[EXEC_STAGE + 16];
   } u;
   s32 wvs[68];
   u32 wll[64], wlit[64], woff[64];
-#if ZH_EXEC_BM
-  static_assert(ZH_EXEC_STAGE <= 2048, "one start-map word per lane");
+  static_assert(EXEC_STAGE <= 2048, "one start-map word per lane");
   alignas(8) u32 bm[128];  // word 2 w: the window bytes [32 w, 32 w + 32) where a sequence starts; 2 w + 1: starts before them
-#endif
-#if ZH_EXEC_LSTAGE
-  __attribute__((aligned(16))) u8 lst[ZH_EXEC_STAGE + 32];  // the window's literal bytes
-#endif
 };
 
 extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_exec_kernel(ZhDecArgs a) {
@@ -1876,96 +1707,31 @@ extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_exec_kernel(ZhD
   return;
 }
 
-// Sequence bitstreams of deferred buffers: lanes = buffers, 64 per wave, so the serial FSE
-// state chains of 64 blocks advance under one instruction stream.  A step's only exposed
-// memory latency is the three table reads (each lane's tables sit in its hand-off record);
-// the bitstream window it needs was fetched one step earlier (win_fetch below), and decoded
-// sequences leave through an LDS ring.  The chain is issue-latency bound: one wave per SIMD,
-// ~180 dependent instructions a step.  Measured alternatives (profiles/r02m_dec_seq.json):
-// 4-32 buffers per wave with the tables staged in LDS (32- or 16-bit entries) were slower,
-// both isolated and pipelined -- LDS-limited occupancy, no shorter chain.
-#ifndef ZH_D2_BUF
-#define ZH_D2_BUF 64
-#endif
-[[maybe_unused]] constexpr u32 D2_BUF = ZH_D2_BUF;
-// Decoded sequences go to an LDS ring and leave in 256-byte bursts every D2_RUN steps:
-// CDNA's vmcnt counts stores too and retires in order, so a per-step global store would
-// make every window load wait for the previous step's write acknowledgement.
-[[maybe_unused]] constexpr u32 D2_RUN = 32;
-
-// the top k (<= 31) bits of T; T <<= k
-__device__ __forceinline__ u32 take(u64 &T, u32 k) {
-  u32 const hi32 = (u32)(T >> 32);
-  u32 const v = k ? hi32 >> (32u - k) : 0u;
-  T <<= k;
-  return v;
-}
-
-// resolve_off without branches (the lanes of a wave decode different blocks)
-__device__ __forceinline__ u32 resolve_off_bf(u32 ofv, u32 ll, u32 &r0, u32 &r1, u32 &r2) {
-  bool const lit = ofv > 3;
-  u32 const idx = ofv - 1 + (ll == 0 ? 1u : 0u);  // repeat index when !lit: 0..3
-  u32 rs = idx == 1 ? r1 : idx == 2 ? r2 : r0 - 1;
-  rs += rs == 0 ? 1u : 0u;
-  u32 const off = lit ? ofv - 3 : idx == 0 ? r0 : rs;
-  bool const upd = lit || idx != 0;
-  u32 const n2 = (!lit && idx == 1) ? r2 : r1;
-  r2 = upd ? n2 : r2;
-  r1 = upd ? r0 : r1;
-  r0 = upd ? off : r0;
-  return off;
-}
-
-// a 320-bit bitstream window: the five little-endian words from an 8-aligned address
-struct Win5 {
-  u64 w0, w1, w2, w3, w4;
-};
-
-// 64 bits of the window ending at bit t (t < 320), bit t - 1 as the MSB; bits below the
-// window read as zeros (t < 64: the stream's first bits).  Two halving selects, not a word
-// index: an indexed form is lowered to a scratch array.
-__device__ __forceinline__ u64 win64(const Win5 &w, u32 t) {
-  u32 const b = t - 64u, r = b & 63u;
-  bool const h2 = b >= 128u, h1 = (b & 64u) != 0u;
-  u64 const y0 = h2 ? w.w2 : w.w0, y1 = h2 ? w.w3 : w.w1, y2 = h2 ? w.w4 : w.w2;
-  u64 const lo = h1 ? y1 : y0, hi = h1 ? y2 : y1;
-  u64 const v = r ? (lo >> r) | (hi << (64u - r)) : lo;
-  return (s32)b < 0 ? w.w0 << ((64u - t) & 63u) : v;
-}
-
-typedef const __attribute__((address_space(1))) u64 *gptr64;
-
-// the five words from the 8-aligned address A (global, not flat, loads: LDS waits do not
-// wait for them; one address, four immediate offsets)
-__device__ __forceinline__ Win5 win_fetch(uintptr_t A) {
-  gptr64 const q = (gptr64)A;
-  return Win5{q[0], q[1], q[2], q[3], q[4]};
-}
-
-#if ZH_DEC_QUAD
-// Quad sequence kernel: FOUR lanes per buffer, 16 buffers per wave.  A block's FSE chain is
-// serial (decoding from a guessed entry never rejoins the true trajectory: tools/seq_sync.py
-// measured 0 of 240 guesses synchronising over whole C3 blocks), so the step itself is what
-// has to get shorter.  Lane q of a quad owns one table: 0 = offsets, 1 = match lengths,
+// Sequence bitstreams of deferred buffers, the quad sequence kernel: FOUR lanes per buffer, 16
+// buffers per wave, so the serial FSE state chains of 16 blocks advance under one instruction
+// stream.  A block's FSE chain is serial (decoding from a guessed entry never rejoins the true
+// trajectory: tools/seq_sync.py measured 0 of 240 guesses synchronising over whole C3 blocks),
+// so the step itself is what has to get shorter.  Lane q of a quad owns one table: 0 = offsets, 1 = match lengths,
 // 2 = literal lengths, 3 = the record (repcodes, ring).  A step is the same instruction stream
 // for all of them: one table read each (entries repacked by phase 1 as newState | symbol << 9
 // | extra bits << 16 | state bits << 24), three quad broadcasts (DPP) give every lane the
 // bit offsets of its two fields (extra bits in the order OF, ML, LL from the top, then the
 // states LL, ML, OF), two 64-bit reads of a 32-byte window the previous step staged in LDS
-// by an LDS-DMA load, and three broadcasts more hand the values to lane 3.  About half the
-// instructions of the one-lane step, and four times as many waves to share the SIMDs the
-// 64-buffer waves left idle.
-#ifndef ZH_DQ_XCD
-#define ZH_DQ_XCD 0
-#endif
-#ifndef ZH_DQ_PF
-#define ZH_DQ_PF 0
-#endif
+// by an LDS-DMA load, and three broadcasts more hand the values to lane 3.  Decoded sequences go
+// to an LDS ring and leave in 256-byte bursts every DQ_RUN steps: CDNA's vmcnt counts stores too
+// and retires in order, so a per-step global store would make every window load wait for the
+// previous step's write acknowledgement.
+// Tried before it: one lane per buffer, 64 buffers per wave (~180 dependent instructions a step,
+// issue-latency bound with one wave per SIMD; the quad step has about half the instructions and
+// four times as many waves to share the SIMDs), and 4-32 buffers per wave with the tables staged
+// in LDS (32- or 16-bit entries): slower, both isolated and pipelined -- LDS-limited occupancy, no
+// shorter chain (profiles/r02m_dec_seq.json).  Tried on the quad kernel and not kept (DESIGN.md
+// "Decoder"): items mapped to the XCD their phase 1 ran on, an early touch of the next table line.
 constexpr u32 DQ_BUF = 16;  // buffers per wave
 constexpr u32 DQ_RUN = 32;  // records per ring run (256 bytes per buffer)
 
-// resolve_off_bf with the repeat candidates picked by masks: the nested selects of the
-// one-lane kernel compile to exec-mask branches here
+// resolve_off without branches (the quads of a wave decode different blocks), the repeat
+// candidates picked by masks: nested selects compile to exec-mask branches here
 __device__ __forceinline__ u32 resolve_off_masks(u32 ofv, u32 ll, u32 &r0, u32 &r1, u32 &r2) {
   bool const lit = ofv > 3;
   u32 const idx = ofv - 1 + (ll == 0 ? 1u : 0u);  // repeat index when !lit: 0..3
@@ -1990,26 +1756,19 @@ typedef const __attribute__((address_space(1))) void *gvoid;
 typedef __attribute__((address_space(3))) void *lvoid;
 
 extern "C" __global__ __launch_bounds__(64) void zh_dec_seq_kernel(ZhDecArgs a, u32 nitems) {
+  // highest issue priority: the chains are issue-latency bound and share SIMDs with the waves of
+  // the pipeline's other phases
   __builtin_amdgcn_s_setprio(3);
   __shared__ u32 info[4][64];  // baselines by code: OF (1 << code), ML, LL, none
   __shared__ __attribute__((aligned(16))) u32 win[2][DQ_BUF][16];  // stream windows, 64 B per quad
   __shared__ __attribute__((aligned(16))) u64 ring[DQ_BUF][DQ_RUN];
-#if ZH_DQ_PF
-  __shared__ u32 pfd[64];  // (the prefetch's landing words, never read)
-#endif
   u32 const lane = lane_id(), q = lane & 3u, b = lane >> 2;
   info[0][lane] = lane < 32 ? 1u << lane : 0u;
   info[1][lane] = lane < 53 ? c_ML_info[lane] & 0xFFFFFFu : 0u;
   info[2][lane] = lane < 36 ? c_LL_info[lane] & 0xFFFFFFu : 0u;
   info[3][lane] = 0u;
   __syncthreads();
-#if ZH_DQ_XCD
-  // the items phase 1 ran on this workgroup's XCD (blocks b and b + 8 share one): workgroup w
-  // takes items w % 8 + 8 (16 (w / 8) + b), so their tables are in the local L2 (speed only)
-  u32 const it = a.item0 + (blockIdx.x & 7u) + 8u * (DQ_BUF * (blockIdx.x >> 3) + b), end = a.item0 + nitems;
-#else
   u32 const it = a.item0 + blockIdx.x * DQ_BUF + b, end = a.item0 + nitems;
-#endif
   if (it >= end) return;  // (quad-uniform from here on: the four lanes read the same buffer)
   DecHandoff *const ho = handoff(a, it);
   if (ho->flag != 1) return;
@@ -2071,12 +1830,6 @@ extern "C" __global__ __launch_bounds__(64) void zh_dec_seq_kernel(ZhDecArgs a, 
       u32 const xv = field(cur, pos - (s32)((pre & 0xFFu) + xb) - wb, xb);
       u32 const sv = field(cur, pos - (s32)(X + NB) + (s32)(pre >> 8) - wb, nb);
       pos -= (s32)(X + NB);
-#if ZH_DQ_PF
-      // the next entry lies in [newState, newState + 2^nb): one 128-byte line when nb <= 5;
-      // touch it before the window read that finishes the state (an LDS-DMA load, so no
-      // register waits for it)
-      __builtin_amdgcn_global_load_lds((gvoid)(tq + (e & 0x1FFu)), (lvoid)&pfd[0], 4, 0, 0);
-#endif
       s = q == 3 ? 0u : (e & 0x1FFu) + sv;
       u32 const en = tq[s];       // step i + 1 (after the last step: a harmless read)
       wb = fetch(pos, cur ^ 1u);  // (after the last step too: no branch; drained below)
@@ -2103,118 +1856,6 @@ extern "C" __global__ __launch_bounds__(64) void zh_dec_seq_kernel(ZhDecArgs a, 
   if (q == 2) ho->sumLL = acc;
   if (q == 3) ho->sbad = (bad || pos != 0 || big) ? 1u : 0u;
 }
-#else
-extern "C" __global__ __launch_bounds__(D2_BUF) void zh_dec_seq_kernel(ZhDecArgs a, u32 nitems) {
-  // highest issue priority: the chains are issue-latency bound and share SIMDs with the
-  // phase-1 / phase-3 waves of the other groups of the pipeline
-  __builtin_amdgcn_s_setprio(3);
-  __shared__ u32 info[2][64];
-  __shared__ u64 ring[D2_BUF][D2_RUN];
-  u32 const lane = lane_id();
-  for (u32 i = lane; i < 53; i += D2_BUF) {
-    if (i < 36) info[0][i] = c_LL_info[i];
-    info[1][i] = c_ML_info[i];
-  }
-  u32 const it0 = a.item0 + blockIdx.x * D2_BUF, end = a.item0 + nitems;
-  __syncthreads();
-  u32 const it = it0 + lane;
-  if (lane >= D2_BUF || it >= end) return;
-  DecHandoff *const ho = handoff(a, it);
-  if (ho->flag != 1) return;
-  const u32 *const TLL = ho->tabs, *const TOF = TLL + 512, *const TML = TLL + 768;
-  const u8 *const sp = (const u8 *)ho->sp;
-  u32 const nseq = ho->nseq, lg = ho->lg;
-  s32 const n = (s32)ho->rem;
-  u64 *const seq = (u64 *)(a.ws + (size_t)it * a.slot_bytes + a.lit_bytes);
-  u32 const last = n > 0 ? sp[n - 1] : 0u;
-  bool const bad = last == 0;
-  s32 pos = bad ? 0 : 8 * (n - 1) + (s32)hb32(last);
-  u32 rep0 = ho->rep[0], rep1 = ho->rep[1], rep2 = ho->rep[2];
-  bool big = false;
-  u64 sumLL = 0, sumML = 0;
-  if (!bad) {
-    // Bitstream window: w holds the 40 bytes from A, fetched one step ahead -- the window
-    // a step reads was fetched at the start of the previous step for that step's position,
-    // which covers the 128 bits below the current one (a step consumes <= 89 bits), so the
-    // fetch latency hides behind a step of arithmetic.
-    // The window start is clamped to the stream's aligned words [wlo, whi]: near the stream
-    // start bits below the window read as zeros, near its end the window still covers the
-    // top.  A stream of at most 33 bytes fits one window: it is fetched once, word by word.
-    uintptr_t const base = (uintptr_t)sp, wlo = base & ~(uintptr_t)7, whi = (base + (u32)n - 1) & ~(uintptr_t)7;
-    bool const small = whi < wlo + 32;
-    uintptr_t const ahi = small ? wlo : whi - 32;
-    auto wbase = [&](s32 p) {
-      uintptr_t const A = (base + (uintptr_t)(intptr_t)(((p + 7) >> 3) - 32)) & ~(uintptr_t)7;
-      return small ? wlo : (intptr_t)A < (intptr_t)wlo ? wlo : A > ahi ? ahi : A;
-    };
-    uintptr_t A = wbase(pos);
-    Win5 w;
-    if (small) {
-      auto ld = [&](uintptr_t q) { return *(gptr64)(q > whi ? whi : q); };
-      w = Win5{ld(wlo), ld(wlo + 8), ld(wlo + 16), ld(wlo + 24), ld(wlo + 32)};
-    } else {
-      w = win_fetch(A);
-    }
-    auto tpos = [&](s32 p) { return (u32)((s32)(8 * (intptr_t)(base - A)) + p); };
-    u32 sLL, sOF, sML;
-    {  // initial states
-      u64 T = win64(w, tpos(pos));
-      u32 const kL = lg & 0xFFu, kO = (lg >> 8) & 0xFFu, kM = lg >> 16;
-      sLL = take(T, kL);
-      sOF = take(T, kO);
-      sML = take(T, kM);
-      pos -= (s32)(kL + kO + kM);
-    }
-    for (u32 i = 1; i <= nseq; i++) {  // step i: sequence i - 1
-      u32 const eLL = TLL[sLL], eOF = TOF[sOF], eML = TML[sML];
-      // issued after the table reads: vmcnt retires in order, so waiting for the tables
-      // leaves this fetch in flight (it is consumed by the next step)
-      uintptr_t const An = wbase(pos);
-      // (a small stream keeps its window; its lane fetches from its own hand-off record
-      // instead, so the fetch is unconditional and the table wait can leave it in flight)
-      Win5 wn = win_fetch(small ? (uintptr_t)ho : An);  // for step i + 1
-      if (small) wn = w;
-      u32 const ofc = eOF & 0xFFu;
-      u32 const mi = info[1][eML & 0xFFu], li = info[0][eLL & 0xFFu];
-      u32 const mb = mi >> 24, lb = li >> 24;
-      u32 t = tpos(pos);
-      u32 const t0 = t;
-      u64 T = win64(w, t);
-      u32 const ofv = (1u << ofc) + take(T, ofc);
-      u32 const ml = (mi & 0xFFFFFFu) + take(T, mb);
-      u32 const ll = (li & 0xFFFFFFu) + take(T, lb);
-      t -= ofc + mb + lb;
-      u32 const off = resolve_off_bf(ofv, ll, rep0, rep1, rep2);
-      big |= off >= OFF_LIMIT;
-      sumLL += ll;
-      sumML += ml;
-      u32 const r = (i - 1) & (D2_RUN - 1);
-      ring[lane][r] = (u64)ll | (u64)(ml - 3) << 17 | (u64)off << 34;
-      if (r == D2_RUN - 1) {  // a full run: 32 sequences, 256-byte aligned
-        uint4 *const dst = (uint4 *)(seq + (i - D2_RUN));
-        const uint4 *const srcr = (const uint4 *)ring[lane];
-#pragma unroll
-        for (u32 k = 0; k < D2_RUN / 2; k++) dst[k] = srcr[k];
-      }
-      if (i < nseq) {
-        u32 const kL = (eLL >> 8) & 0xFFu, kM = (eML >> 8) & 0xFFu, kO = (eOF >> 8) & 0xFFu;
-        u64 U = win64(w, t);
-        sLL = (eLL >> 16) + take(U, kL);
-        sML = (eML >> 16) + take(U, kM);
-        sOF = (eOF >> 16) + take(U, kO);
-        t -= kL + kM + kO;
-      }
-      pos -= (s32)(t0 - t);
-      A = An;
-      w = wn;
-    }
-    for (u32 k = nseq & ~(D2_RUN - 1); k < nseq; k++) seq[k] = ring[lane][k & (D2_RUN - 1)];  // the partial last run
-  }
-  ho->sumLL = sumLL;
-  ho->sumML = sumML;
-  ho->sbad = (bad || pos != 0 || big) ? 1u : 0u;
-}
-#endif  // ZH_DEC_QUAD
 
 namespace {
 struct DecPipeTag {};
@@ -2240,15 +1881,7 @@ hipError_t launch_decompress(const ZhDecArgs &a0, u32 nitems, hipStream_t stream
     hipLaunchKernelGGL(zh_decode_kernel, dim3(cnt), dim3(DEC_THREADS), 0, s, a);
     check("phase 1");
     if (after_p1) (void)hipEventRecord(after_p1, s);
-#if ZH_DEC_QUAD
-#if ZH_DQ_XCD
-    hipLaunchKernelGGL(zh_dec_seq_kernel, dim3(((cnt + 8 * DQ_BUF - 1) / (8 * DQ_BUF)) * 8), dim3(64), 0, s, a, cnt);
-#else
     hipLaunchKernelGGL(zh_dec_seq_kernel, dim3((cnt + DQ_BUF - 1) / DQ_BUF), dim3(64), 0, s, a, cnt);
-#endif
-#else
-    hipLaunchKernelGGL(zh_dec_seq_kernel, dim3((cnt + D2_BUF - 1) / D2_BUF), dim3(D2_BUF), 0, s, a, cnt);
-#endif
     check("sequences");
     hipLaunchKernelGGL(zh_dec_exec_kernel, dim3(cnt), dim3(DEC_THREADS), 0, s, a);
     check("phase 3");
@@ -2265,16 +1898,6 @@ hipError_t launch_decompress(const ZhDecArgs &a0, u32 nitems, hipStream_t stream
   // Round 6 (quad sequence kernel ~4.3 ms, segment-parallel literals: phase 1 4.5 -> 2.5 ms;
   // profiles/r06n_dec_hufpar_ab.json): two groups 1 : 1 / 2 : 1 / 3 : 1 -> 87.9 / 85.3 / 85.7
   // GB/s, three groups 2 : 1 : 1 / 1 : 1 : 1 -> 86.9 / 81.0, four 1 : 1 : 1 : 1 80.5.
-#ifndef ZH_DEC_G
-#define ZH_DEC_G 2
-#endif
-#ifndef ZH_DEC_W0
-#define ZH_DEC_W0 1
-#endif
-#ifndef ZH_DEC_SPLIT
-#define ZH_DEC_SPLIT 1
-#endif
-#if ZH_DEC_SPLIT
   // Split pipeline: phase 4 (headers + sequence tables of the deferrable buffers, no literals)
   // gates the sequence kernel, which then runs every chain at once beside phase 5 (the
   // literals, and whole decodes of the other buffers) on the side stream; phase 3 waits for
@@ -2285,30 +1908,19 @@ hipError_t launch_decompress(const ZhDecArgs &a0, u32 nitems, hipStream_t stream
     ZhDecArgs a = a0;
     a.item0 = 0;
     a.phase = 4;
-#ifndef ZH_DEC_TABK
-#define ZH_DEC_TABK 1
-#endif
-    if (ZH_DEC_TABK) hipLaunchKernelGGL(zh_dec_tables_kernel, dim3(nitems), dim3(DEC_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL(zh_decode_kernel, dim3(nitems), dim3(DEC_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(zh_dec_tables_kernel, dim3(nitems), dim3(DEC_THREADS), 0, stream, a);
     (void)hipEventRecord(sp2->first_done[0], stream);
     (void)hipStreamWaitEvent(side, sp2->first_done[0], 0);
     a.phase = 5;
-#ifndef ZH_DEC_P5_PAD
-#define ZH_DEC_P5_PAD 0  // (occupancy experiments: dynamic LDS added to phase 5's workgroups)
-#endif
-    hipLaunchKernelGGL(zh_decode_kernel, dim3(nitems), dim3(DEC_THREADS), ZH_DEC_P5_PAD, side, a);
+    hipLaunchKernelGGL(zh_decode_kernel, dim3(nitems), dim3(DEC_THREADS), 0, side, a);
     (void)hipEventRecord(sp2->done[0], side);
-#ifdef ZH_DEC_SERIAL_P5
-    (void)hipStreamWaitEvent(stream, sp2->done[0], 0);  // (diagnostic: phase 5 and the chains one after the other)
-#endif
     hipLaunchKernelGGL(zh_dec_seq_kernel, dim3((nitems + DQ_BUF - 1) / DQ_BUF), dim3(64), 0, stream, a, nitems);
     (void)hipStreamWaitEvent(stream, sp2->done[0], 0);
     a.phase = 3;
     hipLaunchKernelGGL(zh_dec_exec_kernel, dim3(nitems), dim3(DEC_THREADS), 0, stream, a);
     return hipGetLastError();
   }
-#endif
-  constexpr u32 G = ZH_DEC_G, W0 = ZH_DEC_W0, MIN_GROUP = 1024;
+  constexpr u32 G = 2, W0 = 1, MIN_GROUP = 1024;
   StreamPipe<G> *p = (!dbg && nitems >= G * MIN_GROUP) ? stream_pipe<DecPipeTag, G>(stream) : nullptr;
   if (!p) {
     group(0, nitems, stream, nullptr);

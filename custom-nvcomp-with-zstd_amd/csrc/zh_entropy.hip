@@ -16,12 +16,6 @@
 
 namespace {
 
-#ifndef ZH_K2_PAIR
-#define ZH_K2_PAIR 1  // the record pass two chunks per iteration
-#endif
-#ifndef ZH_HIST_PF
-#define ZH_HIST_PF 1  // literal histogram: next step's loads before this step's atomics
-#endif
 constexpr u32 K2_THREADS = 128;  // wave 0: literals section; wave 1: frame/sequences section, finish
 constexpr u32 SW_WORDS = 184;  // >= 512 literal codes of <= 11 bits per append (+ pending bits)
 
@@ -59,10 +53,7 @@ static_assert(OFF_WTS + 256 <= U_HUF_END, "weights inside the nodes' region");
 constexpr u32 K2_WAVE_LDS = (U_HUF_END > U_FSE_END ? U_HUF_END : U_FSE_END);  // one wave's layout
 static_assert(K2_WAVE_LDS < 16384, "K2 LDS budget");
 constexpr u32 K2_W1 = (U_HUF_END - OFF_MISC + 15) & ~15u;  // wave 1's layout base
-#ifndef ZH_K2_LDS_PAD
-#define ZH_K2_LDS_PAD 0  // (occupancy experiments: extra LDS per block)
-#endif
-constexpr u32 K2_LDS = K2_W1 + U_FSE_END + ZH_K2_LDS_PAD;  // 15,952 B: 10 blocks per CU (was 17,632: 9)
+constexpr u32 K2_LDS = K2_W1 + U_FSE_END;  // 15,952 B: 10 blocks per CU (was 17,632: 9)
 
 __constant__ u8 c_LL_bits[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
 __constant__ u8 c_ML_bits[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
@@ -149,9 +140,6 @@ struct BitSink {
   u32 pend;  // pending bits in sw[0] (0..7)
 };
 
-#ifndef ZH_SINK_BF
-#define ZH_SINK_BF 1
-#endif
 template <int K>
 __device__ __forceinline__ void sink_append(BitSink &bs, const Out &o, u32 *sw, const u32 (&val)[K], const u32 (&nb)[K]) {
   u32 const lane = lane_id();
@@ -164,32 +152,18 @@ __device__ __forceinline__ void sink_append(BitSink &bs, const Out &o, u32 *sw, 
   u32 const nwords = (end + 31) >> 5;
   for (u32 w = 1 + lane; w < nwords + 1; w += 64) sw[w] = 0;
   wave_sync();
-#if ZH_SINK_BF
   // branch-free: every field ORs its low part into word bit >> 5 and its high part (0 unless it
   // straddles) into the next word, which lies inside [1, nwords] (zeroed above) since bit < end;
   // a field of 0 bits ORs 0.  Field widths are <= 31 (codes, states, extra bits), so v_bfe masks.
-  u32 *const swa = sw;
 #pragma unroll
   for (int k = 0; k < K; k++) {
     u32 const v = __builtin_amdgcn_ubfe(val[k], 0u, nb[k]);
-    u32 *const wp = swa + (bit >> 5);
+    u32 *const wp = sw + (bit >> 5);
     u32 const sh = bit & 31u;
     __hip_atomic_fetch_or(wp, v << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __hip_atomic_fetch_or(wp + 1, (v >> 1) >> (31u - sh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     bit += nb[k];
   }
-#else
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    if (nb[k]) {
-      u32 const v = val[k] & ((nb[k] >= 32) ? 0xFFFFFFFFu : ((1u << nb[k]) - 1u));
-      u32 const w = bit >> 5, sh = bit & 31;
-      atomicOr(&sw[w], v << sh);
-      if (sh + nb[k] > 32) atomicOr(&sw[w + 1], v >> (32 - sh));
-      bit += nb[k];
-    }
-  }
-#endif
   wave_sync();
   u32 const full = end >> 3;
   const u8 *sb = (const u8 *)sw;
@@ -844,52 +818,10 @@ __device__ u32 huf_write_ctable_wave(u8 *hbuf, u8 *w, const u8 *hnb, u32 maxSV, 
   return ret;
 }
 
-// byte copy global -> Out (wave-parallel)
-// Wave copy of n bytes to o[pos..]: byte head up to a 4-B aligned destination, then
-// dword stores (source realigned with alignbyte, 8 independent loads per lane in
-// flight), byte tail; bytes at or past o.cap are dropped like Out::put does.
-__device__ __forceinline__ void copy_bytes4(const Out &o, u32 pos, const u8 *src, u32 n) {
-  u32 const lane = lane_id();
-  u8 *const d0 = o.dst + pos;
-  u32 const h = min((u32)((4u - ((uintptr_t)d0 & 3u)) & 3u), n);
-  u32 const nw = (n - h) >> 2;
-  u32 const capw = o.cap > pos + h ? (o.cap - pos - h) >> 2 : 0u;
-  u32 const lim = min(nw, capw);
-  const u8 *const s0 = src + h;
-  u32 const sa = (u32)((uintptr_t)s0 & 3u);
-  const u32 *const s32 = (const u32 *)(s0 - sa);
-  u32 *const d32 = (u32 *)(d0 + h);
-#ifndef ZH_COPY_U
-#define ZH_COPY_U 8
-#endif
-  constexpr u32 U = ZH_COPY_U;  // dwords per lane in flight (16: no change on random data, 1.33 ms)
-  for (u32 w0 = 0; w0 < lim; w0 += 64 * U) {
-    u32 v[U];
-#pragma unroll
-    for (u32 u = 0; u < U; u++) {
-      u32 const w = w0 + 64 * u + lane;
-      if (w < lim) {
-        u32 const A = s32[w];
-        u32 const B = sa ? s32[w + 1] : A;  // word w+1 holds an in-range byte when sa != 0
-        v[u] = __builtin_amdgcn_alignbyte(B, A, sa);
-      }
-    }
-#pragma unroll
-    for (u32 u = 0; u < U; u++) {
-      u32 const w = w0 + 64 * u + lane;
-      if (w < lim) d32[w] = v[u];
-    }
-  }
-  if (lane < h) o.put(pos + lane, src[lane]);
-  for (u32 i = h + 4 * lim + lane; i < n; i += 64) o.put(pos + i, src[i]);
-}
-
+// byte copy global -> Out (wave-parallel); bytes at or past o.cap are dropped like Out::put does.
 // Large copies (raw blocks, raw literals): 16-B aligned stores, each from the one or two
 // aligned 16-B source chunks holding its bytes (a chunk holding a needed byte never crosses a
-// page), funnel-shifted by the source's offset; CP16_U stores per lane in flight.
-#ifndef ZH_CP16_U
-#define ZH_CP16_U 4
-#endif
+// page), funnel-shifted by the source's offset; U stores per lane in flight.
 __device__ __forceinline__ uint4 funnel16(uint4 a, uint4 b, u32 sa) {
   // bytes [sa, sa + 16) of the 32-byte a:b (sa wave-uniform; selects, no indexed array)
   u32 const q = sa >> 2, r = sa & 3u;
@@ -912,7 +844,7 @@ __device__ __forceinline__ void copy_bytes16(const Out &o, u32 pos, const u8 *sr
   u32 const sa = (u32)((uintptr_t)s & 15u);
   const uint4 *const s16 = (const uint4 *)(s - sa);
   uint4 *const dd = (uint4 *)(d0 + hb);
-  constexpr u32 U = ZH_CP16_U;
+  constexpr u32 U = 4;
   for (u32 c0 = 0; c0 < lim; c0 += 64 * U) {
     uint4 a[U], b2[U];
 #pragma unroll
@@ -932,13 +864,10 @@ __device__ __forceinline__ void copy_bytes16(const Out &o, u32 pos, const u8 *sr
   if (lane < hb) o.put(pos + lane, src[lane]);
   for (u32 i = hb + 16 * lim + lane; i < n; i += 64) o.put(pos + i, src[i]);
 }
-#ifndef ZH_COPY16
-#define ZH_COPY16 1
-#endif
-__device__ __forceinline__ void copy_bytes(const Out &o, u32 pos, const u8 *src, u32 n) {
-  if (ZH_COPY16) copy_bytes16(o, pos, src, n);
-  else copy_bytes4(o, pos, src, n);
-}
+// (tried dword stores, two dword loads each: random data's entropy stage 1.34 ms against 0.53 with
+// K1's histogram, DESIGN.md "entropy stage".  The extra call level stays: folding it into the
+// callers changes their register allocation)
+__device__ __forceinline__ void copy_bytes(const Out &o, u32 pos, const u8 *src, u32 n) { copy_bytes16(o, pos, src, n); }
 
 }  // namespace
 
@@ -1125,9 +1054,7 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
       if (i00 < nl) load2(i00, q);
       for (u32 i0 = i00; i0 < nl; i0 += 4096) {
         uint4 qn[2];
-#if ZH_HIST_PF
-        if (i0 + 4096 < nl) load2(i0 + 4096, qn);
-#endif
+        if (i0 + 4096 < nl) load2(i0 + 4096, qn);  // next step's loads before this step's atomics
 #pragma unroll
         for (u32 g = 0; g < 2; g++) {
           u32 const i = i0 + 16 * g;
@@ -1137,9 +1064,6 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
           for (u32 k = 0; k < 16; k++)
             if (k < cnt) atomicAdd(&hist0[(w[k >> 2] >> (8 * (k & 3))) & 255u], 1u);
         }
-#if !ZH_HIST_PF
-        if (i0 + 4096 < nl) load2(i0 + 4096, qn);
-#endif
         q[0] = qn[0];
         q[1] = qn[1];
       }
@@ -1336,7 +1260,6 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
       bool open = false;
       RecRing ring;  // records loaded RING_DEPTH chunks ahead (a chunk writes only indices < its end)
       ring.init(seq, nseq_raw, lane);
-#if ZH_K2_PAIR
       // Two chunks per iteration: the second chunk's run analysis, its permutes and both
       // chunks' code lookups depend only on records (not on the first chunk's results), so
       // their LDS round trips overlap; the open run and the repcodes pass on in order.
@@ -1346,6 +1269,8 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
       struct Chunk { u32 ll, off, runMl, incl, cum; u64 hm; bool head, fast; };
       auto analyse = [&](u64 rec, u32 i, u32 pc0, u32 po0, Chunk &c) {
         bool const valid = i < nseq_raw;
+        // K1 record: the walk's literals before the match | length | catch-up | offset; the
+        // catch-up e moves e bytes of the literal run into the match (zh_lz.hip)
         u32 const cum = (u32)(rec & 0x1FFFFu), ce = (u32)((rec >> 24) & 0xFFFu);
         u32 const ml = (u32)((rec >> 17) & 0x7Fu) + ce, off = (u32)((rec >> 36) & 0x1FFFFu);
         u32 pc = wave_shr1(cum), po = wave_shr1(off);
@@ -1360,6 +1285,8 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
           c.runMl = mlv;
           c.incl = 0;  // (advance reads it only before the first head: lane 0 is one)
         } else {
+          // run sums of ml: inclusive DPP scan, each head reads the scan at its run's last lane in
+          // this chunk (one ds_bpermute); lanes before the first head extend the open run
           u32 const incl = wave_scan_incl(mlv);
           u64 const headBitsAfter = hm & ~((lane == 63) ? ~0ull : ((2ull << lane) - 1));
           u32 const runEnd = headBitsAfter ? (u32)__builtin_ctzll(headBitsAfter) - 1u : 63u;
@@ -1369,7 +1296,9 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
         }
         c.ll = ll; c.off = off; c.cum = cum; c.hm = hm; c.head = head;
       };
-      // the chunk's runs to lanes hp + rank (ds_permute, as in the single-chunk step below)
+      // the chunk's runs to lanes hp + rank: the sequences of a chunk are the run left open before
+      // (if any), then the chunk's runs but its last (which stays open); heads go to lanes
+      // hp + rank, the other lanes to the lanes above (a bijection, as ds_permute needs)
       auto gather = [&](const Chunk &c, u32 hp, u32 &sll, u32 &sml, u32 &soff) {
         if (c.fast) {  // lane + hp (lane 0 takes the open run in advance)
           sll = hp ? wave_shr1(c.ll) : c.ll;
@@ -1424,56 +1353,6 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
         if (mA) sequences_c(mA, aL, aM, aO, aLc, aMc);
         if (mB) sequences_c(mB, bL, bM, bO, bLc, bMc);
       }
-#else
-      for (u32 base = 0; base < nseq_raw; base += 64) {
-        u32 const i = base + lane;
-        bool const valid = i < nseq_raw;
-        u64 const rec = ring.next(seq, nseq_raw, i);
-        // K1 record: the walk's literals before the match | length | catch-up | offset; the
-        // catch-up e moves e bytes of the literal run into the match (zh_lz.hip)
-        u32 const cum = (u32)(rec & 0x1FFFFu), ce = (u32)((rec >> 24) & 0xFFFu);
-        u32 const ml = (u32)((rec >> 17) & 0x7Fu) + ce, off = (u32)((rec >> 36) & 0x1FFFFu);
-        u32 pc = wave_shr1(cum), po = wave_shr1(off);
-        if (lane == 0) { pc = carryCum; po = carryOff; }
-        u32 const ll = cum - pc - ce;
-        bool const flag = valid && i > 0 && ll == 0 && off == po;
-        bool const head = valid && !flag;
-        u64 const hm = __ballot(head);
-        // run sums of ml: inclusive DPP scan, each head reads the scan at its run's last lane in
-        // this chunk (one ds_bpermute); lanes before the first head extend the open run
-        u32 const mlv = valid ? ml : 0u;
-        u32 const incl = wave_scan_incl(mlv);
-        u64 const headBitsAfter = hm & ~((lane == 63) ? ~0ull : ((2ull << lane) - 1));
-        u32 const runEnd = headBitsAfter ? (u32)__builtin_ctzll(headBitsAfter) - 1u : 63u;
-        u32 const inclEnd = (u32)__builtin_amdgcn_ds_bpermute((int)(runEnd << 2), (int)incl);
-        u32 const runMl = inclEnd - (incl - mlv);  // (heads: the run's ml within this chunk)
-        u32 const hcount = (u32)__popcll(hm);
-        u32 const firstH = hm ? (u32)__builtin_ctzll(hm) : 64u;
-        openMl += firstH ? lane_value(incl, firstH - 1u) : 0u;
-        if (hcount) {
-          // sequences of this step: the run left open before (if any), then this chunk's runs
-          // but its last (which stays open); heads go to lanes hp + rank, the other lanes to
-          // the lanes above (a bijection, as ds_permute needs)
-          u32 const hp = open ? 1u : 0u;
-          u32 const rank = (u32)__popcll(hm & below);
-          u32 const dest = head ? rank + hp : (hcount + hp + (lane - rank)) & 63u;
-          u32 sll = (u32)__builtin_amdgcn_ds_permute((int)(dest << 2), (int)ll);
-          u32 sml = (u32)__builtin_amdgcn_ds_permute((int)(dest << 2), (int)runMl);
-          u32 soff = (u32)__builtin_amdgcn_ds_permute((int)(dest << 2), (int)off);
-          if (hp && lane == 0) { sll = openLL; sml = openMl; soff = openOff; }
-          int const lastH = 63 - __builtin_clzll(hm);
-          openLL = lane_value(ll, (u32)lastH);
-          openOff = lane_value(off, (u32)lastH);
-          openMl = lane_value(runMl, (u32)lastH);
-          open = true;
-          u32 const m = hp + hcount - 1;
-          if (m) sequences(m, sll, sml, soff);
-        }
-        u32 const lastLane = min(63u, nseq_raw - 1 - base);
-        carryCum = lane_value(cum, lastLane);
-        carryOff = lane_value(off, lastLane);
-      }
-#endif
       if (open) sequences(1, openLL, openMl, openOff);
       wave_sync();
     }
@@ -1657,13 +1536,8 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
 // chain's.  The kernel's time is a block's longest segment, not its whole chain.
 constexpr u32 K3_SEGS = ZH_K3_SEGS;  // 3 x 21 x ZH_K3_W lanes
 constexpr u32 K3_W = ZH_K3_W;        // waves per block
-#ifndef ZH_K3_OCC
-#define ZH_K3_OCC 8  // minimum waves per SIMD the chain kernel is compiled for (8: <= 64 VGPRs)
-#endif
-#ifndef ZH_K3_WARM
-#define ZH_K3_WARM 128
-#endif
-constexpr u32 K3_WARM = ZH_K3_WARM;  // warm-up steps before a segment's first step (64 -> 128: entropy
+constexpr u32 K3_OCC = 8;  // minimum waves per SIMD the chain kernel is compiled for (8: <= 64 VGPRs)
+constexpr u32 K3_WARM = 128;         // warm-up steps before a segment's first step (64 -> 128: entropy
                                      // 3.05 -> 3.02 ms at 16,384 blocks, 0.775 -> 0.75 at 2,048)
 constexpr u32 K3_WAVES = K3_W == 1 ? 4 : K3_W;  // waves per workgroup (the CU holds at most 16 workgroups)
 constexpr u32 K3_BPW = K3_WAVES / K3_W;          // blocks per workgroup
@@ -1830,7 +1704,7 @@ __device__ __forceinline__ void k3_chain(ZhWorkspace ws, u32 bb, u8 *smem, u32 l
 #endif
 }
 
-extern "C" __global__ __launch_bounds__(64 * K3_WAVES) __attribute__((amdgpu_waves_per_eu(ZH_K3_OCC, 8))) void zh_fse_chain_kernel(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws) {
+extern "C" __global__ __launch_bounds__(64 * K3_WAVES) __attribute__((amdgpu_waves_per_eu(K3_OCC, 8))) void zh_fse_chain_kernel(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws) {
   extern __shared__ __attribute__((aligned(16))) u8 smem_all[];
   u32 const bw = threadIdx.x / (64 * K3_W), lane = threadIdx.x % (64 * K3_W);  // block of the workgroup, lane in it
   u32 const bb = blockIdx.x * K3_BPW + bw;
@@ -1847,11 +1721,8 @@ extern "C" __global__ __launch_bounds__(64 * K3_WAVES) __attribute__((amdgpu_wav
 // most 16 workgroups.
 constexpr u32 KP_SW = 0, KP_DNB = 4 * SW_WORDS, KP_LDS = (KP_DNB + 4 * 128 + 15) & ~15u;
 constexpr u32 K4_WAVES = 4;
-#ifndef ZH_K4_PF
-#define ZH_K4_PF 1
-#endif
-constexpr u32 K4_PF = ZH_K4_PF;  // chunks in flight (3 measured slower: entropy 3.05 -> 3.20 ms at 16,384
-                                 // blocks, no change at 2,048)
+constexpr u32 K4_PF = 1;  // chunks in flight (tried 3: slower, entropy 3.05 -> 3.20 ms at 16,384 blocks,
+                          // no change at 2,048)
 
 // K4 of block b (one wave; the caller checked that the block needs it); smem = KP_LDS bytes
 __device__ __forceinline__ void k4_pack(const ZhBlockDesc &d, ZhWorkspace ws, u32 b, u8 *smem, u32 lane, u64 *__restrict__ item_size,
@@ -1958,10 +1829,7 @@ void entropy_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32
   // 3.04 -> 3.22 ms at 16,384 blocks, 0.75 -> 0.80 ms at 2,048)
   u32 const g3 = (nblocks + K3_BPW - 1) / K3_BPW, g4 = (nblocks + K4_WAVES - 1) / K4_WAVES;
   hipLaunchKernelGGL(zh_fse_chain_kernel, dim3(g3), dim3(64 * K3_WAVES), K3_LDS, stream, d_descs, nblocks, ws);
-#ifndef ZH_K4_LDS_PAD
-#define ZH_K4_LDS_PAD 0  // (occupancy experiments: LDS padding per K4 workgroup)
-#endif
-  hipLaunchKernelGGL(zh_seq_pack_kernel, dim3(g4), dim3(64 * K4_WAVES), K4_WAVES * KP_LDS + ZH_K4_LDS_PAD, stream, d_descs, nblocks, ws, d_item_size,
+  hipLaunchKernelGGL(zh_seq_pack_kernel, dim3(g4), dim3(64 * K4_WAVES), K4_WAVES * KP_LDS, stream, d_descs, nblocks, ws, d_item_size,
                      d_item_status, d_blk_size);
 }
 }  // namespace zh

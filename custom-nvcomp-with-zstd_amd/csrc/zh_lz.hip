@@ -22,7 +22,7 @@
 //   waves 14, 15  inserters (s_setprio 2): one wave per hash table inserts window k+1's tiles
 //                 of ZH_TILE positions, two per LDS round trip (program order = LDS order
 //                 within a wave; lanes of one store that hit the same slot are checked by a
-//                 read-back); candidates stay in registers and are dumped after barrier X.
+//                 read-back); candidates stay in registers and are dumped before the next step's barrier.
 //   waves 1..13   window k's match lengths, lanes = positions: each candidate's common prefix
 //                 from its first 8 bytes, and along same-offset chains (the candidate of p+1
 //                 is the candidate of p plus one) lcp(p) = 1 + lcp(p+1): a ballot of the chain
@@ -58,8 +58,9 @@ extern "C" u32 zh_fixups_host() {
 // Diagnostic build only (-DZH_TIMELINE, tools/timeline.py): per K1 wave and step phase, the
 // s_memtime cycles summed over every step of every block (VERDICT r5 item 2's executed per-phase
 // breakdown of the window pipeline).  Worker waves: 0 P wait, 1 lengths, 2 parse / records,
-// 3 X wait, 4 span tops + literals; inserter waves: 0 P wait, 1 insertion of the next window (the X
-// barrier taken between its tiles included), 3 barriers left after it, 4 candidate dump; [5] steps.
+// 3 and 4 empty (the second barrier's wait and the work after it, before the step had one barrier);
+// inserter waves: 0 P wait, 1 insertion of the next window, 2 literals, 3 empty, 4 candidate dump;
+// [5] steps.
 #ifdef ZH_TIMELINE
 __device__ unsigned long long g_tl[16 * 8];
 extern "C" __global__ void zh_read_timeline(unsigned long long *out) {
@@ -85,9 +86,6 @@ extern "C" int zh_timeline_host(unsigned long long *out128) {
 #endif
 namespace {
 
-#ifndef ZH_K1_PMAX
-#define ZH_K1_PMAX 1  // Jacobi entries from the prefix max of exits (K1 11.53 -> 11.50 ms)
-#endif
 constexpr u32 K1_THREADS = 1024;
 constexpr u32 K1_REDO = ~0u;      // lz_block: parse this block again without the probe
 constexpr u32 NROUND = ZH_WINDOW / 64;      // 64-position length rounds per window
@@ -137,21 +135,17 @@ constexpr u32 OFF_MISC = OFF_XQ + 2 * XQ_CAP * NWW;  // [2 par + 0] matches, [2 
 constexpr u32 OFF_LB = OFF_MISC + 4 * 16;            // window k - 2's literal prefix counts per walk
                                                      // segment (+ the window's total), for the literal phase
 constexpr u32 LB_WORDS = NSEG + 4;
-// One barrier per window step (ZH_ONE_BARRIER): the take bits at the worker
-// waves' span tops (lazy rule: they need the next span's first info) are decided by wave 0 at the
-// start of the window's parse in the next step (and by every wave in the probe step), and the
-// inserters dump the next window's candidates once wave 0 has read the previous window's match info
-// (an LDS flag, MISC_PF) -- so nothing needs barrier X.  Measured K1 10.12 -> 9.70 ms at level 3,
-// 7.52 -> 7.21 ms at level 1 (profiles/r06k_one_barrier_ab.json; the first version, every wave
-// deciding its own top from an extra info, was slower: 10.50 ms)
-#ifndef ZH_ONE_BARRIER
-#define ZH_ONE_BARRIER 1
-#endif
+// One barrier (P) per window step: the take bits at the worker waves' span tops (lazy rule: they
+// need the next span's first info) are decided by wave 0 at the start of the window's parse in the
+// next step (and by every wave in the probe step), and the inserters dump the next window's
+// candidates once wave 0 has read the previous window's match info (an LDS flag, MISC_PF).  Tried
+// a second barrier X after the lengths, each wave deciding its own top after it: K1 10.12 against
+// 9.70 ms at level 3, 7.52 against 7.21 ms at level 1 (profiles/r06k_one_barrier_ab.json; every
+// wave deciding its own top from an extra info, without X, was slower too: 10.50 ms)
 constexpr u32 K1_LDS = OFF_LB + 4 * LB_WORDS * LB_BUFS;
 constexpr u32 ML_LO = 11, ML_LEN = 22, ML_OFF = 29, ML_CUM = 45;  // match-list entry: start [0, 11) | ...
 constexpr u32 MISC_WNM = 0;   // misc[par]: matches of the window of that parity (its match list's length)
-constexpr u32 MISC_ARR = 12;  // misc[12]: worker-wave barrier arrivals (cumulative)
-constexpr u32 MISC_PF = 12;   // (ZH_ONE_BARRIER, no arrivals) misc[12]: k + 1 once wave 0 has read window k - 1's match info
+constexpr u32 MISC_PF = 12;   // misc[12]: k + 1 once wave 0 has read window k - 1's match info
 constexpr u32 MISC_NM = 4;    // misc[4 + (j & 3)]: matches the parse took in window j (miss skip)
 constexpr u32 MISC_ANY = 13;  // misc[13]: block_any's flag (0 between calls)
 constexpr u32 MISC_SCAN = 2;  // misc[2]: the repeat scan's count
@@ -176,31 +170,6 @@ __device__ __forceinline__ u32 ffbl_raw(u32 x) {
 // the symbol's link-time address).  (Address 0 is the LDS null pointer to the compiler.)
 constexpr u32 K1_DYN = 16;
 __device__ __forceinline__ u8 *k1_lds() { return (u8 *)(__attribute__((address_space(3))) u8 *)(uintptr_t)K1_DYN; }
-
-// Perturbation builds only (-DZH_PAD_A/I/W=N, tools/variants.sh): N dependent VALU added to a
-// phase, to see which phase's instructions set K1's time.  Never in the product build.
-template <int N>
-__device__ __forceinline__ void vpad(u32 x) {
-  if constexpr (N > 0) {
-#pragma unroll
-    for (int i = 0; i < N; i++) __asm__ volatile("v_add_u32 %0, %0, %0" : "+v"(x));
-  }
-}
-#ifndef ZH_PAD_A
-#define ZH_PAD_A 0
-#endif
-#ifndef ZH_PAD_I
-#define ZH_PAD_I 0
-#endif
-#ifndef ZH_PAD_W
-#define ZH_PAD_W 0
-#endif
-#ifndef ZH_PAD_C
-#define ZH_PAD_C 0
-#endif
-#ifndef ZH_PAD_L
-#define ZH_PAD_L 0
-#endif
 
 // K1's workgroup barrier: LDS ordering only.  The waves exchange data through LDS alone; their
 // global writes (records, literals, the next block's prefetch loads in flight) need no ordering
@@ -323,8 +292,8 @@ __device__ __forceinline__ void insert_repair(u16 *T, u32 tb0, u32 lane, const u
 // order; -DZH_INS_CHECK builds a read-back of every lane's slot and a repair path
 // (insert_repair) that make the tables independent of it (measured: no repair ever taken;
 // K1 11.16 ms without the read-back vs 11.27 with it, profiles/r05i_k1_perturbation.json).
-// BT tiles are issued per LDS round trip together with the next batch's input dwords and the
-// workers' arrival counter.  Candidates (position + 1, 0 = none) go to creg as u16 pairs.
+// BT tiles are issued per LDS round trip together with the next batch's input dwords.
+// Candidates (position + 1, 0 = none) go to creg as u16 pairs.
 // A lane's positions are 4-aligned apart (tiles and rows are multiples of 64), so its byte
 // shift is lane & 3 and its dwords sit at one base + immediate offsets; positions past lim read
 // bytes past the block (inside the staging area's pad and the tables: never inserted).
@@ -334,9 +303,9 @@ __device__ __forceinline__ void insert_repair(u16 *T, u32 tb0, u32 lane, const u
 // first ZH_MIN_MATCH_LONG (long table) / ZH_MIN_MATCH_SHORT (short) bytes -- the oracle's "a match
 // among the searched tiles" -- and returns whether the window's search resumes; if not, the rest
 // of the window is neither looked up nor inserted and its candidates are never dumped.
-template <bool LONG, typename Hook, typename Check>
-__device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, u32 lim, u32 lane, u32 (&creg)[NCR], const u32 *arrivals,
-                                              Hook &&between_tiles, Check &&on_check, bool skip, u32 pmin) {
+template <bool LONG, typename Check>
+__device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, u32 lim, u32 lane, u32 (&creg)[NCR], const u32 *flag,
+                                              Check &&on_check, bool skip, u32 pmin) {
   // positions below pmin are already in T (a dictionary's precomputed tables): treated like
   // positions past lim (the junk slot, no candidate)
   constexpr u32 JUNK = LONG ? HL_SIZE : HS_SIZE;
@@ -391,8 +360,9 @@ __device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, 
       for (u32 k = 0; k < TPL; k++) r[b][k] = T[h[b][k]];
 #endif
     if (t0 + BT < NT) load_in(tb0 + BT * ZH_TILE);
-    vpad<ZH_PAD_I>(h[0][0]);
-    u32 const arr = __atomic_load_n(arrivals, __ATOMIC_RELAXED);
+    // (a leftover of the two-barrier protocol, which polled the workers' arrival counter here:
+    // taking this load out changes the inserters' generated code, so it stays for now)
+    (void)__atomic_load_n(flag, __ATOMIC_RELAXED);
 #ifdef ZH_INS_CHECK
     bool lost = false;
 #pragma unroll
@@ -430,12 +400,8 @@ __device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, 
           u32 const dx = (lo ^ clo) | ((hi ^ chi) & (LONG ? ~0u : 0xFFu));
           v |= c != 0 && dx == 0;
         }
-      if (!on_check(__ballot(v) != 0)) {
-        between_tiles(arr);
-        break;
-      }
+      if (!on_check(__ballot(v) != 0)) break;
     }
-    between_tiles(arr);
   }
   __asm__ volatile("" ::: "memory");
 }
@@ -489,9 +455,6 @@ __device__ __forceinline__ bool skip_window(const u32 *misc, u32 k, u32 kskip0) 
 // (decided while window k was inserted, in step k - 1; read by the workers after barrier P of
 // step k -- the next write to that parity is window k + 2's, in step k + 1).
 __device__ __forceinline__ bool skip_window_eff(const u32 *misc, u32 k, u32 kskip0) {
-#ifdef ZH_NO_RESUME
-  return skip_window(misc, k, kskip0);  // (A/B variant without the resume; not the oracle's rule)
-#endif
   return skip_window(misc, k, kskip0) && (u32)__builtin_amdgcn_readfirstlane(__atomic_load_n(&misc[MISC_RESF + (k & 1)], __ATOMIC_RELAXED)) == 0;
 }
 // The two inserter waves' resume checks of miss-skip window j combined (mode 0: each table's wave
@@ -528,7 +491,7 @@ __device__ __forceinline__ bool probe_dead(const u32 *misc, u32 k, u32 kprobe) {
   return (u32)__builtin_amdgcn_readfirstlane(m) == 0;
 }
 static_assert(ZH_PROBE_WINDOWS >= 1 && ZH_PROBE_WINDOWS <= 3, "probe windows fit the match-count ring");
-// Span tops of a window's worker waves (ZH_ONE_BARRIER, modes 0-1): the last position 64 hi - 1 of
+// Span tops of a window's worker waves (modes 0-1): the last position 64 hi - 1 of
 // a span whose next position belongs to another wave -- hi = r_hi of waves 1..NWW-2, or 1..RS-1 in
 // a miss-skip window -- takes its match under the lazy rule only with the next position's info,
 // which its own wave never sees.  Lane L (< 32) decides the top at hi = L + 1 from the window's
@@ -550,9 +513,9 @@ __device__ __forceinline__ bool span_top_dec(const u32 *ci, u32 wn, bool skip, u
 }
 // The one-window probe from the take masks: before any match the parse visits every position,
 // so it takes a match in the probe window exactly when the window has a take bit at or after
-// its first parsed position e0.  Window k - 1's masks (and their span-top bits, set after
-// barrier X of step k - 1) are final at barrier P of step k = kprobe - 1, so every wave --
-// inserters too -- tests them right after that P and leaves the window loop together.
+// its first parsed position e0.  Window k - 1's masks are final at barrier P of step k =
+// kprobe - 1 (their span-top bits are decided here), so every wave -- inserters too -- tests them
+// right after that P and leaves the window loop together.
 __device__ __forceinline__ bool probe_dead_tm(u32 k, u32 kprobe, u32 e0, bool lazy = false, u32 wnp = 0) {
   if (ZH_PROBE_WINDOWS != 1 || k + 1 != kprobe) return false;
   u8 *const smem = k1_lds();
@@ -561,7 +524,7 @@ __device__ __forceinline__ bool probe_dead_tm(u32 k, u32 kprobe, u32 e0, bool la
   const u64 *const tmP = (const u64 *)(smem + OFF_HM) + ((k & 1u) ^ 1u) * NROUND;
   u32 const r = lane & (NROUND - 1);
   u64 m = tmP[r];
-  if (ZH_ONE_BARRIER && lazy) {
+  if (lazy) {
     // (the span tops of the probe window, never a miss-skip window: decided here by every wave)
     const u32 *const ciP = (const u32 *)(smem + OFF_CI) + ((k & 1u) ^ 1u) * CI_WORDS;
     m |= span_top_dec(ciP, wnp, false, r, lane < NROUND) ? 1ull << 63 : 0ull;
@@ -639,11 +602,7 @@ constexpr u32 MAX_RW = 3;   // rounds per worker wave
 // (`profiles/k1_length_phase_diet_ab.json`, K1 9.02 ms): a round moved onto SIMD 2 or 3 9.38 ms,
 // off them onto SIMD 1 or 0 9.13 / 9.19 ms.
 __device__ __forceinline__ u32 rounds_of(u32 w) {
-#ifdef ZH_RTAB
-  return (u32)(((unsigned long long)(ZH_RTAB) >> (2 * w)) & 3u);
-#else
   return (u32)((ROUND_TAB >> (2 * w)) & 3u);
-#endif
 }
 
 // Pass B: extend queue entries [0, k) (k <= 64) of xq, one per lane; the extension (<= 64)
@@ -677,7 +636,7 @@ __device__ __forceinline__ u32 pk_sub16(u32 a, u32 b) {
 // match if it gets there (take_rule on the next positions' info: DPP within the round, the
 // round above by carry; la1 = the position above the span when it is the window's
 // top one) -> the rounds' take masks tm.  At the top of a span that is not the window's top the next positions
-// belong to another wave: those take bits stay clear until the wave decides them after barrier X.
+// belong to another wave: those take bits stay clear until wave 0 decides them (span_top_dec).
 template <u32 MODE, u32 NR = MAX_RW>
 __device__ __forceinline__ void span_lengths(const u32 *in32, u32 *ci, u64 *tm, u16 *xq, u32 r_lo_, u32 r_hi_, u32 wsb, u32 we, u32 n, u32 lim,
                                              u32 lane, bool top, u32 la1) {
@@ -749,7 +708,6 @@ __device__ __forceinline__ void span_lengths(const u32 *in32, u32 *ci, u64 *tm, 
     diff(t >> 16, Sw[k], xs, ys);
     if constexpr (TWO) diff(t, Lw[k], xl, yl);
     u32 const pS = min(ffbl_raw(xs), min(ffbl_raw(ys), 32u) + 32u) >> 3;
-    vpad<ZH_PAD_A>(pS);
     // p + 1's candidates (lane 63: the round above's lane 0) minus p's, both halves at once: a
     // half of 1 continues p's candidate
     u32 const cwn = (u32)__builtin_amdgcn_update_dpp((int)ccw, (int)cw, 0x130, 0xf, 0xf, false);  // wave_shl:1
@@ -820,7 +778,6 @@ __device__ __forceinline__ void span_lengths(const u32 *in32, u32 *ci, u64 *tm, 
     auto first_run = [](u64 f) { return ~f ? 64u - (u32)__builtin_clzll(~f) : 0u; };
     u32 const lL = min((u32)ZH_MAX_MATCH, lLr[k] + (lane >= first_run(mFL[k]) ? clL - 6u : 0u));
     u32 const lS = min((u32)ZH_MAX_MATCH, lSr[k] + (lane >= first_run(mFS[k]) ? clS - 7u : 0u));
-    vpad<ZH_PAD_C>(lS);
     clL = lane_value(lL, 0);
     clS = lane_value(lS, 0);
     u32 const capj = min((u32)ZH_MAX_MATCH, n - min(p, n));
@@ -947,11 +904,7 @@ static_assert(L1_S != 2 || (((ROUND_TAB1 >> 2) & 3) + ((ROUND_TAB1 >> 4) & 3) + 
 template <u32 MODE>
 __device__ __forceinline__ u32 rounds_of_mode(u32 w) {
   if constexpr (MODE == 2 && L1_S == 2) {
-#ifdef ZH_RTAB1
-    return (u32)(((unsigned long long)(ZH_RTAB1) >> (2 * w)) & 3u);
-#else
     return (u32)((ROUND_TAB1 >> (2 * w)) & 3u);
-#endif
   } else if constexpr (MODE == 2 && L1_S == 4) {
     return w >= 1 && w <= 8 ? 1u : 0u;
   } else {
@@ -1010,7 +963,6 @@ template <bool REWALK, typename LenQ>
 __device__ __forceinline__ void seg_walk(LenQ &&lenq, u32 tmk, u32 S, u32 SE, u32 p, bool act0, u32 &LM, u32 &MM, u32 &ex) {
   // (the first walk has no old trajectory: REWALK = false drops the merge test from the step)
   u32 const old = (REWALK && act0) ? (LM | MM) : 0u;
-  vpad<ZH_PAD_W>(p);
   u32 nl = 0, nm = 0;
   bool act = act0 && p < SE, merged = false;
   u32 mpos = 0;
@@ -1070,12 +1022,9 @@ __device__ __forceinline__ void seg_walk(LenQ &&lenq, u32 tmk, u32 S, u32 SE, u3
 // Inserter wave main loop.  Step k of the workers (the lengths of window k, the parse and
 // records of window k - 1, then its literals) opens with barrier P once window k's candidates
 // are dumped into cinfo buffer k & 1, and the inserters then build window k + 1's candidates in
-// registers.  They take the step's barrier X only once
-// all 14 worker waves have arrived there (an LDS arrival counter), between two tiles, so the
-// insertion spreads over the whole step.
-constexpr u32 WIN_BARRIERS = 1;  // X
-// The long table's wave in modes 1, 2 (the short table only): no insertion, only the step's two
-// barriers (P, X) and the probe exit, so the workgroup's barrier sequence stays the same.
+// registers.
+// The long table's wave in modes 1, 2 (the short table only): no insertion, only the step's
+// barrier P and the probe exit, so the workgroup's barrier sequence stays the same.
 // Returns whether the loop ended at the incompressibility probe.
 // Literal bytes of the window at staged position wsj: literal rounds [r0, r0 + nr) of LIT_RP
 // positions, a lane = one dword of the window (window starts are multiples of ZH_WINDOW in staged
@@ -1185,7 +1134,6 @@ __device__ __forceinline__ bool idle_inserter_loop(u32 *misc_, u32 n, u32 wstart
     u32 const wsb = wstart + k * ZH_WINDOW;
     if (probe_dead_tm(k, kprobe, e0p, lazy, min(wsb, n) - (wsb - ZH_WINDOW))) return true;
     lj.step(k, lane);
-    if (!ZH_ONE_BARRIER) k1_barrier();  // X
   }
   return false;
 }
@@ -1194,26 +1142,23 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
                                               u32 pmin, u32 span_s, u32 span_e, u32 kskip0, u32 kprobe, u32 e0p, LJ &lj, bool lazy) {
   u32 creg[NCR];
   if (span_s < span_e) insert_span<LONG>(in32, T, span_s, span_e, lane);
-  // (the first window: its own instantiation, with pmin and no barriers to take)
-  insert_window<LONG>(in32, T, wstart, lim, lane, creg, &misc_[MISC_ARR], [](u32) {}, NoCheck{}, false, pmin);
+  // (the first window: its own instantiation, with pmin and no resume check)
+  insert_window<LONG>(in32, T, wstart, lim, lane, creg, &misc_[MISC_PF], NoCheck{}, false, pmin);
   u32 cwe = lookahead<LONG>(in32, T, min(wstart + (u32)ZH_WINDOW, n), lim, lane);
   bool skipc = false;  // the window whose candidates creg holds is a miss-skip window (not resumed)
 #ifdef ZH_STAMPS
   u32 st_ins = 0;
 #endif
   u32 const nwin = (n - wstart + ZH_WINDOW - 1) / ZH_WINDOW;
-  u32 passed = 0;  // X barriers taken so far
   TL_DECL;
   for (u32 k = 0; k < nwin + STEPS_EXTRA; k++) {
     if (probe_dead(misc_, k, kprobe)) return true;
     u32 const wsb = wstart + k * ZH_WINDOW;
     if (k < nwin) {
-      if (ZH_ONE_BARRIER) {
-        // buffer k & 1 held window k - 2's match info, which wave 0 read in step k - 1
-        // (bounded: wave 0 sets the flag every step; the bound only keeps a bug from hanging the GPU)
-        for (u32 it = 0; it < (1u << 22) && (u32)__builtin_amdgcn_readfirstlane(__atomic_load_n(&misc_[MISC_PF], __ATOMIC_RELAXED)) < k; it++)
-          __builtin_amdgcn_s_sleep(1);
-      }
+      // buffer k & 1 held window k - 2's match info, which wave 0 read in step k - 1
+      // (bounded: wave 0 sets the flag every step; the bound only keeps a bug from hanging the GPU)
+      for (u32 it = 0; it < (1u << 22) && (u32)__builtin_amdgcn_readfirstlane(__atomic_load_n(&misc_[MISC_PF], __ATOMIC_RELAXED)) < k; it++)
+        __builtin_amdgcn_s_sleep(1);
       if (skipc) dump_window<LONG, ZH_SKIP_TILES>(ci8 + (k & 1u) * 4 * CI_WORDS, lane, creg, cwe);
       else dump_window<LONG, TILES>(ci8 + (k & 1u) * 4 * CI_WORDS, lane, creg, cwe);
     }
@@ -1222,16 +1167,6 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
     TL_MARK(0);
     TL_STEP();
     if (probe_dead_tm(k, kprobe, e0p, lazy, min(wsb, n) - (wsb - ZH_WINDOW))) return true;
-    u32 const done = passed + WIN_BARRIERS;
-    // arr: the arrival counter as read with the last tile's read-back; a barrier taken
-    // here means the counter is re-read for the next one
-    auto take_ready = [&](u32 arr) {
-      while (!ZH_ONE_BARRIER && passed < done && arr >= NWW * (passed + 1)) {
-        k1_barrier();
-        passed++;
-        arr = __atomic_load_n(&misc_[MISC_ARR], __ATOMIC_RELAXED);
-      }
-    };
 #ifdef ZH_STAMPS
     u64 const ti0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1239,16 +1174,11 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
     // window k + 1: the parse of window k - 2 ended in step k - 1 (before this step's P)
     skipc = skip_window(misc_, k + 1, kskip0);
     if (k + 1 < nwin) {
-#ifdef ZH_NO_RESUME
-      bool const resumed = false;
-      insert_window<LONG>(in32, T, nx, lim, lane, creg, &misc_[MISC_ARR], take_ready, [](bool) { return false; }, skipc, 0u);
-#else
       // a miss-skip window's first tiles, then the rest of it if any of them found a match (both
       // inserters' checks combined before either takes a barrier)
       bool resumed = false;
-      insert_window<LONG>(in32, T, nx, lim, lane, creg, &misc_[MISC_ARR], take_ready,
+      insert_window<LONG>(in32, T, nx, lim, lane, creg, &misc_[MISC_PF],
                           [&](bool h) { return resumed = resume_exchange<LONG, TWO>(misc_, k + 1, h, lane); }, skipc, 0u);
-#endif
       if (resumed) skipc = false;
       cwe = lookahead<LONG>(in32, T, min(nx + ZH_WINDOW, n), lim, lane);
     }
@@ -1256,11 +1186,10 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
     st_ins += (u32)(__builtin_amdgcn_s_memtime() - ti0);
 #endif
     TL_MARK(1);
-    // window k - 3's literal bytes (their bits and prefix counts were final at X of step k - 1;
+    // window k - 3's literal bytes (their bits and prefix counts were final at P of step k;
     // the next writes to those buffers come after P of step k + 1)
     lj.step(k, lane);
     TL_MARK(2);
-    while (!ZH_ONE_BARRIER && passed < done) { k1_barrier(); passed++; }
     TL_MARK(3);
   }
   TL_FLUSH(LONG ? 14u : 15u, lane);
@@ -1316,15 +1245,12 @@ __device__ __forceinline__ void prefetch_block(const ZhBlockDesc *__restrict__ b
 }
 
 // Workgroup role of a thread: virtual wave = K1_WAVE_MAP nibble of its hardware wave (the
-// wave-to-SIMD assignment is wave id mod 4).  ZH_K1_PERM 1 puts both inserters (virtual 14,
-// 15) on SIMD 3 with one length wave and four length waves on each other SIMD: mix 13.74 ->
+// wave-to-SIMD assignment is wave id mod 4).  Tried 0xDBA9C876F543E210, both inserters (virtual
+// 14, 15) on SIMD 3 with one length wave and four length waves on each other SIMD: mix 13.74 ->
 // 13.68 ms, but random data (few matches, the inserters are the critical path) 10.15 -> 10.72
-// ms, so the default keeps the identity (inserters on SIMDs 2 and 3).
-#ifndef ZH_K1_PERM
-#define ZH_K1_PERM 0
-#endif
+// ms, so the map is the identity (inserters on SIMDs 2 and 3).
 // nibble p = virtual wave of hardware wave p
-constexpr u64 K1_WAVE_MAP = ZH_K1_PERM ? 0xDBA9C876F543E210ull : 0xFEDCBA9876543210ull;
+constexpr u64 K1_WAVE_MAP = 0xFEDCBA9876543210ull;
 // __syncthreads_or for the K1 workgroup: a flag word (0 between calls) raised by one lane per
 // wave, read after a barrier and cleared between two more.  (The runtime's version computes the
 // flat work-item id, whose entry VGPRs would then stay live -- spilled -- across the
@@ -1361,7 +1287,7 @@ __device__ __forceinline__ bool repeat_scan(const u32 *in32, u32 *E, u32 *hw, u3
   static_assert(K1_THREADS / 64 == ZH_K1_HIST_WAVES && 4 * 256 * ZH_K1_HIST_WAVES <= 2 * 4 * CI_WORDS, "sub-histograms in the cinfo space");
   // the clears below take no barrier first: with one probe window the window loop is left right
   // after barrier P, when no inserter is inside a window (with 2-3, probe_dead fires at a step's
-  // top while an inserter that took X in take_ready may still write TL) -- ADVICE r5
+  // top while an inserter may still be writing the next window into TL) -- ADVICE r5
   static_assert(ZH_PROBE_WINDOWS == 1, "repeat_scan reuses the hash tables without a barrier");
   constexpr u32 NS = 1u << ZH_SCAN_LOG;
   u32 const lim = n > ZH_HASH_READ ? n - ZH_HASH_READ : 0u, lane = tid & 63u, wave = tid >> 6;
@@ -1531,11 +1457,7 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
   u32 const pmin = (use_dt || par_hist) ? pre & ~(ZH_TILE - 1) : 0u;  // the tile holding pre
   u32 const wstart = (use_dt || par_hist) ? (pre & ~(ZH_WINDOW - 1)) : 0u;
   u32 const span_s = use_dt ? pre - ZH_DTAB_MARGIN : 0u, span_e = use_dt ? pmin : 0u;
-#ifdef ZH_NO_SKIP
-  u32 const kskip0 = 1u << 20;
-#else
   u32 const kskip0 = pre / ZH_WINDOW + 3 - wstart / ZH_WINDOW;  // first loop window that may skip
-#endif
   u32 const lim = n > ZH_HASH_READ ? n - ZH_HASH_READ : 0;
   // the probe's step: the oracle checks once the parse of windows [a0, a0 + ZH_PROBE_WINDOWS) is
   // done, when the block has a window past them (windows counted up to lim, as the oracle does)
@@ -1559,7 +1481,7 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
     for (u32 i = tid; i < (HL_SIZE + HS_SIZE + 2 * T_PAD) / 2; i += K1_THREADS) ((u32 *)TL)[i] = 0;  // both tables (adjacent)
   }
   if (tid == 0) {
-    misc[MISC_ARR] = 0;
+    misc[MISC_PF] = 0;
 #pragma unroll
     for (u32 i = 0; i < 4; i++) misc[MISC_XCH + i] = 0;
   }
@@ -1647,9 +1569,8 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
   // Step k (window j at wstart + j * ZH_WINDOW, parity j & 1):
   //   phase A  lengths of window k (waves 1..13) | span-top take decisions and parse of window
   //            k - 1 (wave 0) | catch-up and sequence records of window k - 2 (REC_WAVE)
-  //   (ZH_ONE_BARRIER=0 only: X, then the take decisions at window k's span tops, each wave its own)
   u32 m3 = 0;  // k mod LM_BUFS
-  bool skp_prev = false;  // (ZH_ONE_BARRIER) window k - 1 was a miss-skip window (its span tops)
+  bool skp_prev = false;  // window k - 1 was a miss-skip window (its span tops)
   for (u32 k = 0; k < nwin + STEPS_EXTRA; k++, m3 = m3 + 1 == LM_BUFS ? 0u : m3 + 1) {
     if (probe_dead(misc, k, kprobe)) {
       dead = true;
@@ -1724,7 +1645,7 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
       u32 const wn = wep - wsp;
       u32 const S = SEGP * lane, SE = min(S + SEGP, wn);
       u32 tmk = (u32)(tmP[lane >> 1] >> (32 * (lane & 1)));
-      if constexpr (ZH_ONE_BARRIER && MODE != 2) {
+      if constexpr (MODE != 2) {
         // the worker waves' span tops of window k - 1 (lane L: the top ending round L): a top
         // ends the odd segment 2 hi - 1, at its bit 31
         bool const dt = span_top_dec(ciP, wn, skp_prev, lane, lane < NROUND);
@@ -1741,13 +1662,10 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
       seg_walk<false>(lenq, tmk, S, SE, entry, true, LM, MM, ex);
       // Jacobi rounds: a segment's entry is its predecessor's exit
       for (;;) {
-#if ZH_K1_PMAX
         // the largest exit before the segment (its predecessor's once consistent): a match
-        // covering whole segments passes its end through them in one round
+        // covering whole segments passes its end through them in one round (tried the
+        // predecessor's exit alone: K1 11.53 against 11.50 ms)
         u32 const pe = wave_shr1(wave_scan_max_incl(ex));
-#else
-        u32 const pe = wave_shr1(ex);
-#endif
         u32 const ne = lane == 0 ? e0 : max(pe, e0);
         bool const ch = ne != entry;
 #ifdef ZH_STAMPS
@@ -1793,9 +1711,9 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
       if (lane == 0) { misc[MISC_WNM + (kb ^ 1u)] = nm; misc[MISC_NM + ((k - 1) & 3)] = nm; }
       ZH_STAMP(st_J);
     }
-    // (ZH_ONE_BARRIER) wave 0 is done with window k - 1's match info: the inserters may dump
-    // window k + 1's candidates into that buffer
-    if (ZH_ONE_BARRIER && wave == 0 && lane == 0) __atomic_store_n(&misc[MISC_PF], k + 1, __ATOMIC_RELAXED);
+    // wave 0 is done with window k - 1's match info: the inserters may dump window k + 1's
+    // candidates into that buffer
+    if (wave == 0 && lane == 0) __atomic_store_n(&misc[MISC_PF], k + 1, __ATOMIC_RELAXED);
     if (wave == REC_WAVE && prev2) {
       // ---- catch-up and sequence records of window k - 2, lanes = matches.  A match grows
       // back over the literals down to the end of the match before it; it takes back e bytes of
@@ -1823,43 +1741,22 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
       u32 const lc = (u32)__popc(lmQ[lane]), lincl = wave_scan_incl(lc);
       lbxq[lane] = lincl - lc;
       if (lane == 63) lbxq[NSEG] = lincl;
-      if (ZH_ONE_BARRIER) {  // (this wave keeps the block's totals: no barrier before the others could read them)
-        nlit_tot += lane_value(lincl, 63);
-        nseq_tot += nm;
-      }
+      // (this wave keeps the block's totals: no barrier before the others could read them)
+      nlit_tot += lane_value(lincl, 63);
+      nseq_tot += nm;
     }
     TL_MARK(2);
-    if (!ZH_ONE_BARRIER) {
-      if (lane == 0) atomicAdd(&misc[MISC_ARR], 1u);
-      k1_barrier();  // X: window k's match info and take masks; window k - 1's records and literal bits
-    }
+    // (the diagnostic builds' slots of the former second barrier and of the work after it: empty
+    // now, kept so that the tools' columns stand)
     TL_MARK(3);
     ZH_STAMP(st_X);
-    if (!ZH_ONE_BARRIER && MODE != 2 && have && wave != 0 && wave < (skipk ? RS : NWW - 1)) {
-      // ---- take decision at this wave's span top (the next position was the next wave's):
-      // every wave but the window's top one, its last position
-      u32 const hi = skipk ? wave : r_hi;
-      u32 const i = 64 * hi - 1;
-      if (lane == 0) {
-        u32 const inf = ciK[cidx(i)], inf1 = ciK[cidx(i + 1)];
-        // (a 32-bit atomic on the mask's half: a hoisted 64-bit bit constant spilled)
-        if (i < we - wsb && (inf & 255u) && take_rule<MODE>(inf, inf1)) atomicOr((u32 *)&tmK[i >> 6] + ((i >> 5) & 1u), 1u << (i & 31));
-      }
-    }
-    if (ZH_ONE_BARRIER) {
-      // (the records wave keeps the totals)
-    } else if (prev2) {
-      // (the inserters extract window k - 2's literals in step k + 1)
-      nlit_tot += (u32)__builtin_amdgcn_readfirstlane(lbxq[NSEG]);
-      nseq_tot += __builtin_amdgcn_readfirstlane(misc[MISC_WNM + kb]);
-    }
     ZH_STAMP(st_E);
     TL_MARK(4);
     skp_prev = skipk;
   }
   TL_FLUSH(wave, lane);
   if (!dead) {
-    if (tid_ == (ZH_ONE_BARRIER ? 64u * REC_WAVE : 0u)) { meta[0] = nseq_tot; meta[1] = nlit_tot; meta[2] = 0; }
+    if (tid_ == 64u * REC_WAVE) { meta[0] = nseq_tot; meta[1] = nlit_tot; meta[2] = 0; }
 #ifdef ZH_STAMPS
     if (tid == 0) {
       u32 *dbg = ws.dbg(b);
@@ -1872,11 +1769,7 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
     }
     if ((tid & 63) == 0 && tid < INS_TID) {  // each worker wave's length-phase cycles
       u32 const w = tid >> 6;
-#ifdef ZH_EXP_PWAIT
-      ws.dbg(b)[w < 12 ? 28 + w : 53 + (w - 12)] = st_A;
-#else
       ws.dbg(b)[w < 12 ? 28 + w : 53 + (w - 12)] = st_B;
-#endif
     }
 #endif
     return next_b;
@@ -1886,11 +1779,7 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
   // decides between the literal-only block and redoing the block from its staging without the
   // probe (the oracle's parse simply goes on; lz_blocks calls lz_block again with `redo`).
   u32 *const hw = (u32 *)(smem + OFF_CI);  // the scan's per-wave literal sub-histograms
-#ifdef ZH_NO_SCAN
-  if (false) return K1_REDO;  // (A/B variant: the probe alone decides, as in round 4)
-#else
   if (repeat_scan(in32, (u32 *)TL, hw, misc, pre, n, tid)) return K1_REDO;
-#endif
   ZH_STAMP(st_E1);
   u32 const wave = tid >> 6;
   u32 bo;  // (opaque: the block's workspace offset is not kept live across the window loop)

@@ -52,15 +52,6 @@ constexpr u32 L_MM = L_LM + 8 * NSEG;      // u64 match-start bits per segment
 constexpr u32 L_EX = L_MM + 8 * NSEG;      // u32 walk exit per segment
 constexpr u32 L_LP = L_EX + 4 * NSEG;      // u32 literals before the segment
 constexpr u32 L_MP = L_LP + 4 * NSEG;      // u32 matches before the segment
-#ifndef ZH_DEEP_WAVEQ
-#define ZH_DEEP_WAVEQ 1  // per-wave demand queues (C5 no dictionary 12.9 -> 13.8 GB/s)
-#endif
-#ifndef ZH_DEEP_G64EARLY
-#define ZH_DEEP_G64EARLY 1  // (C5 15.5 / 13.5 -> 15.8 / 14.0 GB/s without / with the COVER dictionary)
-#endif
-#ifndef ZH_DEEP_B64
-#define ZH_DEEP_B64 1  // extension bytes by 8-byte loads (C5 12.1 -> 12.9 GB/s)
-#endif
 constexpr u32 DEEP_LDS = 160 * 1024;
 constexpr u32 L_WS = DEEP_LDS - 256;       // u32[32] per-wave sums
 constexpr u32 L_MISC = L_WS + 4 * 32;      // u32[8]: [0] block_any flag, [1] next block
@@ -264,12 +255,12 @@ __device__ __forceinline__ u32 deep_search_one(const u32 *D32, const u16 *P16, c
   while (__ballot(act)) {
     if (act) {
       u32 const q = c - 1u;
-#if ZH_DEEP_G64EARLY
       // the first 8 candidate bytes loaded with the reject byte, not after it: one dependent LDS
-      // round trip per candidate instead of two once best >= 8 (the bytes are dropped on a reject)
+      // round trip per candidate instead of two once best >= 8 (the bytes are dropped on a reject;
+      // tried loading them after it: C5 15.5 / 13.5 against 15.8 / 14.0 GB/s without / with the
+      // COVER dictionary)
       u32 clo, chi;
       g64(D32, q, clo, chi);
-#endif
       bool w = true;
       if (best >= 8) {
         u32 const b = q + best;
@@ -278,19 +269,14 @@ __device__ __forceinline__ u32 deep_search_one(const u32 *D32, const u16 *P16, c
       u32 const nx = link(q);
       u32 l = 0;
       if (w) {
-#if !ZH_DEEP_G64EARLY
-        u32 clo, chi;
-        g64(D32, q, clo, chi);
-#endif
         u32 const x = O[0] ^ clo, y = O[1] ^ chi;
         l = x ? (u32)__builtin_ctz(x) >> 3 : y ? 4u + ((u32)__builtin_ctz(y) >> 3) : 8u;
         if (l == 8 && p + 8 < n) {
           u32 const sq = q & 3;
           u32 e = 56;
-#if ZH_DEEP_B64
           // bytes [q + 8, q + 64) from aligned 8-byte loads (half the LDS instructions of dword
-          // loads), dword j of the candidate being W[odd + j]: dwords 0..6 first (five loads), the
-          // rest (five more) only when those all match
+          // loads; tried those: C5 12.1 against 12.9 GB/s), dword j of the candidate being
+          // W[odd + j]: dwords 0..6 first (five loads), the rest (five more) only when those all match
           u32 const a8 = q + 8, wq8 = a8 >> 3, odd = (a8 >> 2) & 1u;
           const u64 *const D64 = (const u64 *)D32 + wq8;
           u32 W[10];
@@ -320,17 +306,6 @@ __device__ __forceinline__ u32 deep_search_one(const u32 *D32, const u16 *P16, c
               if (xx) e = 4 * (u32)j + ((u32)__builtin_ctz(xx) >> 3);
             }
           }
-#else
-          u32 B[15];
-          u32 const wq = (q >> 2) + 2;
-#pragma unroll
-          for (u32 k = 0; k < 15; k++) B[k] = D32[wq + k];
-#pragma unroll
-          for (int j = 13; j >= 0; j--) {
-            u32 const xx = O[j + 2] ^ __builtin_amdgcn_alignbyte(B[j + 1], B[j], sq);
-            if (xx) e = 4 * (u32)j + ((u32)__builtin_ctz(xx) >> 3);
-          }
-#endif
           l = 8 + e;
         }
       }
@@ -376,25 +351,16 @@ __device__ __forceinline__ void deep_search(const u32 *gdata, const u16 *gP16, u
 // the memo fit in LDS (C5's 16 KiB records with or without the 64 KiB dictionary).
 //   memo[i] (u16): 0xFFFF unsearched; else len | (bit length of off + 1) << 8 (the LAZY2 gain)
 constexpr u32 MEMO_UNK = 0xFFFFu;
-#ifndef ZH_DEEP_DEDUP
-#define ZH_DEEP_DEDUP 1  // (with the warm-up below: C5 13.8 / 12.3 -> 15.5 / 13.5 GB/s; alone no change)
-#endif
-// A position being searched (ZH_DEEP_DEDUP): a lane claims an unsearched position by clearing bit
+// A position being searched: a lane claims an unsearched position by clearing bit
 // 15 of its memo entry with an LDS atomic (known entries never have bit 15 set, so the clear cannot
 // touch them), and only the lane that saw MEMO_UNK come back searches it -- lanes and waves that
-// need the same position in the same round wait for that one search instead of repeating it.
+// need the same position in the same round wait for that one search instead of repeating it
+// (with the warm-up below: C5 13.8 / 12.3 -> 15.5 / 13.5 GB/s; alone no change).
 constexpr u32 MEMO_PEND = 0x7FFFu;
-__device__ __forceinline__ bool memo_unknown(u32 m) { return ZH_DEEP_DEDUP ? m >= MEMO_PEND : m == MEMO_UNK; }
-#ifndef ZH_DEEP_DQ
-#define ZH_DEEP_DQ 3
-#endif
-constexpr u32 DQ_PER = ZH_DEEP_DQ;  // positions posted per blocked lane (the needed one + lookahead)
-#ifndef ZH_DEEP_WARM
-#define ZH_DEEP_WARM (-2)  // first-walk warm-up: >= 0 positions, < 0 that many segment lengths
-#endif
-#ifndef ZH_DEEP_SEG0
-#define ZH_DEEP_SEG0 16u
-#endif
+__device__ __forceinline__ bool memo_unknown(u32 m) { return m >= MEMO_PEND; }
+constexpr u32 DQ_PER = 3;  // positions posted per blocked lane (the needed one + lookahead)
+constexpr int DEEP_WARM = -2;  // first-walk warm-up: >= 0 positions, < 0 that many segment lengths
+constexpr u32 DEEP_SEG0 = 16u;  // segment length for blocks of <= 16 KiB
 __device__ __forceinline__ int memo_gain(u32 m) { return (m & 255u) ? 4 * (int)(m & 255u) - (int)(m >> 8) : -1000; }
 // Segment length: 16 positions for blocks of <= 16 KiB, doubled per doubling of nb (<= 64), and
 // doubled again for a dictionary's first block, whose searches (chains through the dictionary's
@@ -402,24 +368,25 @@ __device__ __forceinline__ int memo_gain(u32 m) { return (m & 255u) ? 4 * (int)(
 // entries (C5 level 9 with the 64 KiB dictionary 11.2 / 11.5 -> 11.7 / 12.2 GB/s; without a
 // dictionary 16 stays faster, 13.8 vs 13.0, as every wave keeps a segment).
 __device__ __forceinline__ u32 demand_segl(u32 nb, bool dict) {
-  u32 const s = (nb <= 16384u ? ZH_DEEP_SEG0 : nb <= 32768u ? 2u * ZH_DEEP_SEG0 : 4u * ZH_DEEP_SEG0) << (dict ? 1 : 0);
+  u32 const s = (nb <= 16384u ? DEEP_SEG0 : nb <= 32768u ? 2u * DEEP_SEG0 : 4u * DEEP_SEG0) << (dict ? 1 : 0);
   return s < 64u ? s : 64u;
 }
 // First-walk warm-up: a segment's first walk starts this many positions before the segment (a
 // walk from a wrong position meets the serial parse within a few steps, as K3's FSE chains do),
 // so its entry guess is usually the true one and fewer Jacobi iterations follow; positions before
 // the segment are walked but not recorded (tools/deep_jacobi_model.c).  The warm-up walks need the
-// positions the segment before also needs at the same time, hence ZH_DEEP_DEDUP.  Measured (C5
+// positions the segment before also needs at the same time, hence the claims above.  Measured (C5
 // level 9, none / COVER dictionary GB/s, tools/gpu_diag.sh c5var): no warm-up 13.8 / 12.3; 16
 // positions 15.0 / 12.9; one segment 14.9 / 13.2; two 15.5 / 13.5 (Jacobi iterations 4.3 -> 2.3
 // and 3.5 -> 1.5); three 15.5 / 12.9; four 15.2 / 12.1.  Without the claims: 13.1-13.3 / 12.4-12.6.
-__device__ __forceinline__ u32 demand_warm(u32 segl) { return ZH_DEEP_WARM < 0 ? (u32)(-(ZH_DEEP_WARM)) * segl : (u32)ZH_DEEP_WARM; }
+__device__ __forceinline__ u32 demand_warm(u32 segl) { return DEEP_WARM < 0 ? (u32)(-DEEP_WARM) * segl : (u32)DEEP_WARM; }
 // LDS bytes the demand path needs above the staged bytes (memo, queue, exits), for nb positions
 __device__ __forceinline__ u32 demand_lds(u32 nb) { return ((2u * nb + 15u) & ~15u) + 2u * DQ_PER * DT + 4u * DT; }
 
 // Returns through meta / seq_out / lit_out like step 5 of deep_block.  lds = the free LDS above the
 // staged bytes (demand_lds(nb) bytes); misc = deep_block's LDS scalars ([0] the wg_any flag,
-// [2] the queue count).
+// [2] cleared here and otherwise unused: it counted the workgroup queue tried before the
+// per-wave queues).
 __device__ void deep_parse_demand(const u32 *D32, const u16 *P16, const u32 *dprev, u32 *offg, u8 *lds, u32 *misc, u32 *wsum, u32 pre, u32 nb,
                                   u32 n, u32 lim, u32 s0, u32 depth, u32 tid, ZhWorkspace ws, u32 b, const u8 *stg) {
   u16 *const memo = (u16 *)lds;
@@ -438,7 +405,7 @@ __device__ void deep_parse_demand(const u32 *D32, const u16 *P16, const u32 *dpr
 #ifdef ZH_STAMPS
   u64 const dm0 = __builtin_amdgcn_s_memtime();
   u32 st_rounds = 0, st_searched = 0, st_walk = 0, st_jac = 0;
-  u32 st_adv = 0, st_sync1 = 0, st_srch = 0, st_sync2 = 0;  // (thread 0's wave)
+  u32 st_adv = 0, st_sync1 = 0, st_srch = 0, st_sync2 = 0;  // (thread 0's wave; the sync slots stay 0: no workgroup barrier in a round)
   u64 tq = 0;
 #define DMSTAMP(acc) do { u64 const _t = __builtin_amdgcn_s_memtime(); acc += (u32)(_t - tq); tq = _t; } while (0)
 #else
@@ -496,11 +463,11 @@ __device__ void deep_parse_demand(const u32 *D32, const u16 *P16, const u32 *dpr
           }
         }
       }
-#if ZH_DEEP_WAVEQ
       // post the needed position and the two after it (the lazy check's lookahead) to this
       // wave's own queue (ballot-compacted), then the wave searches it (lanes = entries): no
       // workgroup barrier, every wave walks at its own pace.  A position another wave is
-      // searching at the same time may be searched twice (same result).
+      // searching at the same time may be searched twice (same result).  (Tried one workgroup
+      // queue and two barriers per round: C5 without a dictionary 12.9 against 13.8 GB/s.)
       DMSTAMP(st_adv);
       if (!__ballot(act)) break;  // every walk of this wave has left its segment or merged
       u16 *const wq = q + (tid & ~63u) * DQ_PER;
@@ -510,13 +477,11 @@ __device__ void deep_parse_demand(const u32 *D32, const u16 *P16, const u32 *dpr
       for (u32 t = 0; t < DQ_PER; t++) {
         u32 const x = need + t;
         bool post = need != ~0u && x < nb && memo[x] == MEMO_UNK;
-#if ZH_DEEP_DEDUP
         if (post) {  // claim it: UNK -> PEND; a lane that finds it claimed leaves it to its claimant
           u32 const sh = 16u * (x & 1u);
           u32 const o = atomicAnd((u32 *)memo + (x >> 1), ~(0x8000u << sh));
           post = ((o >> sh) & 0xFFFFu) == MEMO_UNK;
         }
-#endif
         u64 const bm = __ballot(post);
         u32 const rank = __builtin_amdgcn_mbcnt_hi((u32)(bm >> 32), __builtin_amdgcn_mbcnt_lo((u32)bm, 0u));
         if (post) wq[nq + rank] = (u16)x;
@@ -539,51 +504,11 @@ __device__ void deep_parse_demand(const u32 *D32, const u16 *P16, const u32 *dpr
           memo[x] = (u16)(l ? l | ((31u - (u32)__builtin_clz((r >> 8) + 1u)) << 8) : 0u);
         }
       }
-#if ZH_DEEP_DEDUP
       // (positions this wave waits for may be another wave's: re-read the memo from LDS)
       if (nq == 0) __builtin_amdgcn_s_sleep(2);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-#else
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
       __builtin_amdgcn_wave_barrier();
       DMSTAMP(st_srch);
-#else
-      // post the needed position and the two after it (the lazy check's lookahead)
-      if (need != ~0u) {
-#pragma unroll
-        for (u32 t = 0; t < DQ_PER; t++) {
-          u32 const x = need + t;
-          if (x < nb && memo[x] == MEMO_UNK) q[atomicAdd(&misc[2], 1u)] = (u16)x;
-        }
-      }
-      DMSTAMP(st_adv);
-      __syncthreads();
-      u32 const nq = misc[2];
-      DMSTAMP(st_sync1);
-      if (nq == 0) break;  // (every lane has finished: no lane needed anything)
-#ifdef ZH_STAMPS
-      st_rounds++;
-      st_searched += nq;
-#endif
-      // search the queue, lanes = entries (a position queued twice is searched twice, same result)
-      for (u32 j0 = 0; j0 < nq; j0 += DT) {
-        u32 const j = j0 + tid;
-        bool const v = j < nq;
-        u32 const x = v ? q[j] : 0u;
-        u32 const r = deep_search_one(D32, P16, dprev, x, v, pre, nb, n, lim, s0, depth);
-        if (v) {
-          offg[x] = r;
-          u32 const l = r & 255u;
-          memo[x] = (u16)(l ? l | ((31u - (u32)__builtin_clz((r >> 8) + 1u)) << 8) : 0u);
-        }
-      }
-      DMSTAMP(st_srch);
-      __syncthreads();
-      DMSTAMP(st_sync2);
-      if (tid == 0) misc[2] = 0;
-      __syncthreads();
-#endif
     }
     if (act0) {
       if (merged) {
@@ -757,7 +682,6 @@ __device__ void deep_block(const ZhBlockDesc &d, ZhWorkspace ws, u32 b, u8 *slot
     for (u32 v = tid; 16 * v < n + 80; v += DT) *(uint4 *)(smem + e16 + 16 * v) = *(const uint4 *)(stg + 16 * v);
   __threadfence_block();
   __syncthreads();
-#ifndef ZH_DEEP_NO_DEMAND
   // demand-driven search + parse when the memo fits beside the links and bytes in LDS
   u32 const dbase = e16 + ((n + 96 + 15) & ~15u);
   if (d_lds && dbase + demand_lds(nb) <= SEARCH_LDS) {
@@ -767,7 +691,6 @@ __device__ void deep_block(const ZhBlockDesc &d, ZhWorkspace ws, u32 b, u8 *slot
     DSTAMP(4);
     return;
   }
-#endif
   // typed LDS / global variants (a generic pointer makes every access a flat one: measured slower
   // than global memory)
   if (d_lds) deep_search<true, true>(s32, (const u16 *)(slot + SLOT_P16), e16, dprev, offg, pre, nb, n, lim, s0, depth, tid);

@@ -2,7 +2,9 @@
 `bash tools/variants.sh build tl -DZH_TIMELINE`): s_memtime cycles per step in each phase, averaged
 over every step of every block of one C3-style batch.  Worker waves 0..13: P wait | lengths |
 parse/records | X wait | span tops + literals; inserter waves 14 (long) / 15 (short): P wait |
-insertion (X taken between tiles included) | literal rounds | barriers after them | dump.
+insertion | literal rounds | barriers after them | dump.  The step has one barrier (P) since
+round 6, so the X columns and the workers' last one stay near zero; they are kept so that
+old and new timelines line up.
 usage: CUDA_ZSTD_HIP_LIB=tools/libV_tl.so python3 tools/timeline.py [LEVEL] [CHUNKS] [KIND]"""
 import ctypes
 import json

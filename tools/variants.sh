@@ -1,6 +1,8 @@
 #!/bin/bash
 # Build K1 variants here (`bash tools/variants.sh build NAME "-DFLAG=..." ...`: NAME -> tools/libV_NAME.so,
 # stamps build tools/libVS_NAME.so) and time them on the GPU box (`bash tools/variants.sh run NAME...`).
+# The kernels keep no experiment switches (DESIGN.md "Build switches"): the flags are those of the
+# `#ifndef` knobs an experiment branch has added for itself.
 set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 P=$R/custom-nvcomp-with-zstd_amd
