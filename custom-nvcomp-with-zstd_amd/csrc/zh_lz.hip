@@ -32,7 +32,9 @@
 //                 segment (one literal run + one match per step, from the take mask) from a
 //                 guessed entry; Jacobi rounds re-walk the segments whose entry changed until
 //                 the walk meets the previous one -- exactly the serial parse; then the
-//                 window's match list.
+//                 window's match list, every match's info gathered into registers in two LDS
+//                 trips, the match-info buffer released to the inserters' dump (MISC_PF), and
+//                 only then the scans and the list's entries.
 //   wave 1        after its lengths: window k-2's catch-up and sequence records.
 //   waves 14, 15  after their insertion: window k-3's literal bytes, a lane = one dword of the
 //                 window (lit_rounds; zh_litpack.h).
@@ -41,6 +43,7 @@
 #include "zh_litpack.h"
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #if defined(ZH_STAMPS) || defined(ZH_INS_CHECK)
@@ -57,10 +60,11 @@ extern "C" u32 zh_fixups_host() {
 #endif
 // Diagnostic build only (-DZH_TIMELINE, tools/timeline.py): per K1 wave and step phase, the
 // s_memtime cycles summed over every step of every block (VERDICT r5 item 2's executed per-phase
-// breakdown of the window pipeline).  Worker waves: 0 P wait, 1 lengths, 2 parse / records,
-// 3 and 4 empty (the second barrier's wait and the work after it, before the step had one barrier);
-// inserter waves: 0 P wait, 1 insertion of the next window, 2 literals, 3 empty, 4 candidate dump;
-// [5] steps.
+// breakdown of the window pipeline).  Worker waves: 0 P wait, 1 lengths, 2 parse / records (wave 0:
+// the parse up to its store of MISC_PF), 3 wave 0's work after that store (empty on the others),
+// 4 empty (the work after a second barrier, before the step had one barrier);
+// inserter waves: 0 P wait, 1 insertion of the next window, 2 literals, 3 the wait for MISC_PF,
+// 4 candidate dump; [5] steps.
 #ifdef ZH_TIMELINE
 __device__ unsigned long long g_tl[16 * 8];
 extern "C" __global__ void zh_read_timeline(unsigned long long *out) {
@@ -92,14 +96,16 @@ constexpr u32 NROUND = ZH_WINDOW / 64;      // 64-position length rounds per win
 constexpr u32 SEGP = 32;                    // positions per walk segment (one lane of wave 0)
 constexpr u32 NSEG = ZH_WINDOW / SEGP;      // walk segments per window
 constexpr u32 INS_TID = 896;                // first inserter thread (waves 14, 15)
-// worker rounds per wave (rounds_of below): 2 bits per wave, 0 2 3 3 3 3 3 3 3 2 2 2 2 1
+// worker rounds per wave (rounds_of below): 2 bits per wave, wave 0 in the lowest:
+// 0 | 2 | 3 x 7 (waves 2..8) | 2 x 4 (waves 9..12) | 1 (wave 13), 8 rounds per SIMD
 constexpr u64 ROUND_TAB = 0x6abfff8ull;
 constexpr u32 NWW = INS_TID / 64;           // worker waves
 constexpr u32 TILES = ZH_WINDOW / ZH_TILE;  // 16 tiles per window
 constexpr u32 TPL = ZH_TILE / 64;           // positions per inserter lane per tile
 constexpr u32 NCR = TILES * TPL / 2;        // candidate registers per inserter lane (u16 pairs)
 static_assert(NSEG == 64, "one walk lane per segment");
-static_assert(INS_TID == 896 && NROUND == 32, "round split: waves 1..13 take 6 x 3 + 7 x 2 rounds");
+static_assert(INS_TID == 896 && NROUND == 32, "round split: waves 1..13 take 2, 7 x 3, 4 x 2 and 1 rounds");
+static_assert((ROUND_TAB & 3) == 0 && (ROUND_TAB >> (2 * (INS_TID / 64))) == 0, "no length rounds on wave 0 or the inserters");
 constexpr u32 REC_WAVE = 1;  // the worker wave that writes a window's records (after its length rounds)
 static_assert(ZH_WINDOW % ZH_TILE == 0 && ZH_TILE % 64 == 0 && TILES * TPL % 2 == 0, "tiles tile windows");
 
@@ -138,14 +144,16 @@ constexpr u32 LB_WORDS = NSEG + 4;
 // One barrier (P) per window step: the take bits at the worker waves' span tops (lazy rule: they
 // need the next span's first info) are decided by wave 0 at the start of the window's parse in the
 // next step (and by every wave in the probe step), and the inserters dump the next window's
-// candidates once wave 0 has read the previous window's match info (an LDS flag, MISC_PF).  Tried
+// candidates once wave 0 has read the previous window's match info (an LDS flag, MISC_PF): wave 0
+// gathers every match's info into registers right after the walks and the list build and sets the
+// flag there, ahead of the scans and the match-list entries, which need no read of it.  Tried
 // a second barrier X after the lengths, each wave deciding its own top after it: K1 10.12 against
 // 9.70 ms at level 3, 7.52 against 7.21 ms at level 1 (profiles/r06k_one_barrier_ab.json; every
 // wave deciding its own top from an extra info, without X, was slower too: 10.50 ms)
 constexpr u32 K1_LDS = OFF_LB + 4 * LB_WORDS * LB_BUFS;
 constexpr u32 ML_LO = 11, ML_LEN = 22, ML_OFF = 29, ML_CUM = 45;  // match-list entry: start [0, 11) | ...
 constexpr u32 MISC_WNM = 0;   // misc[par]: matches of the window of that parity (its match list's length)
-constexpr u32 MISC_PF = 12;   // misc[12]: k + 1 once wave 0 has read window k - 1's match info
+constexpr u32 MISC_PF = 12;   // misc[12]: k + 1 once wave 0 has read window k - 1's match info (in step k)
 constexpr u32 MISC_NM = 4;    // misc[4 + (j & 3)]: matches the parse took in window j (miss skip)
 constexpr u32 MISC_ANY = 13;  // misc[13]: block_any's flag (0 between calls)
 constexpr u32 MISC_SCAN = 2;  // misc[2]: the repeat scan's count
@@ -304,7 +312,7 @@ __device__ __forceinline__ void insert_repair(u16 *T, u32 tb0, u32 lane, const u
 // among the searched tiles" -- and returns whether the window's search resumes; if not, the rest
 // of the window is neither looked up nor inserted and its candidates are never dumped.
 template <bool LONG, typename Check>
-__device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, u32 lim, u32 lane, u32 (&creg)[NCR], const u32 *flag,
+__device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, u32 lim, u32 lane, u32 (&creg)[NCR],
                                               Check &&on_check, bool skip, u32 pmin) {
   // positions below pmin are already in T (a dictionary's precomputed tables): treated like
   // positions past lim (the junk slot, no candidate)
@@ -360,9 +368,6 @@ __device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, 
       for (u32 k = 0; k < TPL; k++) r[b][k] = T[h[b][k]];
 #endif
     if (t0 + BT < NT) load_in(tb0 + BT * ZH_TILE);
-    // (a leftover of the two-barrier protocol, which polled the workers' arrival counter here:
-    // taking this load out changes the inserters' generated code, so it stays for now)
-    (void)__atomic_load_n(flag, __ATOMIC_RELAXED);
 #ifdef ZH_INS_CHECK
     bool lost = false;
 #pragma unroll
@@ -1143,7 +1148,7 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
   u32 creg[NCR];
   if (span_s < span_e) insert_span<LONG>(in32, T, span_s, span_e, lane);
   // (the first window: its own instantiation, with pmin and no resume check)
-  insert_window<LONG>(in32, T, wstart, lim, lane, creg, &misc_[MISC_PF], NoCheck{}, false, pmin);
+  insert_window<LONG>(in32, T, wstart, lim, lane, creg, NoCheck{}, false, pmin);
   u32 cwe = lookahead<LONG>(in32, T, min(wstart + (u32)ZH_WINDOW, n), lim, lane);
   bool skipc = false;  // the window whose candidates creg holds is a miss-skip window (not resumed)
 #ifdef ZH_STAMPS
@@ -1155,10 +1160,12 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
     if (probe_dead(misc_, k, kprobe)) return true;
     u32 const wsb = wstart + k * ZH_WINDOW;
     if (k < nwin) {
-      // buffer k & 1 held window k - 2's match info, which wave 0 read in step k - 1
+      // buffer k & 1 held window k - 2's match info, which wave 0 read in step k - 1: for the last
+      // time when it gathered the matches' info, before its entries pass, and it set the flag there
       // (bounded: wave 0 sets the flag every step; the bound only keeps a bug from hanging the GPU)
       for (u32 it = 0; it < (1u << 22) && (u32)__builtin_amdgcn_readfirstlane(__atomic_load_n(&misc_[MISC_PF], __ATOMIC_RELAXED)) < k; it++)
         __builtin_amdgcn_s_sleep(1);
+      TL_MARK(3);
       if (skipc) dump_window<LONG, ZH_SKIP_TILES>(ci8 + (k & 1u) * 4 * CI_WORDS, lane, creg, cwe);
       else dump_window<LONG, TILES>(ci8 + (k & 1u) * 4 * CI_WORDS, lane, creg, cwe);
     }
@@ -1177,7 +1184,7 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
       // a miss-skip window's first tiles, then the rest of it if any of them found a match (both
       // inserters' checks combined before either takes a barrier)
       bool resumed = false;
-      insert_window<LONG>(in32, T, nx, lim, lane, creg, &misc_[MISC_PF],
+      insert_window<LONG>(in32, T, nx, lim, lane, creg,
                           [&](bool h) { return resumed = resume_exchange<LONG, TWO>(misc_, k + 1, h, lane); }, skipc, 0u);
       if (resumed) skipc = false;
       cwe = lookahead<LONG>(in32, T, min(nx + ZH_WINDOW, n), lim, lane);
@@ -1190,7 +1197,6 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
     // the next writes to those buffers come after P of step k + 1)
     lj.step(k, lane);
     TL_MARK(2);
-    TL_MARK(3);
   }
   TL_FLUSH(LONG ? 14u : 15u, lane);
 #ifdef ZH_STAMPS
@@ -1693,11 +1699,42 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
         }
       }
       ZH_STAMP(st_J2);
+      // every match's info (lanes = matches) before anything else: the passes' list reads go out in
+      // one LDS trip and their info reads in a second, the values stay in registers, and these are
+      // wave 0's last reads of window k - 1's match info -- so the buffer is released here, before
+      // the scans and the entry stores, which then run beside the inserters' dump
+      constexpr u32 NPASS = (ML_CAP + 63) / 64;
+      // (straight-line groups of NP1 and NPASS - NP1 passes, lanes past the list read a clamped
+      // slot: a branch per pass would make every info read wait for the one before it)
+      constexpr u32 NP1 = 4;
+      u32 msv[NPASS] = {}, infv[NPASS] = {};
+      auto gather = [&](auto PA, auto PB) {
+        constexpr u32 pa = decltype(PA)::value, pb = decltype(PB)::value;
+#pragma unroll
+        for (u32 p = 0; p < NPASS; p++)
+          if (p >= pa && p < pb) {
+            u32 const j = 64 * p + lane, e = (u32)mlP[min(j, ML_CAP - 1u)];
+            msv[p] = j < nm ? e : 0u;
+          }
+#pragma unroll
+        for (u32 p = 0; p < NPASS; p++)
+          if (p >= pa && p < pb) infv[p] = ciP[cidx(msv[p])];
+      };
+      gather(std::integral_constant<u32, 0>{}, std::integral_constant<u32, NP1>{});
+      if (nm > 64 * NP1) gather(std::integral_constant<u32, NP1>{}, std::integral_constant<u32, NPASS>{});
+      // (the release fence keeps the reads above ahead of the flag's store; LDS operations of one
+      // wave apply in program order)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      if (lane == 0) __atomic_store_n(&misc[MISC_PF], k + 1, __ATOMIC_RELAXED);
+      TL_MARK(2);
       u32 covered = 0, pend = e0;  // walk lengths of the matches before this pass; end of the last one
-      for (u32 j0 = 0; j0 < nm; j0 += 64) {
+#pragma unroll
+      for (u32 p = 0; p < NPASS; p++) {
+        u32 const j0 = 64 * p;
+        if (j0 >= nm) break;
         u32 const j = j0 + lane;
         bool const v = j < nm;
-        u32 const ms = v ? (u32)mlP[j] : 0u, inf = ciP[cidx(ms)];
+        u32 const ms = msv[p], inf = infv[p];
         u32 const len = v ? inf & 255u : 0u, off = (inf >> 8) & 0xFFFFu;
         u32 const incl = wave_scan_incl(len);
         u32 const cum = nwalk_tot + (ms - e0) - (covered + incl - len);
@@ -1711,9 +1748,12 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
       if (lane == 0) { misc[MISC_WNM + (kb ^ 1u)] = nm; misc[MISC_NM + ((k - 1) & 3)] = nm; }
       ZH_STAMP(st_J);
     }
-    // wave 0 is done with window k - 1's match info: the inserters may dump window k + 1's
-    // candidates into that buffer
-    if (wave == 0 && lane == 0) __atomic_store_n(&misc[MISC_PF], k + 1, __ATOMIC_RELAXED);
+    // (a step without a parse: nothing of that buffer is read, the inserters may dump window
+    // k + 1's candidates into it at once; the parse above sets the flag after its last read)
+    if (wave == 0 && !prev) {
+      if (lane == 0) __atomic_store_n(&misc[MISC_PF], k + 1, __ATOMIC_RELAXED);
+      TL_MARK(2);
+    }
     if (wave == REC_WAVE && prev2) {
       // ---- catch-up and sequence records of window k - 2, lanes = matches.  A match grows
       // back over the literals down to the end of the match before it; it takes back e bytes of
@@ -1745,9 +1785,9 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
       nlit_tot += lane_value(lincl, 63);
       nseq_tot += nm;
     }
-    TL_MARK(2);
-    // (the diagnostic builds' slots of the former second barrier and of the work after it: empty
-    // now, kept so that the tools' columns stand)
+    // (the diagnostic builds' slot 3: wave 0's work after it has released the match-info buffer;
+    // empty on the other worker waves.  Slot 4, of the former work after a second barrier, is empty.)
+    if (wave != 0) TL_MARK(2);
     TL_MARK(3);
     ZH_STAMP(st_X);
     ZH_STAMP(st_E);

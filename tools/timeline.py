@@ -1,10 +1,13 @@
 """Diagnostic: K1's window-pipeline timeline per wave (-DZH_TIMELINE build, e.g. tools/libV_tl.so from
 `bash tools/variants.sh build tl -DZH_TIMELINE`): s_memtime cycles per step in each phase, averaged
 over every step of every block of one C3-style batch.  Worker waves 0..13: P wait | lengths |
-parse/records | X wait | span tops + literals; inserter waves 14 (long) / 15 (short): P wait |
-insertion | literal rounds | barriers after them | dump.  The step has one barrier (P) since
-round 6, so the X columns and the workers' last one stay near zero; they are kept so that
-old and new timelines line up.
+parse/records | after the flag | (empty); inserter waves 14 (long) / 15 (short): P wait |
+insertion | literal rounds | flag wait | dump.  The flag is MISC_PF, wave 0's release of the
+previous window's match-info buffer, which the inserters' dump waits for: wave 0's parse_rec is
+its time from P to the flag store (flag_at = lengths + parse_rec, the flag's time after P),
+after_flag the rest of its step; flag_wait is the inserters' poll, split from the dump.  The
+workers' last column is that of the work after a second barrier the step no longer has; it stays
+near zero and is kept so that old and new timelines line up.
 usage: CUDA_ZSTD_HIP_LIB=tools/libV_tl.so python3 tools/timeline.py [LEVEL] [CHUNKS] [KIND]"""
 import ctypes
 import json
@@ -43,8 +46,8 @@ bc.compress_async(*args, temp)
 torch.cuda.synchronize()
 assert L.zh_timeline_host(buf) == 0
 a = np.array(buf[:], dtype=np.float64).reshape(16, 8)
-names_w = ["P_wait", "lengths", "parse_rec", "X_wait", "lits"]
-names_i = ["P_wait", "insert", "lits", "X_after", "dump"]
+names_w = ["P_wait", "lengths", "parse_rec", "after_flag", "lits"]
+names_i = ["P_wait", "insert", "lits", "flag_wait", "dump"]
 res = {"level": level, "chunks": n, "kind": kind, "waves": {}}
 for w in range(16):
     steps = a[w, 5]
@@ -54,6 +57,8 @@ for w in range(16):
     nm = names_i if w >= 14 else names_w
     res["waves"][w] = {nm[i]: round(per[i]) for i in range(5) if nm[i] != "-"}
     res["waves"][w]["step"] = round(per.sum())
+    if w == 0:
+        res["waves"][w]["flag_at"] = round(per[1] + per[2])
 print(json.dumps(res))
 for w, v in res["waves"].items():
     print(f"wave {int(w):2d} (SIMD {int(w) % 4}):", "  ".join(f"{k} {x:6d}" for k, x in v.items()))
