@@ -25,6 +25,7 @@
 //   5. records (walk literals before the match | length | 0 | offset) and the literal bytes
 #include "zh_common.h"
 #include "zh_hash.h"
+#include <vector>
 
 namespace {
 
@@ -367,7 +368,7 @@ __device__ __forceinline__ int memo_gain(u32 m) { return (m & 255u) ? 4 * (int)(
 // links in L2) are the costly part: fewer segment boundaries, fewer positions walked from wrong
 // entries (C5 level 9 with the 64 KiB dictionary 11.2 / 11.5 -> 11.7 / 12.2 GB/s; without a
 // dictionary 16 stays faster, 13.8 vs 13.0, as every wave keeps a segment).
-__device__ __forceinline__ u32 demand_segl(u32 nb, bool dict) {
+__host__ __device__ __forceinline__ u32 demand_segl(u32 nb, bool dict) {
   u32 const s = (nb <= 16384u ? DEEP_SEG0 : nb <= 32768u ? 2u * DEEP_SEG0 : 4u * DEEP_SEG0) << (dict ? 1 : 0);
   return s < 64u ? s : 64u;
 }
@@ -381,18 +382,47 @@ __device__ __forceinline__ u32 demand_segl(u32 nb, bool dict) {
 // and 3.5 -> 1.5); three 15.5 / 12.9; four 15.2 / 12.1.  Without the claims: 13.1-13.3 / 12.4-12.6.
 __device__ __forceinline__ u32 demand_warm(u32 segl) { return DEEP_WARM < 0 ? (u32)(-DEEP_WARM) * segl : (u32)DEEP_WARM; }
 // LDS bytes the demand path needs above the staged bytes (memo, queue, exits), for nb positions
-__device__ __forceinline__ u32 demand_lds(u32 nb) { return ((2u * nb + 15u) & ~15u) + 2u * DQ_PER * DT + 4u * DT; }
+__host__ __device__ __forceinline__ u32 demand_lds(u32 nb) { return ((2u * nb + 15u) & ~15u) + 2u * DQ_PER * DT + 4u * DT; }
+
+// The search / parse variant of a block of nb bytes staged behind pre bytes whose chains start at
+// staged position s0 (a dictionary's precomputed split, else 0) -- what fits in LDS below the scan
+// sums: the u16 link distances of the E linked positions [s0, lim) (e16 bytes), then the staged
+// bytes, then the demand path's memo, queues and exits (from dbase).  deep_block takes its
+// variant from here and nowhere else; tests read it through zh_test_deep_path.
+enum : u32 {
+  DEEP_PATH_DEMAND = 0,  // links, bytes and memo in LDS: deep_parse_demand, segments of segl positions
+  DEEP_PATH_BYTES = 1,   // links and bytes in LDS: deep_search<true, true>
+  DEEP_PATH_LINKS = 2,   // links in LDS, bytes from the slot: deep_search<false, true>
+  DEEP_PATH_SLOT = 3,    // links and bytes from the slot: deep_search<false, false>
+};
+struct DeepPath {
+  u32 e16, dbase, segl;
+  bool p_lds, d_lds, demand;
+  __host__ __device__ u32 path() const { return demand ? DEEP_PATH_DEMAND : d_lds ? DEEP_PATH_BYTES : p_lds ? DEEP_PATH_LINKS : DEEP_PATH_SLOT; }
+};
+__host__ __device__ __forceinline__ DeepPath deep_path(u32 pre, u32 nb, u32 s0) {
+  u32 const n = pre + nb, lim = n > ZH_HASH_READ ? n - ZH_HASH_READ : 0u;
+  u32 const E = lim > s0 ? lim - s0 : 0u;
+  DeepPath r;
+  r.e16 = (2 * E + 15) & ~15u;
+  r.p_lds = r.e16 <= SEARCH_LDS;
+  r.d_lds = r.p_lds && r.e16 + n + 96 <= SEARCH_LDS;
+  r.dbase = r.e16 + ((n + 96 + 15) & ~15u);
+  r.demand = r.d_lds && r.dbase + demand_lds(nb) <= SEARCH_LDS;
+  r.segl = demand_segl(nb, s0 != 0);
+  return r;
+}
 
 // Returns through meta / seq_out / lit_out like step 5 of deep_block.  lds = the free LDS above the
 // staged bytes (demand_lds(nb) bytes); misc = deep_block's LDS scalars ([0] the wg_any flag,
 // [2] cleared here and otherwise unused: it counted the workgroup queue tried before the
 // per-wave queues).
 __device__ void deep_parse_demand(const u32 *D32, const u16 *P16, const u32 *dprev, u32 *offg, u8 *lds, u32 *misc, u32 *wsum, u32 pre, u32 nb,
-                                  u32 n, u32 lim, u32 s0, u32 depth, u32 tid, ZhWorkspace ws, u32 b, const u8 *stg) {
+                                  u32 n, u32 lim, u32 s0, u32 depth, u32 tid, ZhWorkspace ws, u32 b, const u8 *stg, u32 SEGL) {
   u16 *const memo = (u16 *)lds;
   u16 *const q = (u16 *)(lds + ((2u * nb + 15u) & ~15u));
   u32 *const exL = (u32 *)((u8 *)q + 2u * DQ_PER * DT);
-  u32 const SEGL = demand_segl(nb, s0 != 0), nseg = (nb + SEGL - 1) / SEGL;
+  u32 const nseg = (nb + SEGL - 1) / SEGL;  // SEGL: deep_path's segment length
   // unsearched below lim, no match at or past it (the oracle's len[] is 0 there)
   for (u32 i = tid; i < nb; i += DT) memo[i] = pre + i < lim ? (u16)MEMO_UNK : (u16)0;
   if (tid == 0) misc[2] = 0;
@@ -670,9 +700,9 @@ __device__ void deep_block(const ZhBlockDesc &d, ZhWorkspace ws, u32 b, u8 *slot
   // 64 KiB dictionary: every candidate step is LDS-only); otherwise the distances in LDS or the
   // slot and the bytes from the slot (L2).  Generic pointers: one code path for both.
   u32 const E = lim > s0 ? lim - s0 : 0u;  // linked positions [s0, lim)
-  u32 const e16 = (2 * E + 15) & ~15u;
-  bool const p_lds = e16 <= SEARCH_LDS;
-  bool const d_lds = p_lds && e16 + n + 96 <= SEARCH_LDS;
+  DeepPath const dp = deep_path(pre, nb, s0);
+  u32 const e16 = dp.e16;
+  bool const p_lds = dp.p_lds, d_lds = dp.d_lds;
   u16 *const P16w = p_lds ? (u16 *)smem : (u16 *)(slot + SLOT_P16);
   for (u32 i = tid; i < E; i += DT) {
     u32 const c = prev[s0 + i], dl = c ? s0 + i + 1u - c : 0u;
@@ -683,11 +713,15 @@ __device__ void deep_block(const ZhBlockDesc &d, ZhWorkspace ws, u32 b, u8 *slot
   __threadfence_block();
   __syncthreads();
   // demand-driven search + parse when the memo fits beside the links and bytes in LDS
-  u32 const dbase = e16 + ((n + 96 + 15) & ~15u);
-  if (d_lds && dbase + demand_lds(nb) <= SEARCH_LDS) {
+  u32 const dbase = dp.dbase;
+  // (deep_path asked again behind d_lds: the compiler then keeps the demand figures inside that
+  // branch, the code this kernel had before deep_path existed; `if (dp.demand)` computes them
+  // ahead of the loop above and the level-9 kernel runs 1-1.5 % longer, C5 4.60 / 4.04 against
+  // 4.55 / 3.98 ms)
+  if (d_lds && deep_path(pre, nb, s0).demand) {
     DSTAMP(2);  // (search set-up: link distances and bytes in LDS)
     deep_parse_demand((const u32 *)(smem + e16), (const u16 *)smem, dprev, offg, smem + dbase, misc, wsum, pre, nb, n, lim, s0, depth, tid, ws, b,
-                      stg);
+                      stg, dp.segl);
     DSTAMP(4);
     return;
   }
@@ -817,10 +851,14 @@ extern "C" __global__ __launch_bounds__(DT) void zh_deep_dict_kernel(const u8 *_
 namespace zh {
 // chains of a dictionary's last min(cn, ZH_DEEP_PRE) content bytes: dprev u32[ZH_DEEP_PRE],
 // dhead u32[2^ZH_HASH_LOG_SHORT], stg >= ZH_DEEP_PRE + 64 bytes; P = 0: none (too short)
-hipError_t lz_deep_dict_tables(const u8 *content, size_t cn, u8 *stg, u32 *dprev, u32 *dhead, u32 &P, u32 &split, hipStream_t stream) {
+static void deep_dict_split(size_t cn, u32 &P, u32 &split) {
   P = (u32)std::min(cn, (size_t)ZH_DEEP_PRE);
   split = (P > ZH_HASH_READ ? P - ZH_HASH_READ : 0u) & ~3u;
-  if (split < 64) { P = split = 0; return hipSuccess; }
+  if (split < 64) P = split = 0;
+}
+hipError_t lz_deep_dict_tables(const u8 *content, size_t cn, u8 *stg, u32 *dprev, u32 *dhead, u32 &P, u32 &split, hipStream_t stream) {
+  deep_dict_split(cn, P, split);
+  if (!P) return hipSuccess;
   hipLaunchKernelGGL(zh_deep_dict_kernel, dim3(1), dim3(DT), DEEP_LDS, stream, content + cn - P, P, stg, dprev, dhead);
   return hipGetLastError();
 }
@@ -831,7 +869,7 @@ hipError_t lz_deep_init() {
   return e;
 }
 
-hipError_t lz_deep_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, int level, hipStream_t stream) {
+static hipError_t deep_launch_depth(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 depth, hipStream_t stream) {
   int dev = 0, cus = 0;
   if (stream) (void)hipStreamGetDevice(stream, &dev);
   else (void)hipGetDevice(&dev);
@@ -840,7 +878,126 @@ hipError_t lz_deep_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace w
   // one persistent workgroup per CU, at most one per scratch slot of the caller's workspace
   if (!ws.deep_slots || !ws.deep_nslots) return hipErrorInvalidValue;
   u32 const grid = std::min(std::min(nblocks, (u32)cus), ws.deep_nslots);
-  hipLaunchKernelGGL(zh_lz_deep_kernel, dim3(grid), dim3(DT), DEEP_LDS, stream, d_descs, nblocks, ws, ws.deep_slots, (u32)ZH_DEEP_DEPTH(level));
+  hipLaunchKernelGGL(zh_lz_deep_kernel, dim3(grid), dim3(DT), DEEP_LDS, stream, d_descs, nblocks, ws, ws.deep_slots, depth);
   return hipGetLastError();
 }
+
+hipError_t lz_deep_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, int level, hipStream_t stream) {
+  return deep_launch_depth(d_descs, nblocks, ws, (u32)ZH_DEEP_DEPTH(level), stream);
+}
 }  // namespace zh
+
+// ---- test hooks (tests/test_gpu_deep.py, not product entry points) --------------------------------
+// The variant deep_block takes for (pre, nb, s0): DEEP_PATH_* (0 demand, 1 links + bytes in LDS,
+// 2 links in LDS, 3 everything from the slot); *segl = the demand path's segment length (else 64,
+// the full-search parse's).
+extern "C" int zh_test_deep_path(u32 pre, u32 nb, u32 s0, u32 *segl) {
+  DeepPath const dp = deep_path(pre, nb, s0);
+  if (segl) *segl = dp.demand ? dp.segl : 64u;
+  return (int)dp.path();
+}
+// The staged content bytes P and the split lz_deep_dict_tables takes for cn content bytes (0, 0:
+// no tables).
+extern "C" void zh_test_deep_split(u64 cn, u32 *P, u32 *split) { zh::deep_dict_split((size_t)cn, *P, *split); }
+// The deep matcher alone at search depth `depth` over single-block items: item i is the block
+// blk[i * blk_stride, + n[i]) (n <= ZH_BLOCK_MAX) staged behind the prefix pre[i * pre_stride,
+// + pre_n[i]) (host bytes; pre_n may be 0), both placed in device memory at byte offset align[i]
+// (0-15) past a 256-byte boundary.
+//   tables = 0: pre_n <= ZH_DEEP_PRE, no dictionary tables (dd_head null): the shape of stream
+//     history and of a multi-block frame's later blocks.  One launch over all items on
+//     min(nitems, nslots) scratch slots; nslots = 1 runs the items in order in one slot.
+//   tables = 1: the prefix is a dictionary's content (any length; its last ZH_DEEP_PRE bytes are
+//     staged): lz_deep_dict_tables on it and ZH_F_DICT | ZH_F_FIRST | ZH_F_DEEP as zh_host.cpp
+//     sets them; one launch per item (the tables are one dictionary's).
+// Copied back per item as zh_test_lz does: ZH_SEQ_CAP records, ZH_LIT_BYTES of the literal area,
+// meta {nseq, nlit, rle}.  off (may be null; one item only): the slot's off << 8 | len of the n
+// block positions -- every position on the full-search paths, the searched ones on the demand path.
+// Returns 0, 1 (HIP error) or 2 (bad arguments).
+extern "C" int zh_test_lz_deep(const u8 *pre, const u32 *pre_n, u32 pre_stride, const u8 *blk, const u32 *n, u32 blk_stride, const u32 *align,
+                               u32 nitems, u32 depth, int tables, u32 nslots, u64 *h_recs, u8 *h_lits, u32 *h_meta, u32 *h_off) {
+  if (!nitems) return 0;
+  if (!nslots || !depth || (h_off && nitems != 1)) return 2;
+  size_t pre_cap = 0;
+  for (u32 i = 0; i < nitems; i++) {
+    if (n[i] == 0 || n[i] > ZH_BLOCK_MAX || align[i] > 15 || (!tables && pre_n[i] > ZH_DEEP_PRE)) return 2;
+    pre_cap = std::max(pre_cap, (size_t)pre_n[i]);
+  }
+  size_t const pre_area = (pre_cap + 16 + 255) & ~(size_t)255, item_area = pre_area + ZH_BLOCK_MAX + 256;
+  nslots = std::min(nslots, nitems);
+  ZhBlockDesc *dd = nullptr;
+  u8 *in = nullptr, *base = nullptr, *slots = nullptr, *dstg = nullptr;
+  u32 *ctr = nullptr, *dprev = nullptr, *dhead = nullptr;
+  std::vector<ZhBlockDesc> descs(nitems);
+  int rc = 0;
+  if (zh::lz_deep_init() != hipSuccess || hipMalloc(&dd, sizeof(ZhBlockDesc) * nitems) != hipSuccess ||
+      hipMalloc(&in, item_area * nitems) != hipSuccess || hipMalloc(&base, (size_t)ZH_WS_BLOCK_BYTES * nitems) != hipSuccess ||
+      hipMalloc(&slots, ZH_DEEP_SLOT_BYTES * nslots) != hipSuccess || hipMalloc(&ctr, 4) != hipSuccess ||
+      hipMalloc(&dprev, 4u * ZH_DEEP_PRE) != hipSuccess || hipMalloc(&dhead, 4u << ZH_HASH_LOG_SHORT) != hipSuccess ||
+      hipMalloc(&dstg, ZH_DEEP_PRE + 256) != hipSuccess) {
+    rc = 1;
+  } else {
+    // (a fresh slot holds arbitrary bytes; the length caps keep them out of the result)
+    (void)hipMemset(slots, 0xA5, ZH_DEEP_SLOT_BYTES * nslots);
+    (void)hipMemset(in, 0x5A, item_area * nitems);
+    for (u32 i = 0; i < nitems; i++) {
+      u8 *const p = in + (size_t)i * item_area + align[i], *const s = in + (size_t)i * item_area + pre_area + align[i];
+      u32 const pn = (u32)std::min((size_t)pre_n[i], (size_t)ZH_DEEP_PRE);
+      if (pn) (void)hipMemcpy(p, pre + (size_t)i * pre_stride + (pre_n[i] - pn), pn, hipMemcpyHostToDevice);
+      (void)hipMemcpy(s, blk + (size_t)i * blk_stride, n[i], hipMemcpyHostToDevice);
+      ZhBlockDesc d{};
+      d.src = s;
+      d.n = n[i];
+      d.frame_size = n[i];
+      d.item = i;
+      d.flags = ZH_F_FIRST | ZH_F_LAST | ZH_F_DIRECT | ZH_F_DEEP | (tables ? ZH_F_DICT : 0u);
+      d.pre = pn ? p : nullptr;
+      d.pre_n = pn;
+      descs[i] = d;
+    }
+    (void)hipMemcpy(dd, descs.data(), sizeof(ZhBlockDesc) * nitems, hipMemcpyHostToDevice);
+    ZhWorkspace ws{};
+    ws.base = base;
+    ws.ctr = ctr;
+    ws.deep_slots = slots;
+    ws.deep_nslots = nslots;
+    if (!tables) {
+      (void)hipMemset(ctr, 0, 4);
+      if (zh::deep_launch_depth(dd, nitems, ws, depth, nullptr) != hipSuccess) rc = 1;
+    } else {
+      for (u32 i = 0; i < nitems && !rc; i++) {
+        // (the tables hash the device copy of the content's staged tail: the same bytes)
+        u32 P = 0, split = 0;
+        ZhWorkspace w1 = ws;
+        w1.base = base + (size_t)i * ZH_WS_BLOCK_BYTES;
+        if (descs[i].pre_n &&
+            zh::lz_deep_dict_tables(descs[i].pre, descs[i].pre_n, dstg, dprev, dhead, P, split, nullptr) != hipSuccess) rc = 1;
+        if (P) {
+          w1.dd_prev = dprev;
+          w1.dd_head = dhead;
+          w1.dd_pre = P;
+          w1.dd_split = split;
+        }
+        (void)hipMemset(ctr, 0, 4);
+        if (!rc && zh::deep_launch_depth(dd + i, 1, w1, depth, nullptr) != hipSuccess) rc = 1;
+        if (hipDeviceSynchronize() != hipSuccess) rc = 1;
+      }
+    }
+    if (hipDeviceSynchronize() != hipSuccess) rc = 1;
+    for (u32 i = 0; i < nitems && !rc; i++) {
+      u8 *const b = base + (size_t)i * ZH_WS_BLOCK_BYTES;
+      (void)hipMemcpy(h_recs + (size_t)i * ZH_SEQ_CAP, b, ZH_SEQ_BYTES, hipMemcpyDeviceToHost);
+      (void)hipMemcpy(h_lits + (size_t)i * ZH_LIT_BYTES, b + ZH_SEQ_BYTES, ZH_LIT_BYTES, hipMemcpyDeviceToHost);
+      (void)hipMemcpy(h_meta + 4 * i, b + ZH_SEQ_BYTES + ZH_LIT_BYTES, 16, hipMemcpyDeviceToHost);
+    }
+    if (h_off && !rc) (void)hipMemcpy(h_off, slots + SLOT_OFF, 4u * n[0], hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dd);
+  (void)hipFree(in);
+  (void)hipFree(base);
+  (void)hipFree(slots);
+  (void)hipFree(ctr);
+  (void)hipFree(dprev);
+  (void)hipFree(dhead);
+  (void)hipFree(dstg);
+  return rc;
+}

@@ -884,12 +884,15 @@ static int match_gain32(const u8 *len, const u32 *off, u32 p) {
  *     bytes wins, the nearest on ties; the walk stops early at a capped match;
  *   - LAZY2 parse from pre (libzstd ZSTD_compressBlock_lazy_generic's depth-2 rule, as
  *     orc_lz_parse_pre), no catch-up, a directly following same-offset match merged. */
-size_t orc_lz_parse_deep(const u8 *buf, u32 pre, u32 n, u32 depth, orc_seq_t *seq, u32 *last_lits) {
+/* The deep matcher's per-position matches over buf[0, n): len[p] / off[p] for p in [pre, lim), 0
+ * elsewhere (len and off hold n + 3 entries; positions below pre are chain candidates only).  The
+ * first two points of the comment above; orc_lz_parse_deep parses these. */
+void orc_deep_matches(const u8 *buf, u32 pre, u32 n, u32 depth, u8 *len, u32 *off) {
   u32 const lim = n > ZH_HASH_READ ? n - ZH_HASH_READ : 0;
   u32 *prev = malloc(sizeof(u32) * (lim + 1));
   u32 *head = calloc((size_t)1 << ZH_HASH_LOG_SHORT, sizeof(u32));
-  u8 *len = calloc(n + 3, 1);
-  u32 *off = calloc(n + 3, sizeof(u32));
+  memset(len, 0, (size_t)n + 3);
+  memset(off, 0, sizeof(u32) * ((size_t)n + 3));
   for (u32 p = 0; p < lim; p++) {
     u32 const h = zh_hash_short(rd64(buf + p));
     prev[p] = head[h]; /* q + 1, 0 = none */
@@ -909,6 +912,14 @@ size_t orc_lz_parse_deep(const u8 *buf, u32 pre, u32 n, u32 depth, orc_seq_t *se
     len[p] = (u8)best;
     off[p] = bo;
   }
+  free(prev); free(head);
+}
+
+size_t orc_lz_parse_deep(const u8 *buf, u32 pre, u32 n, u32 depth, orc_seq_t *seq, u32 *last_lits) {
+  u32 const lim = n > ZH_HASH_READ ? n - ZH_HASH_READ : 0;
+  u8 *len = malloc((size_t)n + 3);
+  u32 *off = malloc(sizeof(u32) * ((size_t)n + 3));
+  orc_deep_matches(buf, pre, n, depth, len, off);
   size_t ns = 0;
   u32 p = pre, anchor = pre;
   while (p < lim) {
@@ -922,7 +933,7 @@ size_t orc_lz_parse_deep(const u8 *buf, u32 pre, u32 n, u32 depth, orc_seq_t *se
     anchor = p;
   }
   *last_lits = n - anchor;
-  free(prev); free(head); free(len); free(off);
+  free(len); free(off);
   return ns;
 }
 /* Miss skip (libzstd dfast's kSearchStrength idea at window granularity): the matcher and the
