@@ -6,7 +6,8 @@ compress_batch / decompress_batch), ``HybridEngine``, module-level ``compress``,
 ``decompress``, ``compress_batch``, ``decompress_batch``, ``hybrid_compress``,
 ``hybrid_decompress``, ``validate_compressed_data``, ``estimate_compressed_size``,
 ``is_cuda_available``, ``get_cuda_device_info`` and the level constants -- plus a
-``StreamingManager`` and the dictionary / batched device entries, all over the
+``StreamingManager``, the dictionary / batched device entries and adaptive level selection
+(``analyze_batch``, ``select_level``, ``is_compressible``, ``compress_batch_adaptive``), all over the
 library's C ABI (include/cuda_zstd_capi.h).  Host inputs (bytes, bytearray, numpy)
 give host ``bytes`` back, as the reference's binding does; torch device tensors stay
 on the device.  PyTorch is only used for device memory and streams.
@@ -114,6 +115,10 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_seekable_read_get_temp_size": (sz, [sz, sz]),
             "cuda_zstd_seekable_read_get_temp_size_jobs": (sz, [sz, sz, sz]),
             "cuda_zstd_seekable_read": (i, [vp, vp, sz, ctypes.c_ulonglong, sz, vp, psz, i, vp, sz, vp]),
+            "cuda_zstd_adaptive_get_temp_size": (sz, [sz]),
+            "cuda_zstd_adaptive_analyze_batch_async": (i, [vp, vp, sz, sz, i, vp, vp, vp, sz, vp]),
+            "cuda_zstd_adaptive_select_level": (i, [vp, sz, sz, i, vp, vp]),
+            "cuda_zstd_adaptive_finalize_host": (i, [ctypes.POINTER(ctypes.c_uint), ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, i, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -799,6 +804,114 @@ class SeekableReader:
 
     def read_all(self, verify: bool = False, stream=None):
         return self.read(0, self.size, verify, stream)
+
+
+# Adaptive level selection (cuda_zstd_adaptive_*; reference adaptive::AdaptiveLevelSelector,
+# include/cuda_zstd_adaptive.h): which level a chunk is worth, from statistics of its first
+# sample_bytes bytes and the reference's decision tree.
+SPEED, BALANCED, RATIO = 0, 1, 2  # AdaptivePreference
+HAS_PATTERNS, IS_RANDOM = 1, 2  # bits of a statistics record's flags
+
+
+class AdaptiveStats(ctypes.Structure):
+    """cuda_zstd_adaptive_stats_t."""
+    _fields_ = [("sample_size", ctypes.c_uint), ("repeated_pairs", ctypes.c_uint), ("max_run_length", ctypes.c_uint),
+                ("pattern_score", ctypes.c_uint), ("unique_bytes", ctypes.c_uint), ("flags", ctypes.c_uint), ("entropy", ctypes.c_float),
+                ("repetition_ratio", ctypes.c_float), ("compressibility", ctypes.c_float), ("level", ctypes.c_int)]
+
+
+def _stats_dict(s: AdaptiveStats) -> dict:
+    d = {name: getattr(s, name) for name, _ in AdaptiveStats._fields_}
+    d["has_patterns"], d["is_random"] = bool(s.flags & HAS_PATTERNS), bool(s.flags & IS_RANDOM)
+    return d
+
+
+def adaptive_stats_numpy(stats):
+    """The stats tensor of analyze_batch as a structured numpy array, one record per chunk, with
+    the fields of cuda_zstd_adaptive_stats_t (copies to the host: waits for the device)."""
+    import numpy as np
+
+    dt = np.dtype([(name, {ctypes.c_uint: "<u4", ctypes.c_float: "<f4", ctypes.c_int: "<i4"}[t]) for name, t in AdaptiveStats._fields_])
+    return stats.cpu().numpy().view(dt).reshape(-1)
+
+
+def analyze_batch_device(d_ptrs, d_sizes, preference: int = BALANCED, sample_bytes: int = 65536, stream=None):
+    """analyze_batch over device arrays (int64 tensors of chunk addresses and sizes): one
+    stream-ordered launch for the whole batch (cuda_zstd_adaptive_analyze_batch_async)."""
+    torch = _torch()
+    n = d_ptrs.numel()
+    s = stream if stream is not None else torch.cuda.current_stream()
+    with torch.cuda.stream(s):  # the outputs and the temp buffer are ordered on the same stream
+        levels = torch.empty(n, dtype=torch.int32, device=d_ptrs.device)
+        stats = torch.empty(n * ctypes.sizeof(AdaptiveStats), dtype=torch.uint8, device=d_ptrs.device)
+        temp = torch.empty(max(lib().cuda_zstd_adaptive_get_temp_size(n), 4), dtype=torch.uint8, device=d_ptrs.device)
+        rc = lib().cuda_zstd_adaptive_analyze_batch_async(d_ptrs.data_ptr(), d_sizes.data_ptr(), n, sample_bytes, preference, stats.data_ptr(),
+                                                          levels.data_ptr(), temp.data_ptr(), temp.numel(), s.cuda_stream)
+    if rc:
+        raise ZstdError(rc, "cuda_zstd_adaptive_analyze_batch_async")
+    return levels, stats
+
+
+def analyze_batch(chunks: Sequence, preference: int = BALANCED, sample_bytes: int = 65536, stream=None):
+    """Level and statistics of every chunk (uint8 device tensors) -> (levels, stats): an int32
+    device tensor and a device byte tensor of cuda_zstd_adaptive_stats_t records
+    (adaptive_stats_numpy reads them).  Nothing waits for the device: the chunk addresses go up
+    from pinned memory, and the results are valid in stream order."""
+    torch = _torch()
+    ins = [c.contiguous().view(torch.uint8) for c in chunks]
+    n = len(ins)
+    s = stream if stream is not None else torch.cuda.current_stream()
+    table = torch.tensor([[t.data_ptr() for t in ins], [t.numel() for t in ins]], dtype=torch.int64).reshape(2, n)
+    with torch.cuda.stream(s):
+        d_table = table.pin_memory().to("cuda", non_blocking=True)
+        for t in ins:
+            t.record_stream(s)
+    return analyze_batch_device(d_table[0], d_table[1], preference, sample_bytes, s)
+
+
+def select_level(data, preference: int = BALANCED, sample_bytes: int = 65536, stream=None) -> dict:
+    """cuda_zstd_adaptive_select_level on one buffer (a device tensor, or host bytes / numpy,
+    which are uploaded): the fields of cuda_zstd_adaptive_stats_t, `level` among them, plus
+    has_patterns / is_random.  Waits for the result."""
+    torch = _torch()
+    t = _to_device(data) if _is_host(data) else data.contiguous().view(torch.uint8)
+    out = AdaptiveStats()
+    rc = lib().cuda_zstd_adaptive_select_level(t.data_ptr() if t.numel() else None, t.numel(), sample_bytes, preference, ctypes.byref(out),
+                                               _stream_ptr(stream))
+    if rc:
+        raise ZstdError(rc, "cuda_zstd_adaptive_select_level")
+    return _stats_dict(out)
+
+
+def is_compressible(data):
+    """(compressible, estimated_ratio): compressibility > 0.3 and 1 + 3 * compressibility
+    (reference adaptive::is_compressible)."""
+    c = select_level(data)["compressibility"]
+    return c > 0.3, 1.0 + 3.0 * c
+
+
+def adaptive_finalize_host(hist, repeated_pairs: int, max_run_length: int, pattern_score: int, preference: int = BALANCED) -> dict:
+    """The derived values and the level from integer statistics, on the host
+    (cuda_zstd_adaptive_finalize_host: the function the device runs); needs no GPU."""
+    h = (ctypes.c_uint * 256)(*[int(v) for v in hist])
+    out = AdaptiveStats()
+    rc = lib().cuda_zstd_adaptive_finalize_host(h, sum(h), repeated_pairs, max_run_length, pattern_score, preference, ctypes.byref(out))
+    if rc:
+        raise ZstdError(rc, "cuda_zstd_adaptive_finalize_host")
+    return _stats_dict(out)
+
+
+def compress_batch_adaptive(chunks: Sequence, preference: int = BALANCED, stream=None):
+    """Compress every chunk (uint8 device tensors) at the level the selector gives it ->
+    (frames, levels): one analysis of the batch, one copy of the levels to the host, then one
+    Manager(level).compress_batch per distinct level; frames in input order."""
+    levels = [int(v) for v in analyze_batch(chunks, preference, stream=stream)[0].cpu()]
+    frames = [None] * len(chunks)
+    for level in sorted(set(levels)):
+        idx = [k for k, v in enumerate(levels) if v == level]
+        for k, f in zip(idx, Manager(level).compress_batch([chunks[k] for k in idx], stream)):
+            frames[k] = f
+    return frames, levels
 
 
 def hybrid_compress(data, level: int = 3) -> bytes:

@@ -251,6 +251,38 @@ size_t cuda_zstd_seekable_read_get_temp_size_jobs(size_t num_frames, size_t max_
 int cuda_zstd_seekable_read(nvcomp_zstd_batch_manager_t *mgr, const void *d_stream, size_t size, unsigned long long offset, size_t length,
                             void *d_out, size_t *written, int verify_checksums, void *d_temp, size_t temp_bytes, hipStream_t stream);
 
+/* ---------------- adaptive level selection ----------------
+ * C counterpart of include/cuda_zstd_adaptive.h (reference adaptive::AdaptiveLevelSelector), for
+ * whole batches: which level a chunk is worth, from statistics of its first
+ * min(size, sample_bytes) bytes -- byte histogram and entropy, equal neighbours, longest run
+ * (saturating at 256), short-period pattern score -- and the reference's decision tree.
+ * preference: 0 speed, 1 balanced, 2 ratio.
+ *
+ * analyze_batch_async: stream-ordered; d_ptrs, d_sizes, d_stats, d_levels and d_temp are DEVICE
+ * arrays, nothing is allocated or synchronised, results are valid once `stream` reaches this
+ * point.  d_levels[i] = the level of chunk i; d_stats[i] (d_stats may be NULL) its statistics.  A
+ * chunk of size 0 gets all-zero statistics and level 3.  d_temp: 4-byte aligned,
+ * cuda_zstd_adaptive_get_temp_size(num_chunks) bytes.  num_chunks == 0 does nothing.
+ * select_level: one device buffer; waits for `stream` and fills *h_out (host).
+ * finalize_host: the derived values and the level from integer statistics computed elsewhere
+ * (the function the device uses); host only, needs no GPU.
+ * Codes: 2 for a null pointer, a preference outside 0..2, sample_bytes == 0, select_level's
+ * size == 0, a misaligned d_temp or a batch too large for one launch (num_chunks x 16 KiB tiles of
+ * sample_bytes over 2^31 - 1); 7 for a short temp; 4 on a HIP error. */
+typedef struct {
+  unsigned sample_size, repeated_pairs, max_run_length, pattern_score, unique_bytes, flags; /* bit0 has_patterns, bit1 is_random */
+  float entropy, repetition_ratio, compressibility;
+  int level;
+} cuda_zstd_adaptive_stats_t;
+size_t cuda_zstd_adaptive_get_temp_size(size_t num_chunks);
+int cuda_zstd_adaptive_analyze_batch_async(const void *const *d_ptrs, const size_t *d_sizes, size_t num_chunks, size_t sample_bytes,
+                                           int preference, cuda_zstd_adaptive_stats_t *d_stats /* may be NULL */, int *d_levels,
+                                           void *d_temp, size_t temp_bytes, hipStream_t stream);
+int cuda_zstd_adaptive_select_level(const void *d_data, size_t size, size_t sample_bytes, int preference,
+                                    cuda_zstd_adaptive_stats_t *h_out, hipStream_t stream);
+int cuda_zstd_adaptive_finalize_host(const unsigned *hist256, unsigned sample_size, unsigned repeated_pairs, unsigned max_run_length,
+                                     unsigned pattern_score, int preference, cuda_zstd_adaptive_stats_t *out);
+
 /* ---------------- library info ---------------- */
 const char *cuda_zstd_hip_version(void);
 /* Per-kernel timing with HIP events recorded on the launch stream (bench.py roofline).
