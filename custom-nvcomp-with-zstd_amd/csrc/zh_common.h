@@ -33,6 +33,8 @@ enum : u32 {
   ZH_F_DICT = 16u,     // dictionary frame: Dictionary_ID in the header, repcodes start unknown
   ZH_F_DEEP = 32u,     // level >= ZH_DEEP_LEVEL (zh_lz_deep.hip): a dictionary frame's first block is staged
                        // behind the last ZH_DEEP_PRE content bytes
+  ZH_F_LDM = 64u,      // one-sequence block of a long-distance match (zh_ldm.hip): n = 0, so K1-K4 skip the slot; its
+                       // bytes and staged size are already written, and the gather copies them like any block's
 };
 
 // Per-block workspace carved from the caller's temp buffer.

@@ -298,7 +298,11 @@ struct WsLayout {
   size_t descs, items, blk_size, item_size, item_status, staging, counter, blocks, deep, deep_slots, total;
   // deep: a level >= ZH_DEEP_LEVEL call (the deep matcher's scratch slots, one per persistent
   // workgroup, follow the block areas)
-  static WsLayout make(size_t nblocks, size_t nitems, bool staged, bool deep = false) {
+  // ldm_cells > 0: a long-distance-matching call (zh_ldm.hip) over one frame of that many cells
+  // -- nblocks is then three slots per cell -- with its table of 2^ldm_tlog entries, the per-cell
+  // sample lists and the per-cell records behind everything else
+  size_t ldm_table, ldm_skey, ldm_sslot, ldm_scount, ldm_rec;
+  static WsLayout make(size_t nblocks, size_t nitems, bool staged, bool deep = false, size_t ldm_cells = 0, u32 ldm_tlog = 0) {
     WsLayout L{};
     size_t o = 0;
     L.descs = o; o = align256(o + nblocks * sizeof(ZhBlockDesc));
@@ -311,6 +315,13 @@ struct WsLayout {
     L.blocks = o; o = align256(o + nblocks * (size_t)ZH_WS_BLOCK_BYTES);
     L.deep_slots = deep ? std::min(nblocks, (size_t)ZH_DEEP_SLOTS_MAX) : 0;
     L.deep = o; o = align256(o + L.deep_slots * ZH_DEEP_SLOT_BYTES);
+    if (ldm_cells) {
+      L.ldm_table = o; o = align256(o + (sizeof(u64) << ldm_tlog));
+      L.ldm_skey = o; o = align256(o + ldm_cells * ZH_LDM_CELL_SAMPLES * sizeof(u64));
+      L.ldm_sslot = o; o = align256(o + ldm_cells * ZH_LDM_CELL_SAMPLES * sizeof(u32));
+      L.ldm_scount = o; o = align256(o + ldm_cells * sizeof(u32));
+      L.ldm_rec = o; o = align256(o + ldm_cells * sizeof(ZhLdmRecord));
+    }
     L.total = o + 256;  // slack for base alignment
     return L;
   }
@@ -323,6 +334,16 @@ inline bool split_dict_of(bool has_dict, int level) { return has_dict && level <
 inline size_t blocks_of(size_t n, bool split_dict = false) {
   size_t const bs = block_size_of(n, split_dict);
   return (n + bs - 1) / bs;
+}
+
+// Long-distance matching applies to a frame of n bytes: asked for, no dictionary or history, a
+// window that reaches past one block, more than one device block, 32-bit positions
+inline bool ldm_applies(const CompressionConfig &c, size_t n, bool has_dict) {
+  return c.enable_ldm && !has_dict && c.window_log >= ZH_HIST_WINDOW_LOG && n > (size_t)ZH_BLOCK_MAX && n <= ZH_LDM_MAX_FRAME;
+}
+inline WsLayout ldm_layout(const CompressionConfig &c, size_t n) {
+  size_t const cells = blocks_of(n);
+  return WsLayout::make(3 * cells, 1, true, c.level >= ZH_DEEP_LEVEL, cells, zh_ldm_table_log(n, c.ldm_hash_log));
 }
 
 // Decoder workspace (zh_decode.hip): per-item arrays (host-array entry points upload
@@ -568,10 +589,19 @@ class ZstdBatchManager::Impl {
     return pinned;
   }
 
+  // The long-distance finder over one frame (layout L = ldm_layout): descriptors, one-sequence
+  // blocks, staged sizes and records of all its cells
+  hipError_t launch_ldm(const WsLayout &L, u8 *base, const void *src, size_t n, size_t cells, u32 flags, hipStream_t stream) {
+    return zh::ldm_launch((const u8 *)src, n, (u32)cells, zh_ldm_table_log(n, config.ldm_hash_log), zh_ldm_max_dist(config.window_log), flags,
+                          (u64 *)(base + L.ldm_table), (u64 *)(base + L.ldm_skey), (u32 *)(base + L.ldm_sslot), (u32 *)(base + L.ldm_scount),
+                          (ZhBlockDesc *)(base + L.descs), base + L.staging, (u32 *)(base + L.blk_size), (ZhLdmRecord *)(base + L.ldm_rec),
+                          stream);
+  }
+
   // Run the device pipeline over a list of frames given as host arrays.
   // out_sizes: in = capacity, out = bytes; statuses out.
   Status run(const void *const *in_ptrs, const size_t *in_sizes, size_t count, void *const *out_ptrs, size_t *out_sizes, Status *statuses,
-             void *temp, size_t temp_size, hipStream_t stream, const DevDict *dd = nullptr) {
+             void *temp, size_t temp_size, hipStream_t stream, const DevDict *dd = nullptr, bool allow_ldm = false) {
     Status s = ensure_kernels();
     if (s != Status::SUCCESS) return s;
     size_t nblocks = 0;
@@ -583,7 +613,13 @@ class ZstdBatchManager::Impl {
       nblocks += nb;
       staged |= nb > 1;
     }
-    WsLayout L = WsLayout::make(nblocks, count, staged, config.level >= ZH_DEEP_LEVEL);
+    // long-distance matching (allow_ldm: compress() of one frame, whose workspace query sized for
+    // it; the batch entries never ask): three slots per cell, the cells' descriptors come from
+    // zh_ldm_cell_kernel instead of the loop below
+    bool const ldm = allow_ldm && count == 1 && ldm_applies(config, in_sizes[0], has_dict);
+    size_t const ldm_cells = ldm ? nblocks : 0;
+    if (ldm) nblocks *= 3;
+    WsLayout L = ldm ? ldm_layout(config, in_sizes[0]) : WsLayout::make(nblocks, count, staged, config.level >= ZH_DEEP_LEVEL);
     if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
     u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
 
@@ -595,22 +631,22 @@ class ZstdBatchManager::Impl {
     ZhItemDesc *hi = (ZhItemDesc *)(h + L.items);
     u8 *staging = base + L.staging;
     size_t b = 0;
+    u32 const frame_flags = (config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY ? ZH_F_CHECKSUM : 0u) |
+                            (config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u);
     for (size_t i = 0; i < count; i++) {
       bool const sd = split_dict_of(has_dict, config.level);
-      size_t const n = in_sizes[i], nb = blocks_of(n, sd), bs = block_size_of(n, sd);
+      size_t const n = in_sizes[i], nb = ldm ? 0 : blocks_of(n, sd), bs = block_size_of(n, sd);
       hi[i].dst = (u8 *)out_ptrs[i];
       hi[i].cap = out_sizes[i];
       hi[i].first_block = (u32)b;
-      hi[i].nblocks = (u32)nb;
+      hi[i].nblocks = (u32)(ldm ? nblocks : nb);
       for (size_t k = 0; k < nb; k++, b++) {
         ZhBlockDesc &d = hd[b];
         d.src = (const u8 *)in_ptrs[i] + k * bs;
         d.frame_size = n;
         d.n = (u32)std::min(bs, n - k * bs);
         d.item = (u32)i;
-        d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) |
-                  (config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY ? ZH_F_CHECKSUM : 0u) |
-                  (config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u);
+        d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) | frame_flags;
         set_dict_block(d, dd, k == 0, hist, config.level >= ZH_DEEP_LEVEL);
         if (nb == 1) {
           d.dst = (u8 *)out_ptrs[i];
@@ -621,7 +657,12 @@ class ZstdBatchManager::Impl {
         }
       }
     }
-    if (hipMemcpyAsync(base, h, up_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+    if (ldm) {  // the item descriptor only; the finder writes the block descriptors, stream-ordered in front of K1
+      if (hipMemcpyAsync(base + L.items, h + L.items, up_bytes - L.items, hipMemcpyHostToDevice, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+      if (launch_ldm(L, base, in_ptrs[0], in_sizes[0], ldm_cells, frame_flags, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+    } else if (hipMemcpyAsync(base, h, up_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
+      return Status::ERROR_CUDA_ERROR;
+    }
     ZhWorkspace ws{base + L.blocks, (u32 *)(base + L.counter), dd && dd->tabs_P ? dd->tabs : nullptr, dd ? dd->tabs_P : 0u};
     set_deep_dict(ws, dd);
     ws.deep_slots = L.deep_slots ? base + L.deep : nullptr;
@@ -645,8 +686,8 @@ class ZstdBatchManager::Impl {
       stats.input_bytes += in_sizes[i];
       if (st == Status::SUCCESS) stats.output_bytes += h_size[i];
     }
-    stats.blocks_processed += nblocks;
-    stats.num_blocks += nblocks;
+    stats.blocks_processed += ldm ? ldm_cells : nblocks;  // (cells: how many of the three slots a cell fills stays on the device)
+    stats.num_blocks += ldm ? ldm_cells : nblocks;
     return all_ok ? Status::SUCCESS : Status::ERROR_GENERIC;
   }
 
@@ -746,7 +787,32 @@ CompressionConfig ZstdBatchManager::get_config() const { return pimpl_->config; 
 // sized for the dictionary layout as well (a per-call dictionary is only known at compress())
 size_t ZstdBatchManager::get_compress_temp_size(size_t n) const {
   size_t nb = std::max<size_t>(1, blocks_of(n, true));
-  return WsLayout::make(nb, 1, nb > 1, pimpl_->config.level >= ZH_DEEP_LEVEL).total;
+  size_t const plain = WsLayout::make(nb, 1, nb > 1, pimpl_->config.level >= ZH_DEEP_LEVEL).total;
+  // long-distance matching: three slots per cell, the table and the sample lists (a dictionary
+  // given at compress() switches it off: the plain layout must fit too)
+  return ldm_applies(pimpl_->config, n, false) ? std::max(plain, ldm_layout(pimpl_->config, n).total) : plain;
+}
+
+Status ZstdBatchManager::ldm_plan(const void *d_src, size_t size, unsigned int *host_records, size_t capacity, size_t *num_records, void *temp,
+                                  size_t temp_size, hipStream_t stream) {
+  std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
+  if (!d_src || !num_records || (capacity && !host_records) || !temp) return Status::ERROR_INVALID_PARAMETER;
+  *num_records = 0;
+  if (!ldm_applies(pimpl_->config, size, pimpl_->active() != nullptr)) return Status::SUCCESS;
+  if (!is_device_ptr(d_src)) return Status::ERROR_INVALID_PARAMETER;
+  Status s = ensure_kernels();
+  if (s != Status::SUCCESS) return s;
+  WsLayout const L = ldm_layout(pimpl_->config, size);
+  size_t const cells = blocks_of(size);
+  if (temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
+  if (capacity < cells) return Status::ERROR_BUFFER_TOO_SMALL;
+  u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
+  if (pimpl_->launch_ldm(L, base, d_src, size, cells, 0, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+  if (hipMemcpyAsync(host_records, base + L.ldm_rec, cells * sizeof(ZhLdmRecord), hipMemcpyDeviceToHost, stream) != hipSuccess)
+    return Status::ERROR_CUDA_ERROR;
+  if (hipStreamSynchronize(stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+  *num_records = cells;
+  return Status::SUCCESS;
 }
 // one slot for 128 KiB blocks (reference src/cuda_zstd_manager.cu:1373-1408 also sizes for one block)
 size_t ZstdBatchManager::get_decompress_temp_size(size_t) const { return DecLayout::make(1, DecLayout::kBlockMax).total; }
@@ -776,7 +842,7 @@ Status ZstdBatchManager::compress(const void *in, size_t n, void *out, size_t *o
     const void *ip[1] = {in};
     void *opv[1] = {out};
     size_t sz[1] = {n};
-    st = pimpl_->run(ip, sz, 1, opv, out_size, &item, temp, temp_size, stream, dd);
+    st = pimpl_->run(ip, sz, 1, opv, out_size, &item, temp, temp_size, stream, dd, true);
     if (st == Status::ERROR_GENERIC) st = item;
   }
   pimpl_->stats.compression_time_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -813,7 +879,7 @@ Status ZstdBatchManager::compress_with_history(const void *in, size_t n, void *o
   void *opv[1] = {out};
   size_t sz[1] = {n};
   auto t0 = std::chrono::steady_clock::now();
-  Status st = pimpl_->run(ip, sz, 1, opv, out_size, &item, temp, temp_size, stream, hist_n ? &view : pimpl_->active());
+  Status st = pimpl_->run(ip, sz, 1, opv, out_size, &item, temp, temp_size, stream, hist_n ? &view : pimpl_->active(), true);
   if (st == Status::ERROR_GENERIC) st = item;
   pimpl_->stats.compression_time_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return st;
@@ -2485,6 +2551,45 @@ unsigned int cuda_zstd_hybrid_query_routing(cuda_zstd_hybrid_engine_t *e, size_t
   return (unsigned)e->engine->query_routing(n, (DataLocation)il, (DataLocation)ol, is_c != 0);
 }
 
+// Long-distance matching on a manager.  enable != 0: window_log / hash_log 0 select
+// 27 / 20, what `zstd --long` takes.  enable == 0: matching off; a window_log / hash_log of 0 leaves
+// the manager's value alone, another value is stored (the frame a caller compares against).
+// Returns 2 for a window_log outside 16..31; the table size is clamped to 2^10..2^30 where it is used.
+int cuda_zstd_set_long_distance(cuda_zstd_manager_t *m, int enable, unsigned window_log, unsigned hash_log) {
+  if (!m || !m->manager) return c_err(Status::ERROR_INVALID_PARAMETER);
+  CompressionConfig c = m->manager->get_config();
+  if (enable && window_log == 0) window_log = 27;
+  if (enable && hash_log == 0) hash_log = 20;
+  if (window_log && (window_log < ZH_HIST_WINDOW_LOG || window_log > MAX_WINDOW_LOG)) return c_err(Status::ERROR_INVALID_PARAMETER);
+  c.enable_ldm = enable != 0;
+  if (window_log) c.window_log = window_log;
+  if (hash_log) c.ldm_hash_log = hash_log;
+  return c_err(m->manager->configure(c));
+}
+// Content checksum of the manager's frames (0: none, the default)
+int cuda_zstd_set_checksum(cuda_zstd_manager_t *m, int enable) {
+  if (!m || !m->manager) return c_err(Status::ERROR_INVALID_PARAMETER);
+  CompressionConfig c = m->manager->get_config();
+  c.checksum = enable ? ChecksumPolicy::COMPUTE_NO_VERIFY : ChecksumPolicy::NO_COMPUTE_NO_VERIFY;
+  return c_err(m->manager->configure(c));
+}
+// The finder's per-cell records {seg_start, seg_len, distance} (u32 each) for compress() of this
+// device buffer; returns the number of records (cells), 0 when long-distance matching does not
+// apply to the buffer, or -1 on error (capacity in records too small, workspace too small, ...)
+long long cuda_zstd_hip_ldm_plan(cuda_zstd_manager_t *m, const void *d_src, size_t size, unsigned int *host_records, size_t capacity,
+                                 void *workspace, size_t workspace_size, hipStream_t stream) {
+  if (!m || !m->manager) return -1;
+  size_t n = 0;
+  Status const s = m->manager->ldm_plan(d_src, size, host_records, capacity, &n, workspace, workspace_size, stream);
+  if (s != Status::SUCCESS) { (void)c_err(s); return -1; }
+  return (long long)n;
+}
+// HIP events around the finder's two kernels: on = 1 starts recording; on = 0 stops and stores the
+// summed milliseconds of the launches since then
+void cuda_zstd_hip_ldm_profile(int on, double *ms) {
+  double const t = zh::ldm_profile(on != 0);
+  if (ms) *ms = t;
+}
 void cuda_zstd_hip_profile_enable(int on) { zh::profile_enable(on != 0); }
 int cuda_zstd_hip_profile_collect(double *ms3) { return zh::profile_collect(ms3); }
 

@@ -1,6 +1,7 @@
 // zh_launch.h — host-side entry points into the device pipeline (K1 lz, K2 entropy, K3 gather).
 #pragma once
 #include "zh_common.h"
+#include "zh_ldm.h"
 
 // Per-item bookkeeping for frames that span several device blocks.
 struct ZhItemDesc {
@@ -59,4 +60,8 @@ int profile_collect(double *totals);
 hipError_t launch_plan(const void *const *d_in_ptrs, const size_t *d_in_sizes, u32 nitems, u32 bpi, void *const *d_out_ptrs, u64 out_cap,
                        u8 *staging, ZhBlockDesc *d_descs, ZhItemDesc *d_items, u64 *d_item_size, u32 *d_item_status, u32 extra_flags,
                        const u8 *dict, u32 dict_n, u32 dict_id, u32 hist, hipStream_t stream);
+// Long-distance matching (zh_ldm.hip): index + per-cell split of one frame, three descriptor slots per cell
+hipError_t ldm_launch(const u8 *src, u64 size, u32 ncells, u32 table_log, u32 max_dist, u32 flags, u64 *table, u64 *skey, u32 *sslot,
+                      u32 *scount, ZhBlockDesc *descs, u8 *staging, u32 *blk_size, ZhLdmRecord *rec, hipStream_t stream);
+double ldm_profile(bool on);
 }  // namespace zh

@@ -84,7 +84,7 @@ extern "C" __global__ __launch_bounds__(256) void zh_gather_kernel(const ZhItemD
                                                                     const u32 *__restrict__ blk_size, u64 *item_size, u32 *item_status) {
   u32 const b = blockIdx.x, tid = threadIdx.x;
   ZhBlockDesc const d = descs[b];
-  if (d.n == 0) return;
+  if (d.n == 0 && !(d.flags & ZH_F_LDM)) return;
   ZhItemDesc const id = items[d.item];
   if (id.nblocks <= 1) return;
   u32 const k = b - id.first_block;

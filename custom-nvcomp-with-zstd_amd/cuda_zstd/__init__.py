@@ -115,6 +115,10 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_seekable_read_get_temp_size": (sz, [sz, sz]),
             "cuda_zstd_seekable_read_get_temp_size_jobs": (sz, [sz, sz, sz]),
             "cuda_zstd_seekable_read": (i, [vp, vp, sz, ctypes.c_ulonglong, sz, vp, psz, i, vp, sz, vp]),
+            "cuda_zstd_set_long_distance": (i, [vp, i, ctypes.c_uint, ctypes.c_uint]),
+            "cuda_zstd_set_checksum": (i, [vp, i]),
+            "cuda_zstd_hip_ldm_plan": (ctypes.c_longlong, [vp, vp, sz, vp, sz, vp, sz, vp]),
+            "cuda_zstd_hip_ldm_profile": (None, [i, ctypes.POINTER(ctypes.c_double)]),
             "cuda_zstd_adaptive_get_temp_size": (sz, [sz]),
             "cuda_zstd_adaptive_analyze_batch_async": (i, [vp, vp, sz, sz, i, vp, vp, vp, sz, vp]),
             "cuda_zstd_adaptive_select_level": (i, [vp, sz, sz, i, vp, vp]),
@@ -193,12 +197,21 @@ class Manager:
 
     Device tensors in -> device tensors out; host bytes / numpy in -> bytes out."""
 
-    def __init__(self, level: int = 3):
+    def __init__(self, level: int = 3, long_distance=False, hash_log: int = 0, checksum: bool = False):
+        """long_distance: True = long-distance matching with a 2^27 window (`zstd --long`), an int =
+        that window log (16..31); it applies to compress() of one buffer over 64 KiB."""
         self.level = level
         self._h = lib().cuda_zstd_create_manager(level)
         if not self._h:
             raise ZstdError(INVALID, "cuda_zstd_create_manager")
         self._ws = None
+        if long_distance:  # (False, None and 0: off)
+            rc = lib().cuda_zstd_set_long_distance(self._h, 1, 0 if long_distance is True else int(long_distance), hash_log)
+            if rc:
+                self.close()
+                raise ZstdError(rc, "cuda_zstd_set_long_distance")
+        if checksum:
+            lib().cuda_zstd_set_checksum(self._h, 1)
 
     def close(self):
         if self._h:
@@ -246,6 +259,27 @@ class Manager:
         if rc:
             raise ZstdError(rc, "cuda_zstd_compress")
         return out[: size.value]
+
+    def workspace_size(self, n: int) -> int:
+        """Workspace bytes compress() of n bytes needs."""
+        return lib().cuda_zstd_get_compress_workspace_size(self._h, n)
+
+    def ldm_plan(self, data, stream=None):
+        """The long-distance finder's decision for compress(data): a numpy uint32 array [cells, 3] of
+        (seg_start, seg_len, distance) per 32 KiB cell, seg_len 0 = not split; no rows when
+        long-distance matching does not apply."""
+        import numpy as np
+
+        torch = _torch()
+        data = (_to_device(data) if _is_host(data) else data).contiguous().view(torch.uint8)
+        n = data.numel()
+        cells = (n + 32767) // 32768
+        rec = np.zeros((max(cells, 1), 3), dtype=np.uint32)
+        ws = self._workspace(self.workspace_size(n))
+        got = lib().cuda_zstd_hip_ldm_plan(self._h, data.data_ptr(), n, rec.ctypes.data, cells, ws.data_ptr(), ws.numel(), _stream_ptr(stream))
+        if got < 0:
+            raise ZstdError(INVALID, "cuda_zstd_hip_ldm_plan")
+        return rec[:got]
 
     def compress_batch(self, chunks: Sequence, stream=None) -> List:
         """ZstdBatchManager::compress_batch over a list of uint8 device tensors (host inputs:
@@ -699,8 +733,13 @@ class HybridEngine:
         raise ZstdError(TOO_SMALL, "hybrid decompress")
 
 
-def compress(data, level: int = 3, stream=None):
-    return Manager(level).compress(data, stream)
+def compress(data, level: int = 3, stream=None, long_distance=False):
+    return Manager(level, long_distance=long_distance).compress(data, stream)
+
+
+def ldm_plan(data, window_log: int = 27, hash_log: int = 20, stream=None):
+    """Manager.ldm_plan with long-distance matching at that window and table size."""
+    return Manager(3, long_distance=window_log, hash_log=hash_log).ldm_plan(data, stream)
 
 
 def compress_batch(chunks, level: int = 3, stream=None):

@@ -283,6 +283,29 @@ int cuda_zstd_adaptive_select_level(const void *d_data, size_t size, size_t samp
 int cuda_zstd_adaptive_finalize_host(const unsigned *hist256, unsigned sample_size, unsigned repeated_pairs, unsigned max_run_length,
                                      unsigned pattern_score, int preference, cuda_zstd_adaptive_stats_t *out);
 
+/* ---------------- long-distance matching (INTEGRATION.md for what ignores it) ----------------
+ * With it on, cuda_zstd_compress of one buffer of more than 64 KiB finds repeats further back than
+ * the 64 KiB its block matcher sees (up to 2^window_log bytes, at most 2^29 - 4) and writes each as a
+ * block of its own; cuda_zstd_get_compress_workspace_size grows accordingly (three block slots per
+ * 32 KiB plus the table).  enable != 0: window_log / hash_log 0 select 27 / 20 (`zstd --long`).
+ * enable == 0: matching off; a window_log / hash_log of 0 leaves the manager's value alone, another
+ * value is stored, and frames and workspace sizes are what a manager with that window gives without
+ * this feature.  Returns 2 for a window_log outside 16..31; the table size is clamped to
+ * 2^10..2^30.  Batch, dictionary and streaming entry points ignore it. */
+int cuda_zstd_set_long_distance(cuda_zstd_manager_t *manager, int enable, unsigned window_log, unsigned hash_log);
+/* Content checksum on the manager's frames (0: none, the default). */
+int cuda_zstd_set_checksum(cuda_zstd_manager_t *manager, int enable);
+/* Inspection: the finder's decision per 32 KiB cell of a device buffer, as cuda_zstd_compress would
+ * take it: host_records[3 i .. 3 i + 2] = {seg_start, seg_len, distance} (seg_len 0: the cell is not
+ * split).  capacity in records; workspace as for cuda_zstd_compress.  Returns the number of cells,
+ * 0 when long-distance matching does not apply to the buffer (off, <= 64 KiB, a dictionary is
+ * set, over 4 GiB), -1 on error. */
+long long cuda_zstd_hip_ldm_plan(cuda_zstd_manager_t *manager, const void *d_src, size_t size, unsigned int *host_records, size_t capacity,
+                                 void *workspace, size_t workspace_size, hipStream_t stream);
+/* HIP events around the finder's two kernels: on != 0 starts recording; on == 0 stops and stores the
+ * summed milliseconds of the launches since then in *ms (optional). */
+void cuda_zstd_hip_ldm_profile(int on, double *ms);
+
 /* ---------------- library info ---------------- */
 const char *cuda_zstd_hip_version(void);
 /* Per-kernel timing with HIP events recorded on the launch stream (bench.py roofline).

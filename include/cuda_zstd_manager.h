@@ -118,6 +118,14 @@ class ZstdBatchManager : public ZstdManager {
   Status decompress_with_history(const void *compressed_data, size_t compressed_size, void *uncompressed_data, size_t *uncompressed_size,
                                  void *temp_workspace, size_t temp_size, const void *d_history, size_t history_size, hipStream_t stream = 0);
 
+  // Long-distance matching (config.enable_ldm): what compress() of this device buffer
+  // would split, one record per 32 KiB cell = {first byte of the run, its length (0: the cell is
+  // not split), distance}, three u32 each, copied to host_records (capacity in records).
+  // *num_records = cells.  temp_workspace as for compress() of the same size with enable_ldm set.
+  // Frames the long-distance plan does not apply to (one block, or over 4 GiB) report 0 records.
+  Status ldm_plan(const void *d_src, size_t size, unsigned int *host_records, size_t capacity, size_t *num_records, void *temp_workspace,
+                  size_t temp_size, hipStream_t stream = 0);
+
  private:
   class Impl;
   std::unique_ptr<Impl> pimpl_;
