@@ -1806,13 +1806,21 @@ extern "C" __global__ __launch_bounds__(64) void zh_dec_seq_kernel(ZhDecArgs a, 
       u32 const w0 = win[buf][b][d], w1 = win[buf][b][d + 1];
       return __builtin_amdgcn_ubfe(__builtin_amdgcn_alignbit(w1, w0, (u32)lo & 31u), 0u, k);
     };
-    s32 wb = fetch(pos, 0);
+    s32 wb;
     u32 s;
     {  // initial states, from the top: LL, OF, ML
       u32 const kL = lg & 0xFFu, kO = (lg >> 8) & 0xFFu, kM = lg >> 16;
       u32 const k = q == 0 ? kO : q == 1 ? kM : q == 2 ? kL : 0u;
       u32 const off = q == 0 ? kL : q == 1 ? kL + kO : 0u;
-      s = field(0, pos - (s32)(off + k) - wb, k);
+      // The first window is step 0's, fetched from below the initial states: they and step 0 read
+      // up to 26 + 89 bits below pos, more than a window fetched at pos holds at every alignment
+      // (a first sequence of 64 bits or more was read as corrupt where (pos - 89) >> 3 fell in
+      // the first bytes of a 16-byte chunk).  The states lie above it, up to window bit 242: a
+      // field from bit 224 on reads dword 7 alone (its k <= 9 bits end by bit 18 of it).
+      wb = fetch(pos - (s32)(kL + kO + kM), 0);
+      s32 const lo = pos - (s32)(off + k) - wb;
+      u32 const d = min((u32)(lo >> 5), 7u);
+      s = __builtin_amdgcn_ubfe(__builtin_amdgcn_alignbit(win[0][b][d + 1], win[0][b][d], (u32)lo & 31u), 0u, k);
       pos -= (s32)(kL + kO + kM);
     }
     // software-pipelined: the table read of step i + 1 is issued as soon as its state is
