@@ -28,6 +28,8 @@
 // checksum mismatch -> ERROR_CHECKSUM_FAILED, a frame naming another (or no given) dictionary ->
 // ERROR_DICTIONARY_MISMATCH.  With a dictionary (RFC 8878 §5) its content precedes every frame
 // and a formatted one's tables and repcodes seed the frame state.
+// Kernels: the walker decode_body<Pass> (zh_decode_kernel = Whole; split pipeline: zh_dec_tables_kernel
+// = Tables, zh_dec_rest_kernel = Rest), zh_dec_seq_kernel, zh_dec_exec_kernel ("the walker's passes" below).
 #include "zh_common.h"
 #include "zh_launch.h"
 #include "zh_pipe.h"
@@ -79,14 +81,13 @@ __device__ __forceinline__ u32 tab_maxlog(u32 t) { return t == 1 ? 8u : 9u; }
 constexpr u32 TAB_NONE = 0xFFFFu, TAB_PREDEF = 0xFFFEu;  // tkind; else RLE symbol | 0x100, or 0 = FSE
 
 // The union's three views are used one after the other inside a block: Huffman decode,
-// sequence bitstream, execution window.  TAB = the split pipeline's tables-only pass
+// sequence bitstream, execution window.  TAB = the layout of the split pipeline's Tables pass
 // (zh_dec_tables_kernel): no literals, no execution, so the union shrinks to the 320-byte stage
-// of the table descriptions and the window arrays to stubs (8.5 KB instead of 16.8: twice the
+// of the table descriptions and the window arrays to stubs (7.8 KB instead of 16.8: twice the
 // workgroups per CU).
 template <bool TAB>
 struct DecLdsT {
   static constexpr bool kStartMap = false;
-  static constexpr bool kTablesOnly = TAB;
   u32 fse[1280];  // LL [0,512) OF [512,768) ML [768,1280): sym | nbBits << 8 | newState << 16
   union {
     struct {
@@ -115,7 +116,6 @@ struct DecLdsT {
   u32 used;  // serial-section byte count (lane 0 writes)
 };
 using DecLds = DecLdsT<false>;
-using DecLdsTab = DecLdsT<true>;
 
 __device__ __forceinline__ u32 hb32(u32 v) { return 31u - (u32)__builtin_clz(v); }
 __device__ __forceinline__ u32 lane_id() { return threadIdx.x; }
@@ -1038,7 +1038,7 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
   u32 q = 0, qd = 0, opos = 0, lcur = 0;
   bool bad = false;
 #ifdef ZH_STAMPS
-  // (-DZH_STAMPS, phase 3: xs[1] windows, xs[2] records + scan, [3] pass A, [4] pass B, [5] flush)
+  // (-DZH_STAMPS, zh_dec_exec_kernel: xs[1] windows, xs[2] records + scan, [3] pass A, [4] pass B, [5] flush)
   u64 xp = __builtin_amdgcn_s_memtime();
 #define XSTAMP(k)                                   \
   do {                                              \
@@ -1215,12 +1215,18 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
   return !bad;
 }
 
-// ---- split pipeline.  A buffer holding one frame of one compressed block (every chunk
-// of a batch) is decoded by three kernels: phase 1 (this kernel) does the headers, the
-// literals and the sequence tables and leaves a hand-off record; zh_dec_seq_kernel runs
-// the sequence bitstreams of 16 such buffers per wave, four lanes each (the serial FSE chains
-// of 16 blocks interleave in one wave instead of one chain per wave); zh_dec_exec_kernel
-// (phase 3) executes the block and finishes the frame.  Anything else is decoded in phase 1.
+// ---- the walker's passes.  A buffer holding one frame of one compressed block (every chunk
+// of a batch) is deferred: the walker does its headers, literals and sequence tables and
+// leaves a hand-off record; zh_dec_seq_kernel runs the sequence bitstreams of 16 such buffers
+// per wave, four lanes each (the serial FSE chains of 16 blocks interleave in one wave instead
+// of one chain per wave); zh_dec_exec_kernel executes the block and finishes the frame.
+// Anything else the walker decodes itself.  Whole does all of the walker's share in one kernel.
+// The split pipeline (launch_decompress) cuts it in two: Tables visits only the deferrable
+// buffers, skips their literals and writes the record (no status, no output); Rest decodes the
+// deferred buffers' literals into their records and every other buffer whole.
+enum class Pass { Whole, Tables, Rest };
+template <Pass P> using PassLds = DecLdsT<P == Pass::Tables>;
+
 struct DecHandoff {
   u32 tabs[1280];  // DecLds::fse of the block
   u64 sp;          // sequence bitstream
@@ -1234,8 +1240,44 @@ struct DecHandoff {
 };
 static_assert(sizeof(DecHandoff) <= ZH_DEC_HANDOFF_BYTES, "hand-off record");
 
-__device__ __forceinline__ DecHandoff *handoff(const ZhDecArgs &a, u32 item) {
-  return (DecHandoff *)(a.ws + (size_t)item * a.slot_bytes + a.ho_off);
+// ---- item view: what one input buffer of the launch owns
+__device__ __forceinline__ Slot item_slot(const ZhDecArgs &a, u32 idx) {
+  u8 *const lit = a.ws + (size_t)idx * a.slot_bytes;
+  return Slot{lit, (u64 *)(lit + a.lit_bytes), a.block_cap, a.seq_cap};
+}
+__device__ __forceinline__ DecHandoff *handoff(const ZhDecArgs &a, u32 idx) {
+  return (DecHandoff *)(a.ws + (size_t)idx * a.slot_bytes + a.ho_off);
+}
+
+struct Item {
+  u32 idx;
+  const u8 *src;
+  u8 *dst;
+  u64 srcn, cap;
+  Slot sl;
+  DecHandoff *ho;
+  const u8 *dend;  // dictionary content precedes every frame: match sources before the frame start
+  s64 dlen;
+};
+__device__ __forceinline__ Item item_view(const ZhDecArgs &a, u32 idx) {
+  Item it;
+  it.idx = idx;
+  it.src = (const u8 *)(a.in_ptrs ? a.in_ptrs[idx] : a.one_in);
+  it.srcn = a.in_ptrs ? (u64)a.in_sizes[idx] : a.one_in_size;
+  it.dst = (u8 *)(a.in_ptrs ? a.out_ptrs[idx] : a.one_out);
+  it.cap = a.out_caps ? (u64)a.out_caps[idx] : a.out_cap_all;
+  it.sl = item_slot(a, idx);
+  it.ho = handoff(a, idx);
+  it.dend = a.dict ? a.dict + a.dict_n : nullptr;
+  it.dlen = a.dict ? (s64)(a.dict_n - a.dict_off) : 0;
+  return it;
+}
+// The item's size and status, by whichever kernel finishes it
+__device__ __forceinline__ void finish_item(const ZhDecArgs &a, const Item &it, u32 st, u64 produced) {
+  if (lane_id() == 0) {
+    a.out_sizes[it.idx] = st == ST_OK ? produced : 0ull;
+    if (a.statuses) a.statuses[it.idx] = a.nvcomp_codes ? to_nvcomp(st) : st;
+  }
 }
 
 // Offset_Value -> offset with the repeat-offset history (RFC 8878 §3.1.1.5; libzstd
@@ -1271,81 +1313,260 @@ __device__ __forceinline__ u32 resolve_off(u32 ofv, u32 ll, u32 &rep0, u32 &rep1
     stv[k] += _t - stp;                        \
     stp = _t;                                  \
   } while (0)
+// Rest's split of a deferred item into its record's spare bytes (tools/p5_stamps.py)
+#define REST_STAMPS()                              \
+  do {                                             \
+    u64 *const xs5 = (u64 *)((u8 *)it.ho + 5248);  \
+    if (lane == 0) {                               \
+      xs5[0] = stv[0];                             \
+      xs5[1] = L.lst_t[0] - (stp - stv[1]);        \
+      xs5[2] = L.lst_t[1] - L.lst_t[0];            \
+      xs5[3] = L.lst_t[2] - L.lst_t[1];            \
+      xs5[4] = stp - L.lst_t[2];                   \
+      xs5[5] = lits.n;                             \
+    }                                              \
+  } while (0)
 #else
 #define DSTAMP(k) do { } while (0)
+#define REST_STAMPS() do { } while (0)
 #endif
 
-// One workgroup (one wave) per input buffer.
+// ---- frame header (RFC 8878 §3.1.1.1) at p, n bytes left in the buffer (first: the buffer
+// starts here).  -> ST_OK and h (a skippable frame: only skip and size), or the frame's error.
+struct FrameHdr {
+  u64 size, fcs;  // bytes up to the first block (skip: the whole frame); content size (~0: absent)
+  u32 chk, did;   // content checksum flag, dictionary id (0: none)
+  bool skip;
+};
+__device__ __forceinline__ u32 frame_header(const ZhDecArgs &a, const u8 *p, u64 n, bool first, FrameHdr &h) {
+  if (n < 4) return ST_CORRUPT;
+  u32 const magic = rd32(p);
+  h.skip = (magic & 0xFFFFFFF0u) == 0x184D2A50u;
+  if (h.skip) {
+    if (n < 8) return ST_CORRUPT;
+    h.size = 8ull + rd32(p + 4);
+    return h.size > n ? ST_CORRUPT : ST_OK;
+  }
+  if (magic != ZH_MAGIC) return first ? ST_MAGIC : ST_CORRUPT;
+  if (n < 5) return ST_CORRUPT;
+  u32 const fhd = ub(p + 4);
+  u32 const fcsf = fhd >> 6, single = (fhd >> 5) & 1u, didf = fhd & 3u;
+  if (fhd & 8u) return ST_CORRUPT;
+  u32 const didn = didf == 0 ? 0u : didf == 1 ? 1u : didf == 2 ? 2u : 4u;
+  u32 const fcsn = fcsf == 0 ? (single ? 1u : 0u) : fcsf == 1 ? 2u : fcsf == 2 ? 4u : 8u;
+  h.size = 5ull + (single ? 0u : 1u) + didn + fcsn;
+  if (n < h.size) return ST_CORRUPT;
+  const u8 *q = p + 5;
+  if (!single) {
+    u32 const wd = ub(q++);
+    if (10 + (wd >> 3) > 30) return ST_CORRUPT;
+  }
+  h.chk = (fhd >> 2) & 1u;
+  h.did = 0;
+  for (u32 i = 0; i < didn; i++) h.did |= ub(q + i) << (8 * i);
+  q += didn;
+  h.fcs = ~0ull;
+  if (fcsn == 1) h.fcs = ub(q);
+  else if (fcsn == 2) h.fcs = rd16(q) + 256ull;
+  else if (fcsn == 4) h.fcs = rd32(q);
+  else if (fcsn == 8) h.fcs = (u64)rd32(q) | (u64)rd32(q + 4) << 32;
+  if (h.did != 0 && (!a.dict || h.did != a.dict_id)) return ST_DICT;  // libzstd: dictionary_wrong
+  return ST_OK;
+}
+
+// ---- sequences section header (RFC 8878 §3.1.1.3.2.1) at sp, rem bytes: Number_of_Sequences
+// in its 1 / 2 / 3-byte forms and, when there are sequences, the Symbol_Compression_Modes byte
+struct SeqHdr { u32 nseq, modes, size; };
+__device__ __forceinline__ u32 seq_header(const u8 *sp, u32 rem, u32 seq_cap, SeqHdr &h) {
+  if (rem < 1) return ST_CORRUPT;
+  u32 const b0 = ub(sp);
+  h.modes = 0;
+  if (b0 < 128) {
+    h.nseq = b0;
+    h.size = 1;
+  } else if (b0 < 255) {
+    if (rem < 2) return ST_CORRUPT;
+    h.nseq = ((b0 - 128) << 8) + ub(sp + 1);
+    h.size = 2;
+  } else {
+    if (rem < 3) return ST_CORRUPT;
+    h.nseq = rd16(sp + 1) + 0x7F00u;
+    h.size = 3;
+  }
+  if (h.nseq == 0) return rem != h.size ? ST_CORRUPT : ST_OK;  // no sequences: the section ends here
+  if (h.nseq > seq_cap) return h.nseq > BLOCKSIZE_MAX / 3 + 1 ? ST_CORRUPT : ST_SMALL;
+  if (rem < h.size + 1) return ST_CORRUPT;
+  h.modes = ub(sp + h.size++);
+  return (h.modes & 3u) ? ST_CORRUPT : ST_OK;  // Reserved bits
+}
+
+// ---- sequence tables: the three descriptions at sp (modes = Symbol_Compression_Modes) into
+// L.fse / L.tlog / L.tkind.  -> false: corrupt; else used = the descriptions' bytes.
 template <class LDS>
-__device__ __forceinline__ void decode_body(LDS &L, ZhDecArgs a) {
-  u32 const item = a.item0 + blockIdx.x, lane = lane_id();
-  const u8 *const src = (const u8 *)(a.in_ptrs ? a.in_ptrs[item] : a.one_in);
-  u64 const srcn = a.in_ptrs ? (u64)a.in_sizes[item] : a.one_in_size;
-  u8 *const dst = (u8 *)(a.in_ptrs ? a.out_ptrs[item] : a.one_out);
-  u64 const cap = a.out_caps ? (u64)a.out_caps[item] : a.out_cap_all;
-  Slot sl;
-  sl.lit = a.ws + (size_t)item * a.slot_bytes;
-  sl.lit_cap = a.block_cap;
-  sl.seq = (u64 *)(sl.lit + a.lit_bytes);
-  sl.seq_cap = a.seq_cap;
-  // dictionary content precedes every frame: match sources before the frame start
-  const u8 *const dend = a.dict ? a.dict + a.dict_n : nullptr;
-  s64 const dlen = a.dict ? (s64)(a.dict_n - a.dict_off) : 0;
-  if constexpr (!LDS::kTablesOnly) {
+__device__ __forceinline__ bool seq_tables(LDS &L, u32 modes, const u8 *sp, u32 rem, u32 &used) {
+  u32 const lane = lane_id();
+  // the table descriptions staged in LDS with one wave load: lane 0's NCount parse was a
+  // chain of dependent global byte loads (three descriptions take <= ~240 bytes)
+  constexpr u32 DEC_TSTAGE = 320;
+  u32 const tb = min(rem, DEC_TSTAGE);
+  for (u32 k = lane; k < tb; k += 64) L.u.sstage[k] = sp[k];
+  __syncthreads();
+  if (lane == 0) {
+    u32 e = 0, n = 0;
+    u32 const md[3] = {modes >> 6, (modes >> 4) & 3u, (modes >> 2) & 3u};
+    L.bld[0] = L.bld[1] = L.bld[2] = 0;
+    for (u32 t = 0; t < 3 && !e; t++) {
+      s32 const u = seq_table(L, t, md[t], L.u.sstage + n, tb - n, true);
+      if (u < 0) e = 1;
+      else n += (u32)u;
+    }
+    L.err = e;
+    L.used = n;
+  }
+  __syncthreads();
+  if (uni(L.err)) return false;
+  bool ok = true;
+  for (u32 t = 0; t < 3; t++)
+    if (uni(L.bld[t])) ok = ok && build_dtable_wave(L.fse + tab_off(t), L.norm + 64 * t, tab_maxsv(t), uni(L.tlog[t]));
+  __syncthreads();
+  if (!ok && lane == 0) L.tkind[0] = L.tkind[1] = L.tkind[2] = TAB_NONE;  // (a failed build leaves them unusable)
+  used = uni(L.used);
+  return ok;
+}
+
+// ---- defer: fill the hand-off record of a buffer whose only block goes to zh_dec_seq_kernel and
+// zh_dec_exec_kernel (Whole, Tables).  Tables leaves the literals to Rest (rest_literals).
+template <Pass P>
+__device__ __forceinline__ void defer_block(PassLds<P> &L, DecHandoff *ho, const u8 *sp, u32 rem, u32 nseq, const LitSrc &lits, u64 fcs,
+                                            u64 ipc, u32 rep0, u32 rep1, u32 rep2) {
+  u32 const lane = lane_id();
+  // the quad sequence kernel's entries: newState | symbol << 9 | extra bits << 16 |
+  // state bits << 24 (the extra bits of a code: LL / ML from the code tables, OF = code)
+  for (u32 w = lane; w < 1280; w += 64) {
+    u32 const e = L.fse[w], sym = e & 0x3Fu;
+    u32 const xb = w < 512 ? L.info[0][sym] >> 24 : w < 768 ? sym : L.info[1][sym] >> 24;
+    ho->tabs[w] = (e >> 16) | sym << 9 | xb << 16 | ((e >> 8) & 0xFFu) << 24;
+  }
+  if (lane == 0) {
+    ho->sp = (u64)sp;
+    ho->rem = rem;
+    ho->nseq = nseq;
+    ho->lg = L.tlog[TAB_LL] | L.tlog[TAB_OF] << 8 | L.tlog[TAB_ML] << 16;
+    if constexpr (P == Pass::Whole) {
+      ho->litg = (u64)lits.g;
+      ho->litrle = lits.rle;
+      ho->litn = lits.n;
+    }
+    ho->fcs = fcs;
+    ho->ipc = ipc;
+    ho->rep[0] = rep0;
+    ho->rep[1] = rep1;
+    ho->rep[2] = rep2;
+    ho->flag = 1;
+  }
+}
+// Rest's side of a buffer Tables deferred: its literals are all this pass owes it (ls = their
+// section's size).  A corrupt literals section (ls = 0) takes the deferral back: zh_dec_exec_kernel
+// skips the buffer and Rest reports the error.
+__device__ __forceinline__ void rest_literals(DecHandoff *ho, u32 ls, const LitSrc &lits) {
+  if (lane_id() != 0) return;
+  if (!ls) {
+    ho->flag = 0;
+    return;
+  }
+  ho->litg = (u64)lits.g;
+  ho->litrle = lits.rle;
+  ho->litn = lits.n;
+}
+
+// ---- sequence bitstream (RFC 8878 §3.1.1.3.2.2) of the blocks the walker executes itself:
+// every lane decodes redundantly (uniform control flow, no exec-mask work); lane j keeps record
+// j of each 64.  Records to seq, the repcodes advance.  -> false: corrupt.
+__device__ __forceinline__ bool decode_sequences(DecLds &L, const u8 *sp, u32 rem, u32 nseq, u64 *seq, u32 &rep0, u32 &rep1, u32 &rep2,
+                                                 u64 &sumLL, u64 &sumML) {
+  u32 const lane = lane_id();
+  BitRevS r;
+  if (!r.start<true>(sp, rem)) return false;
+  u8 *const stg = L.u.sstage;
+  // read k bits; the bitstream comes from an LDS stage refilled SSTAGE bytes at a time
+  auto rd = [&](u32 k) -> u32 {
+    if (!r.ensure<true>(stg, k)) {
+      u32 lo, hi;
+      r.stage_range(SSTAGE, lo, hi);
+      stage_copy(stg, sp, lo, hi);
+      __syncthreads();
+      r.slo = (s32)uni(lo);
+      r.ensure<true>(stg, k);
+    }
+    u32 const v = (u32)r.bits(k);
+    r.pos -= (s32)k;
+    return v;
+  };
+  u32 const lgLL = uni(L.tlog[TAB_LL]), lgOF = uni(L.tlog[TAB_OF]), lgML = uni(L.tlog[TAB_ML]);
+  const u32 *TLL = L.fse + tab_off(TAB_LL), *TOF = L.fse + tab_off(TAB_OF), *TML = L.fse + tab_off(TAB_ML);
+  u32 sLL = rd(lgLL), sOF = rd(lgOF), sML = rd(lgML);
+  bool big = false;
+  u64 rec = 0;
+  for (u32 i = 0; i < nseq; i++) {
+    // (table entries made wave-uniform: the chain runs in SGPRs)
+    u32 const eLL = __builtin_amdgcn_readfirstlane(TLL[sLL]), eOF = __builtin_amdgcn_readfirstlane(TOF[sOF]),
+              eML = __builtin_amdgcn_readfirstlane(TML[sML]);
+    u32 const ofc = eOF & 0xFFu;
+    u32 const ofv = (1u << ofc) + rd(ofc);
+    u32 const mi = __builtin_amdgcn_readfirstlane(L.info[1][eML & 0xFFu]);
+    u32 const ml = (mi & 0xFFFFFFu) + rd(mi >> 24);
+    u32 const li = __builtin_amdgcn_readfirstlane(L.info[0][eLL & 0xFFu]);
+    u32 const ll = (li & 0xFFFFFFu) + rd(li >> 24);
+    u32 const off = resolve_off(ofv, ll, rep0, rep1, rep2);
+    big |= off >= OFF_LIMIT;
+    sumLL += ll;
+    sumML += ml;
+    u64 const v = (u64)ll | (u64)(ml - 3) << 17 | (u64)off << 34;
+    rec = lane == (i & 63u) ? v : rec;
+    if ((i & 63u) == 63u || i + 1 == nseq) {
+      if (lane <= (i & 63u)) seq[(i & ~63u) + lane] = rec;
+    }
+    if (i + 1 < nseq) {
+      sLL = (eLL >> 16) + rd((eLL >> 8) & 0xFFu);
+      sML = (eML >> 16) + rd((eML >> 8) & 0xFFu);
+      sOF = (eOF >> 16) + rd((eOF >> 8) & 0xFFu);
+    }
+  }
+  return r.pos <= 0 && !big;
+}
+
+// ---- the walker: one workgroup (one wave) per input buffer walks its frames and blocks.
+// ST_ELSEWHERE (never reported): the buffer was deferred, zh_dec_exec_kernel finishes it.
+constexpr u32 ST_ELSEWHERE = ~0u;
+template <Pass P>
+__device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
+  u32 const lane = lane_id();
+  Item const it = item_view(a, blockIdx.x);
+  const u8 *const src = it.src;
+  u64 const srcn = it.srcn, cap = it.cap;
+  if constexpr (P != Pass::Tables) {
     if (lane < 4) L.wvs[64 + lane] = 0x7FFFFFFF;
   }
   if (lane < 36) L.info[0][lane] = c_LL_info[lane];
   if (lane < 53) L.info[1][lane] = c_ML_info[lane];
   __syncthreads();
-
-  // split pipeline (launch_decompress): phase 4 = the sequence tables of deferrable buffers
-  // only (no literals, no status), phase 5 = everything else (the literals of the deferred
-  // buffers, whole decodes of the others)
-  if ((a.phase == 1 || a.phase == 4) && lane == 0) handoff(a, item)->flag = 0;
+  if constexpr (P != Pass::Rest) {
+    if (lane == 0) it.ho->flag = 0;
+  }
 
   u32 st = ST_OK;
   u64 produced = 0, ip = 0;
-  if (!src || (!dst && cap)) st = ST_INVALID;
+  if (!src || (!it.dst && cap)) st = ST_INVALID;
 #ifdef ZH_STAMPS
   u64 stv[8] = {}, stp = __builtin_amdgcn_s_memtime();
 #endif
   while (st == ST_OK && ip < srcn) {
-    // ---- frame header (RFC 8878 §3.1.1.1)
-    if (srcn - ip < 4) { st = ST_CORRUPT; break; }
-    u32 const magic = rd32(src + ip);
-    if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {  // skippable frame
-      if (srcn - ip < 8) { st = ST_CORRUPT; break; }
-      u64 const sk = 8ull + rd32(src + ip + 4);
-      if (sk > srcn - ip) { st = ST_CORRUPT; break; }
-      ip += sk;
-      continue;
-    }
-    if (magic != ZH_MAGIC) { st = ip == 0 ? ST_MAGIC : ST_CORRUPT; break; }
-    ip += 4;
-    if (srcn - ip < 1) { st = ST_CORRUPT; break; }
-    u32 const fhd = ub(src + ip);
-    u32 const fcsf = fhd >> 6, single = (fhd >> 5) & 1u, chk = (fhd >> 2) & 1u, didf = fhd & 3u;
-    if (fhd & 8u) { st = ST_CORRUPT; break; }
-    u32 const didn = didf == 0 ? 0u : didf == 1 ? 1u : didf == 2 ? 2u : 4u;
-    u32 const fcsn = fcsf == 0 ? (single ? 1u : 0u) : fcsf == 1 ? 2u : fcsf == 2 ? 4u : 8u;
-    u64 const hsz = 1ull + (single ? 0u : 1u) + didn + fcsn;
-    if (srcn - ip < hsz) { st = ST_CORRUPT; break; }
-    const u8 *h = src + ip + 1;
-    if (!single) {
-      u32 const wd = ub(h++);
-      if (10 + (wd >> 3) > 30) { st = ST_CORRUPT; break; }
-    }
-    u32 did = 0;
-    for (u32 i = 0; i < didn; i++) did |= ub(h + i) << (8 * i);
-    h += didn;
-    u64 fcs = ~0ull;
-    if (fcsn == 1) fcs = ub(h);
-    else if (fcsn == 2) fcs = rd16(h) + 256ull;
-    else if (fcsn == 4) fcs = rd32(h);
-    else if (fcsn == 8) fcs = (u64)rd32(h) | (u64)rd32(h + 4) << 32;
-    if (did != 0 && (!a.dict || did != a.dict_id)) { st = ST_DICT; break; }  // libzstd: dictionary_wrong
-    ip += hsz;
-    if (fcs != ~0ull && fcs > cap - produced) { st = ST_SMALL; break; }
+    FrameHdr fh;
+    st = frame_header(a, src + ip, srcn - ip, ip == 0, fh);
+    if (st != ST_OK) break;
+    ip += fh.size;
+    if (fh.skip) continue;
+    if (fh.fcs != ~0ull && fh.fcs > cap - produced) { st = ST_SMALL; break; }
     u64 const fstart = produced;
     // frame state: repcodes, table kinds
     u32 rep0 = 1, rep1 = 4, rep2 = 8;
@@ -1369,8 +1590,12 @@ __device__ __forceinline__ void decode_body(LDS &L, ZhDecArgs a) {
       u32 const bh = rd24(src + ip);
       u32 const last = bh & 1u, bt = (bh >> 1) & 3u, bsz = bh >> 3;
       ip += 3;
-      u8 *const ob = dst + produced;  // this block's first output byte
-      if (a.phase == 4 && !(bt == 2 && produced == 0 && last)) return;  // not deferrable
+      u8 *const ob = it.dst + produced;  // this block's first output byte
+      // the buffer's only block, compressed: its sequences can go to zh_dec_seq_kernel
+      bool const only = bt == 2 && produced == 0 && last && ip + bsz + (fh.chk ? 4ull : 0ull) == srcn;
+      if constexpr (P == Pass::Tables) {
+        if (!only) break;  // not deferrable: Rest decodes the buffer
+      }
       if (bt == 0) {
         if (srcn - ip < bsz) { st = ST_CORRUPT; break; }
         if (bsz > cap - produced) { st = ST_SMALL; break; }
@@ -1389,213 +1614,66 @@ __device__ __forceinline__ void decode_body(LDS &L, ZhDecArgs a) {
         LitSrc lits;
         DSTAMP(0);
         u32 ls;
-        if constexpr (LDS::kTablesOnly) ls = skip_literals(bp, bsz);
-        else ls = a.phase == 4 ? skip_literals(bp, bsz) : decode_literals(L, bp, bsz, sl, lits, st);
+        if constexpr (P == Pass::Tables) ls = skip_literals(bp, bsz);
+        else ls = decode_literals(L, bp, bsz, it.sl, lits, st);
         DSTAMP(1);
-        if (a.phase == 5 && produced == 0 && uni(handoff(a, item)->flag) == 1) {
-          // deferred by phase 4: the literals are all this pass owes it (a corrupt literals
-          // section takes it back: the status is written below, phase 3 skips it)
-          DecHandoff *const ho = handoff(a, item);
-          if (!ls) {
-            if (lane == 0) ho->flag = 0;
+        if constexpr (P == Pass::Rest) {
+          if (produced == 0 && uni(it.ho->flag) == 1) {  // deferred by Tables
+            rest_literals(it.ho, ls, lits);
+            if (ls) {
+              REST_STAMPS();
+              st = ST_ELSEWHERE;
+            }
             break;
           }
-          if (lane == 0) {
-            ho->litg = (u64)lits.g;
-            ho->litrle = lits.rle;
-            ho->litn = lits.n;
-          }
-#ifdef ZH_STAMPS
-          // (-DZH_STAMPS: phase 5's split into the record's spare bytes, tools/p5_stamps.py)
-          if (lane == 0) {
-            u64 *const xs5 = (u64 *)((u8 *)ho + 5248);
-            xs5[0] = stv[0];
-            xs5[1] = L.lst_t[0] - (stp - stv[1]);
-            xs5[2] = L.lst_t[1] - L.lst_t[0];
-            xs5[3] = L.lst_t[2] - L.lst_t[1];
-            xs5[4] = stp - L.lst_t[2];
-            xs5[5] = lits.n;
-          }
-#endif
-          return;  // phase 3 writes the size and status
         }
-        if (!ls) {
-          if (a.phase == 4) return;
-          break;
-        }
-        // ---- sequences section header (RFC 8878 §3.1.1.3.2.1)
+        if (!ls) break;
         const u8 *sp = bp + ls;
         u32 rem = bsz - ls;
-        if (rem < 1) { st = ST_CORRUPT; break; }
-        u32 nseq = ub(sp);
-        if (nseq == 0) {
-          if (rem != 1) { st = ST_CORRUPT; break; }
-          sp += 1;
-          rem -= 1;
-        } else if (nseq < 128) {
-          sp += 1;
-          rem -= 1;
-        } else if (nseq < 255) {
-          if (rem < 2) { st = ST_CORRUPT; break; }
-          nseq = ((nseq - 128) << 8) + ub(sp + 1);
-          sp += 2;
-          rem -= 2;
-        } else {
-          if (rem < 3) { st = ST_CORRUPT; break; }
-          nseq = rd16(sp + 1) + 0x7F00u;
-          sp += 3;
-          rem -= 3;
-        }
+        SeqHdr sh;
+        st = seq_header(sp, rem, it.sl.seq_cap, sh);
+        if (st != ST_OK) break;
+        sp += sh.size;
+        rem -= sh.size;
+        u32 const nseq = sh.nseq;
         u64 sumML = 0, sumLL = 0;
         if (nseq) {
-          if (nseq > sl.seq_cap) { st = nseq > BLOCKSIZE_MAX / 3 + 1 ? ST_CORRUPT : ST_SMALL; break; }
-          if (rem < 1) { st = ST_CORRUPT; break; }
-          u32 const modes = ub(sp);
-          sp += 1;
-          rem -= 1;
-          if (modes & 3u) { st = ST_CORRUPT; break; }
-          // the table descriptions staged in LDS with one wave load: lane 0's NCount parse was a
-          // chain of dependent global byte loads (three descriptions take <= ~240 bytes)
-          constexpr u32 DEC_TSTAGE = 320;
-          u32 const tb = min(rem, DEC_TSTAGE);
-          for (u32 k = lane; k < tb; k += 64) L.u.sstage[k] = sp[k];
-          __syncthreads();
-          const u8 *const tsrc = L.u.sstage;
-          u32 const tavail = tb;
-          if (lane == 0) {
-            u32 e = 0, used = 0;
-            u32 const md[3] = {modes >> 6, (modes >> 4) & 3u, (modes >> 2) & 3u};
-            L.bld[0] = L.bld[1] = L.bld[2] = 0;
-            for (u32 t = 0; t < 3 && !e; t++) {
-              s32 const u = seq_table(L, t, md[t], tsrc + used, tavail - used, true);
-              if (u < 0) e = 1;
-              else used += (u32)u;
-            }
-            L.err = e;
-            L.used = used;
-          }
-          __syncthreads();
-          if (uni(L.err)) { st = ST_CORRUPT; break; }
-          {
-            bool ok = true;
-            for (u32 t = 0; t < 3; t++)
-              if (uni(L.bld[t])) ok = ok && build_dtable_wave(L.fse + tab_off(t), L.norm + 64 * t, tab_maxsv(t), uni(L.tlog[t]));
-            __syncthreads();
-            if (!ok) {
-              if (lane == 0) L.tkind[0] = L.tkind[1] = L.tkind[2] = TAB_NONE;  // (as the serial build left them unusable)
-              st = ST_CORRUPT;
+          u32 tused;
+          if (!seq_tables(L, sh.modes, sp, rem, tused)) { st = ST_CORRUPT; break; }
+          DSTAMP(2);
+          sp += tused;
+          rem -= tused;
+          if constexpr (P != Pass::Rest) {
+            if (only) {
+              defer_block<P>(L, it.ho, sp, rem, nseq, lits, fh.fcs, fh.chk ? ip + bsz : ~0ull, rep0, rep1, rep2);
+              st = ST_ELSEWHERE;
               break;
             }
           }
-          DSTAMP(2);
-          u32 const tused = uni(L.used);
-          sp += tused;
-          rem -= tused;
-          if ((a.phase == 1 || a.phase == 4) && produced == 0 && last && ip + bsz + (chk ? 4ull : 0ull) == srcn) {
-            // the buffer's only block: hand the sequence bitstream to zh_dec_seq_kernel
-            DecHandoff *const ho = handoff(a, item);
-            // the quad sequence kernel's entries: newState | symbol << 9 | extra bits << 16 |
-            // state bits << 24 (the extra bits of a code: LL / ML from the code tables, OF = code)
-            for (u32 w = lane; w < 1280; w += 64) {
-              u32 const e = L.fse[w], sym = e & 0x3Fu;
-              u32 const xb = w < 512 ? L.info[0][sym] >> 24 : w < 768 ? sym : L.info[1][sym] >> 24;
-              ho->tabs[w] = (e >> 16) | sym << 9 | xb << 16 | ((e >> 8) & 0xFFu) << 24;
-            }
-            if (lane == 0) {
-              ho->sp = (u64)sp;
-              ho->rem = rem;
-              ho->nseq = nseq;
-              ho->lg = L.tlog[TAB_LL] | L.tlog[TAB_OF] << 8 | L.tlog[TAB_ML] << 16;
-              if (a.phase == 1) {
-                ho->litg = (u64)lits.g;
-                ho->litrle = lits.rle;
-                ho->litn = lits.n;
-              }
-              ho->fcs = fcs;
-              ho->ipc = chk ? ip + bsz : ~0ull;
-              ho->rep[0] = rep0;
-              ho->rep[1] = rep1;
-              ho->rep[2] = rep2;
-              ho->flag = 1;
-            }
-            return;  // phase 3 writes the size and status
+          if constexpr (P != Pass::Tables) {
+            if (!decode_sequences(L, sp, rem, nseq, it.sl.seq, rep0, rep1, rep2, sumLL, sumML)) { st = ST_CORRUPT; break; }
+            DSTAMP(3);
           }
-          if (LDS::kTablesOnly || a.phase == 4) return;
-          if constexpr (!LDS::kTablesOnly) {
-          // ---- sequence bitstream (RFC 8878 §3.1.1.3.2.2): every lane decodes redundantly
-          // (uniform control flow, no exec-mask work); lane j keeps record j of each 64
-          BitRevS r;
-          if (!r.start<true>(sp, rem)) { st = ST_CORRUPT; break; }
-          u8 *const stg = L.u.sstage;
-          // read k bits; the bitstream comes from an LDS stage refilled SSTAGE bytes at a time
-          auto rd = [&](u32 k) -> u32 {
-            if (!r.ensure<true>(stg, k)) {
-              u32 lo, hi;
-              r.stage_range(SSTAGE, lo, hi);
-              stage_copy(stg, sp, lo, hi);
-              __syncthreads();
-              r.slo = (s32)uni(lo);
-              r.ensure<true>(stg, k);
-            }
-            u32 const v = (u32)r.bits(k);
-            r.pos -= (s32)k;
-            return v;
-          };
-          u32 const lgLL = uni(L.tlog[TAB_LL]), lgOF = uni(L.tlog[TAB_OF]), lgML = uni(L.tlog[TAB_ML]);
-          const u32 *TLL = L.fse + tab_off(TAB_LL), *TOF = L.fse + tab_off(TAB_OF), *TML = L.fse + tab_off(TAB_ML);
-          u32 sLL = rd(lgLL), sOF = rd(lgOF), sML = rd(lgML);
-          bool big = false;
-          u64 rec = 0;
-          for (u32 i = 0; i < nseq; i++) {
-            // (table entries made wave-uniform: the chain runs in SGPRs)
-            u32 const eLL = __builtin_amdgcn_readfirstlane(TLL[sLL]), eOF = __builtin_amdgcn_readfirstlane(TOF[sOF]),
-                      eML = __builtin_amdgcn_readfirstlane(TML[sML]);
-            u32 const ofc = eOF & 0xFFu;
-            u32 const ofv = (1u << ofc) + rd(ofc);
-            u32 const mi = __builtin_amdgcn_readfirstlane(L.info[1][eML & 0xFFu]);
-            u32 const ml = (mi & 0xFFFFFFu) + rd(mi >> 24);
-            u32 const li = __builtin_amdgcn_readfirstlane(L.info[0][eLL & 0xFFu]);
-            u32 const ll = (li & 0xFFFFFFu) + rd(li >> 24);
-            u32 const off = resolve_off(ofv, ll, rep0, rep1, rep2);
-            big |= off >= OFF_LIMIT;
-            sumLL += ll;
-            sumML += ml;
-            u64 const v = (u64)ll | (u64)(ml - 3) << 17 | (u64)off << 34;
-            rec = lane == (i & 63u) ? v : rec;
-            if ((i & 63u) == 63u || i + 1 == nseq) {
-              if (lane <= (i & 63u)) sl.seq[(i & ~63u) + lane] = rec;
-            }
-            if (i + 1 < nseq) {
-              sLL = (eLL >> 16) + rd((eLL >> 8) & 0xFFu);
-              sML = (eML >> 16) + rd((eML >> 8) & 0xFFu);
-              sOF = (eOF >> 16) + rd((eOF >> 8) & 0xFFu);
-            }
-          }
-          if (r.pos > 0 || big) { st = ST_CORRUPT; break; }
-          DSTAMP(3);
-          }  // !kTablesOnly
-        } else if (rem != 0) {
-          st = ST_CORRUPT;
-          break;
         }
-        if (LDS::kTablesOnly || a.phase == 4) return;  // (no sequences: nothing deferred)
-        if constexpr (!LDS::kTablesOnly) {
-        if (sumLL > lits.n) { st = ST_CORRUPT; break; }
-        u64 const total = lits.n + sumML;
-        // RFC 8878 §3.1.1.2.4: a block regenerates at most Block_Maximum_Size (128 KiB), which
-        // also keeps execute_block's u32 window arithmetic in range
-        if (total > BLOCKSIZE_MAX) { st = ST_CORRUPT; break; }
-        if (total > cap - produced) { st = ST_SMALL; break; }
-        __threadfence_block();  // the records (and Huffman literals) are read back below
-        __syncthreads();
-        u32 const tl = lits.n - (u32)sumLL;
-        s64 const fpos = (s64)(produced - fstart);  // frame bytes before this block
-        bool const bad = !execute_block(L, sl, ob, fpos, lits, nseq, tl, dend, dlen);
-        DSTAMP(4);
-        if (bad) { st = ST_CORRUPT; break; }
-        produced += total;
-        ip += bsz;
-        }  // !kTablesOnly
+        if constexpr (P == Pass::Tables) {
+          break;  // (no sequences: nothing to defer)
+        } else {
+          if (sumLL > lits.n) { st = ST_CORRUPT; break; }
+          u64 const total = lits.n + sumML;
+          // RFC 8878 §3.1.1.2.4: a block regenerates at most Block_Maximum_Size (128 KiB), which
+          // also keeps execute_block's u32 window arithmetic in range
+          if (total > BLOCKSIZE_MAX) { st = ST_CORRUPT; break; }
+          if (total > cap - produced) { st = ST_SMALL; break; }
+          __threadfence_block();  // the records (and Huffman literals) are read back below
+          __syncthreads();
+          u32 const tl = lits.n - (u32)sumLL;
+          s64 const fpos = (s64)(produced - fstart);  // frame bytes before this block
+          bool const bad = !execute_block(L, it.sl, ob, fpos, lits, nseq, tl, it.dend, it.dlen);
+          DSTAMP(4);
+          if (bad) { st = ST_CORRUPT; break; }
+          produced += total;
+          ip += bsz;
+        }
       } else {
         st = ST_CORRUPT;
         break;
@@ -1603,40 +1681,42 @@ __device__ __forceinline__ void decode_body(LDS &L, ZhDecArgs a) {
       __threadfence_block();
       if (last) break;
     }
-    if (st != ST_OK) break;
-    if (fcs != ~0ull && produced - fstart != fcs) { st = ST_CORRUPT; break; }
-    if (chk) {
+    if (P == Pass::Tables || st != ST_OK) break;  // (Tables looks at one block)
+    if (fh.fcs != ~0ull && produced - fstart != fh.fcs) { st = ST_CORRUPT; break; }
+    if (fh.chk) {
       if (srcn - ip < 4) { st = ST_CORRUPT; break; }
-      u64 const hx = zh_xxh64(dst + fstart, produced - fstart);
+      u64 const hx = zh_xxh64(it.dst + fstart, produced - fstart);
       if ((u32)hx != rd32(src + ip)) { st = ST_CHECKSUM; break; }
       ip += 4;
     }
   }
+  // Tables reports nothing: Rest meets the errors it met
+  if constexpr (P != Pass::Tables) {
+    if (st == ST_ELSEWHERE) return;
 #ifdef ZH_STAMPS
-  DSTAMP(5);
-  if (lane < 8) ((u64 *)sl.lit)[lane] = stv[lane];
+    DSTAMP(5);
+    if (lane < 8) ((u64 *)it.sl.lit)[lane] = stv[lane];
 #endif
-  if (a.phase == 4) return;  // (an error met here is reported by phase 5)
-  if (lane == 0) {
-    a.out_sizes[item] = st == ST_OK ? produced : 0ull;
-    if (a.statuses) a.statuses[item] = a.nvcomp_codes ? to_nvcomp(st) : st;
+    finish_item(a, it, st, produced);
   }
 }
 
 extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_decode_kernel(ZhDecArgs a) {
-  __shared__ DecLds L;
-  decode_body(L, a);
+  __shared__ PassLds<Pass::Whole> L;
+  decode_body<Pass::Whole>(L, a);
 }
-
-// The split pipeline's phase 4 with the small LDS layout (a.phase == 4)
 extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_tables_kernel(ZhDecArgs a) {
-  __shared__ DecLdsTab L;
-  decode_body(L, a);
+  __shared__ PassLds<Pass::Tables> L;
+  decode_body<Pass::Tables>(L, a);
+}
+extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_rest_kernel(ZhDecArgs a) {
+  __shared__ PassLds<Pass::Rest> L;
+  decode_body<Pass::Rest>(L, a);
 }
 
-// Phase 3: execute the block of a buffer deferred by phase 1 (its sequence records are in
-// the slot) and finish the frame.  Its own kernel with only the execution window in LDS
-// (ExecLds, ~9 KB against DecLds' ~16 KB), so twice as many buffers execute per CU.
+// Execute the block of a deferred buffer (its sequence records are in the slot) and finish the
+// frame.  Its own kernel with only the execution window in LDS (ExecLds, 3.6 KB against DecLds'
+// 16.8 KB), so more buffers execute per CU.
 constexpr u32 EXEC_STAGE = 2048;  // (8192: 87.8 GB/s, 1024: 92.9, 2048: 92.8, 3072: 92.4; profiles/r06o_dec_exec_ab.json)
 struct ExecLds {
   static constexpr bool kStartMap = true;
@@ -1651,20 +1731,11 @@ struct ExecLds {
 
 extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_exec_kernel(ZhDecArgs a) {
   __shared__ ExecLds L;
-  u32 const item = a.item0 + blockIdx.x, lane = lane_id();
-  const u8 *const src = (const u8 *)(a.in_ptrs ? a.in_ptrs[item] : a.one_in);
-  u8 *const dst = (u8 *)(a.in_ptrs ? a.out_ptrs[item] : a.one_out);
-  u64 const cap = a.out_caps ? (u64)a.out_caps[item] : a.out_cap_all;
-  Slot sl;
-  sl.lit = a.ws + (size_t)item * a.slot_bytes;
-  sl.lit_cap = a.block_cap;
-  sl.seq = (u64 *)(sl.lit + a.lit_bytes);
-  sl.seq_cap = a.seq_cap;
-  const u8 *const dend = a.dict ? a.dict + a.dict_n : nullptr;
-  s64 const dlen = a.dict ? (s64)(a.dict_n - a.dict_off) : 0;
+  u32 const lane = lane_id();
+  Item const it = item_view(a, blockIdx.x);
   if (lane < 4) L.wvs[64 + lane] = 0x7FFFFFFF;
   __syncthreads();
-  DecHandoff *const ho = handoff(a, item);
+  DecHandoff *const ho = it.ho;
   if (uni(ho->flag) != 1) return;
   LitSrc lits;
   lits.g = (const u8 *)uni64(ho->litg);
@@ -1682,9 +1753,9 @@ extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_exec_kernel(ZhD
   u64 produced = 0;
   if (uni(ho->sbad) || sumLL > lits.n || lits.n + sumML > BLOCKSIZE_MAX) {
     st = ST_CORRUPT;
-  } else if (lits.n + sumML > cap) {
+  } else if (lits.n + sumML > it.cap) {
     st = ST_SMALL;
-  } else if (!execute_block(L, sl, dst, 0, lits, nseq, lits.n - (u32)sumLL, dend, dlen, xs)) {
+  } else if (!execute_block(L, it.sl, it.dst, 0, lits, nseq, lits.n - (u32)sumLL, it.dend, it.dlen, xs)) {
     st = ST_CORRUPT;
   } else {
     produced = lits.n + sumML;
@@ -1692,19 +1763,15 @@ extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_exec_kernel(ZhD
   }
   if (st == ST_OK && ipc != ~0ull) {
     __threadfence_block();
-    if ((u32)zh_xxh64(dst, produced) != rd32(src + ipc)) st = ST_CHECKSUM;
+    if ((u32)zh_xxh64(it.dst, produced) != rd32(it.src + ipc)) st = ST_CHECKSUM;
   }
 #ifdef ZH_STAMPS
   xs[0] = __builtin_amdgcn_s_memtime() - xt0;
   xs[6] = nseq;
   xs[7] = produced;
-  if (lane < 8) ((u64 *)sl.lit)[lane] = xs[lane];
+  if (lane < 8) ((u64 *)it.sl.lit)[lane] = xs[lane];
 #endif
-  if (lane == 0) {
-    a.out_sizes[item] = st == ST_OK ? produced : 0ull;
-    if (a.statuses) a.statuses[item] = a.nvcomp_codes ? to_nvcomp(st) : st;
-  }
-  return;
+  finish_item(a, it, st, produced);
 }
 
 // Sequence bitstreams of deferred buffers, the quad sequence kernel: FOUR lanes per buffer, 16
@@ -1713,7 +1780,7 @@ extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_exec_kernel(ZhD
 // trajectory: tools/seq_sync.py measured 0 of 240 guesses synchronising over whole C3 blocks),
 // so the step itself is what has to get shorter.  Lane q of a quad owns one table: 0 = offsets, 1 = match lengths,
 // 2 = literal lengths, 3 = the record (repcodes, ring).  A step is the same instruction stream
-// for all of them: one table read each (entries repacked by phase 1 as newState | symbol << 9
+// for all of them: one table read each (entries repacked by defer_block as newState | symbol << 9
 // | extra bits << 16 | state bits << 24), three quad broadcasts (DPP) give every lane the
 // bit offsets of its two fields (extra bits in the order OF, ML, LL from the top, then the
 // states LL, ML, OF), two 64-bit reads of a 32-byte window the previous step staged in LDS
@@ -1726,7 +1793,7 @@ extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_exec_kernel(ZhD
 // four times as many waves to share the SIMDs), and 4-32 buffers per wave with the tables staged
 // in LDS (32- or 16-bit entries): slower, both isolated and pipelined -- LDS-limited occupancy, no
 // shorter chain (profiles/r02m_dec_seq.json).  Tried on the quad kernel and not kept (DESIGN.md
-// "Decoder"): items mapped to the XCD their phase 1 ran on, an early touch of the next table line.
+// "Decoder"): items mapped to the XCD their walker pass ran on, an early touch of the next table line.
 constexpr u32 DQ_BUF = 16;  // buffers per wave
 constexpr u32 DQ_RUN = 32;  // records per ring run (256 bytes per buffer)
 
@@ -1757,7 +1824,7 @@ typedef __attribute__((address_space(3))) void *lvoid;
 
 extern "C" __global__ __launch_bounds__(64) void zh_dec_seq_kernel(ZhDecArgs a, u32 nitems) {
   // highest issue priority: the chains are issue-latency bound and share SIMDs with the waves of
-  // the pipeline's other phases
+  // the pipeline's other kernels
   __builtin_amdgcn_s_setprio(3);
   __shared__ u32 info[4][64];  // baselines by code: OF (1 << code), ML, LL, none
   __shared__ __attribute__((aligned(16))) u32 win[2][DQ_BUF][16];  // stream windows, 64 B per quad
@@ -1768,15 +1835,15 @@ extern "C" __global__ __launch_bounds__(64) void zh_dec_seq_kernel(ZhDecArgs a, 
   info[2][lane] = lane < 36 ? c_LL_info[lane] & 0xFFFFFFu : 0u;
   info[3][lane] = 0u;
   __syncthreads();
-  u32 const it = a.item0 + blockIdx.x * DQ_BUF + b, end = a.item0 + nitems;
-  if (it >= end) return;  // (quad-uniform from here on: the four lanes read the same buffer)
+  u32 const it = blockIdx.x * DQ_BUF + b;
+  if (it >= nitems) return;  // (quad-uniform from here on: the four lanes read the same buffer)
   DecHandoff *const ho = handoff(a, it);
   if (ho->flag != 1) return;
   const u32 *const tq = ho->tabs + (q == 0 ? 512u : q == 1 ? 768u : 0u);
   const u8 *const sp = (const u8 *)ho->sp;
   u32 const nseq = ho->nseq, lg = ho->lg;
   s32 const n = (s32)ho->rem;
-  u64 *const seq = (u64 *)(a.ws + (size_t)it * a.slot_bytes + a.lit_bytes);
+  u64 *const seq = item_slot(a, it).seq;
   u32 const lastb = n > 0 ? sp[n - 1] : 0u;
   bool const bad = lastb == 0;
   s32 pos = bad ? 0 : 8 * (n - 1) + (s32)hb32(lastb);
@@ -1865,81 +1932,41 @@ extern "C" __global__ __launch_bounds__(64) void zh_dec_seq_kernel(ZhDecArgs a, 
   if (q == 3) ho->sbad = (bad || pos != 0 || big) ? 1u : 0u;
 }
 
-namespace {
-struct DecPipeTag {};
-}  // namespace
-
 namespace zh {
 u32 dec_lds_bytes() { return (u32)sizeof(DecLds); }
-hipError_t launch_decompress(const ZhDecArgs &a0, u32 nitems, hipStream_t stream) {
+hipError_t launch_decompress(const ZhDecArgs &a, u32 nitems, hipStream_t stream) {
   if (!nitems) return hipSuccess;
-  // ZH_DEC_SYNC=1 (diagnostics only): synchronise and report after each of the three kernels
+  // ZH_DEC_SYNC=1 (diagnostics only): the one-stream path, synchronised and reported after each kernel
   static const bool dbg = getenv("ZH_DEC_SYNC") != nullptr;
-  // items [first, first + cnt): phase 1, the sequence kernel, phase 3, in order on s;
-  // after_p1 (optional) is recorded once phase 1 is queued
-  auto group = [&](u32 first, u32 cnt, hipStream_t s, hipEvent_t after_p1) {
-    auto check = [&](const char *k) {
-      if (!dbg) return;
-      hipError_t e = hipStreamSynchronize(s);
-      fprintf(stderr, "zh_decode: %s -> %s\n", k, hipGetErrorString(e));
-    };
-    ZhDecArgs a = a0;
-    a.item0 = first;
-    a.phase = 1;
-    hipLaunchKernelGGL(zh_decode_kernel, dim3(cnt), dim3(DEC_THREADS), 0, s, a);
-    check("phase 1");
-    if (after_p1) (void)hipEventRecord(after_p1, s);
-    hipLaunchKernelGGL(zh_dec_seq_kernel, dim3((cnt + DQ_BUF - 1) / DQ_BUF), dim3(64), 0, s, a, cnt);
-    check("sequences");
-    hipLaunchKernelGGL(zh_dec_exec_kernel, dim3(cnt), dim3(DEC_THREADS), 0, s, a);
-    check("phase 3");
+  auto check = [&](const char *k) {
+    if (!dbg) return;
+    hipError_t e = hipStreamSynchronize(stream);
+    fprintf(stderr, "zh_decode: %s -> %s\n", k, hipGetErrorString(e));
   };
-  // Large batches run as G groups on staggered streams (zh_pipe.h): group k's phase 1 starts
-  // once group k-1's phase 1 is done, so the sequence kernel of a group (one wave per 64
-  // buffers, a ~7 ms issue-latency-bound chain whatever the group size) overlaps the phase 1
-  // of the later group and the execution of the earlier one.  The end is about phase 1 of
-  // every group + one chain + the last group's execution, so the first group is the larger
-  // (2 : 1).  Measured (profiles/r02m_dec_seq.json): G = 1 / 2 / 3 / 4 / 8 -> 56.8 / 59.1 /
-  // 56.0 / 56.2 / 36.6 GB/s, 2 : 1 and 3 : 1 splits 59.3 / 59.7.  Re-measured in round 4 with
-  // the current kernels (tools/dec_ab.sh, profiles/r04zd_decode_groups_ab.json): G = 1 / 2 / 3
-  // -> 57.6 / 60.6 / 59.1 GB/s; two groups 1 : 1 / 2 : 1 / 3 : 1 -> 60.6 / 60.6 / 60.5.
-  // Round 6 (quad sequence kernel ~4.3 ms, segment-parallel literals: phase 1 4.5 -> 2.5 ms;
-  // profiles/r06n_dec_hufpar_ab.json): two groups 1 : 1 / 2 : 1 / 3 : 1 -> 87.9 / 85.3 / 85.7
-  // GB/s, three groups 2 : 1 : 1 / 1 : 1 : 1 -> 86.9 / 81.0, four 1 : 1 : 1 : 1 80.5.
-  // Split pipeline: phase 4 (headers + sequence tables of the deferrable buffers, no literals)
-  // gates the sequence kernel, which then runs every chain at once beside phase 5 (the
-  // literals, and whole decodes of the other buffers) on the side stream; phase 3 waits for
-  // both.  The chains no longer wait for the Huffman literals.
-  if (StreamPipe<2> *const sp2 = (!dbg && nitems >= 2048) ? stream_pipe<DecPipeTag, 2>(stream) : nullptr) {
-    std::lock_guard<std::mutex> lk(sp2->mu);
-    hipStream_t const side = sp2->side[0];
-    ZhDecArgs a = a0;
-    a.item0 = 0;
-    a.phase = 4;
-    hipLaunchKernelGGL(zh_dec_tables_kernel, dim3(nitems), dim3(DEC_THREADS), 0, stream, a);
-    (void)hipEventRecord(sp2->first_done[0], stream);
-    (void)hipStreamWaitEvent(side, sp2->first_done[0], 0);
-    a.phase = 5;
-    hipLaunchKernelGGL(zh_decode_kernel, dim3(nitems), dim3(DEC_THREADS), 0, side, a);
-    (void)hipEventRecord(sp2->done[0], side);
-    hipLaunchKernelGGL(zh_dec_seq_kernel, dim3((nitems + DQ_BUF - 1) / DQ_BUF), dim3(64), 0, stream, a, nitems);
-    (void)hipStreamWaitEvent(stream, sp2->done[0], 0);
-    a.phase = 3;
-    hipLaunchKernelGGL(zh_dec_exec_kernel, dim3(nitems), dim3(DEC_THREADS), 0, stream, a);
+  dim3 const items(nitems), quads((nitems + DQ_BUF - 1) / DQ_BUF), wave(DEC_THREADS);
+  // Split pipeline: the sequence kernel's chains (~4 ms, issue-latency bound whatever the batch)
+  // wait only for Tables and run beside Rest (the Huffman literals) on the side stream; the
+  // execution waits for both.  From 2,048 buffers: the threshold of the two-group pipeline it
+  // replaced (two groups of at least 1,024 buffers; history and measurements in DESIGN.md).
+  if (SidePipe *const p = (!dbg && nitems >= 2048) ? side_pipe(stream) : nullptr) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    hipLaunchKernelGGL(zh_dec_tables_kernel, items, wave, 0, stream, a);
+    (void)hipEventRecord(p->tables_done, stream);
+    (void)hipStreamWaitEvent(p->side, p->tables_done, 0);
+    hipLaunchKernelGGL(zh_dec_rest_kernel, items, wave, 0, p->side, a);
+    (void)hipEventRecord(p->rest_done, p->side);
+    hipLaunchKernelGGL(zh_dec_seq_kernel, quads, dim3(64), 0, stream, a, nitems);
+    (void)hipStreamWaitEvent(stream, p->rest_done, 0);
+    hipLaunchKernelGGL(zh_dec_exec_kernel, items, wave, 0, stream, a);
     return hipGetLastError();
   }
-  constexpr u32 G = 2, W0 = 1, MIN_GROUP = 1024;
-  StreamPipe<G> *p = (!dbg && nitems >= G * MIN_GROUP) ? stream_pipe<DecPipeTag, G>(stream) : nullptr;
-  if (!p) {
-    group(0, nitems, stream, nullptr);
-    return hipGetLastError();
-  }
-  u32 const shares = W0 + G - 1, unit = nitems / shares;  // group 0: W0 shares, others one
-  p->run(stream, [&](u32 k, hipStream_t s, hipEvent_t after_first) {
-    u32 const first = k == 0 ? 0u : (W0 + k - 1) * unit;
-    u32 const last = k + 1 == G ? nitems : (W0 + k) * unit;
-    group(first, last - first, s, after_first);
-  });
+  // One-stream path: small batches, diagnostics, or no side stream
+  hipLaunchKernelGGL(zh_decode_kernel, items, wave, 0, stream, a);
+  check("whole");
+  hipLaunchKernelGGL(zh_dec_seq_kernel, quads, dim3(64), 0, stream, a, nitems);
+  check("sequences");
+  hipLaunchKernelGGL(zh_dec_exec_kernel, items, wave, 0, stream, a);
+  check("execution");
   return hipGetLastError();
 }
 }  // namespace zh

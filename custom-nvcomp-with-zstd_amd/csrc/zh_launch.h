@@ -31,9 +31,7 @@ struct ZhDecArgs {
   u8 *ws;
   u64 slot_bytes;
   u32 lit_bytes, block_cap, seq_cap, nvcomp_codes;
-  u32 ho_off;  // offset of the item's hand-off record inside its slot (split pipeline)
-  u32 phase;   // 0: whole decode in one kernel; 1 / 3: first / last kernel of the split pipeline
-  u32 item0;   // first item of this launch (launch_decompress's pipelined groups)
+  u32 ho_off;  // offset of the item's hand-off record (deferred buffers) inside its slot
   const u8 *dict;  // dictionary (device, whole buffer) or null; its content precedes every frame
   u64 dict_n;      // its size
   u32 dict_off;    // content offset (formatted dictionary: after tables + repcodes; raw: 0)
@@ -43,7 +41,7 @@ struct ZhDecArgs {
 
 namespace zh {
 u32 dec_lds_bytes();
-// Split pipeline: phase-1 kernel, lanes=frames sequence kernel, phase-3 kernel.
+// Walker (one pass; from 2,048 items a tables and a rest pass), sequence kernel, execution kernel.
 hipError_t launch_decompress(const ZhDecArgs &a, u32 nitems, hipStream_t stream);
 hipError_t init_kernels();
 u32 lz_lds_bytes();

@@ -1,11 +1,10 @@
-// zh_pipe.h — side streams + events for the staggered group pipelines (host code).
+// zh_pipe.h — the decoder's side stream (host code).
 //
-// The entropy stage (zh_entropy.hip) and the decoder (zh_decode.hip) split large batches into
-// G groups of consecutive blocks/items on G streams: group k's first, throughput-bound kernel
-// starts once group k-1's first kernel is done, so the latency-bound kernels after it (one
-// wave per few blocks) overlap the next groups' first kernel.  One set per device and per
-// pipeline (Tag), created on the device of the caller's stream at its first large call and
-// kept; a call holds the set's mutex while it enqueues its groups.
+// The split pipeline of zh_decode.hip (launch_decompress) runs one kernel beside the caller's
+// stream: an event orders the side stream after the tables pass, a second one orders the
+// execution after the side stream's kernel.  One set per device, created on the device of the
+// caller's stream at its first large call and kept; a call holds the set's mutex while it
+// enqueues its kernels.
 #ifndef ZH_PIPE_H_
 #define ZH_PIPE_H_
 
@@ -17,41 +16,18 @@
 
 namespace zh {
 
-template <unsigned G>
-struct StreamPipe {
+struct SidePipe {
   std::mutex mu;
-  hipStream_t side[G - 1] = {};
-  hipEvent_t start = nullptr, first_done[G - 1] = {}, done[G - 1] = {};
+  hipStream_t side = nullptr;
+  hipEvent_t tables_done = nullptr, rest_done = nullptr;
   bool ok = true;
-  explicit StreamPipe(int dev) {
+  explicit SidePipe(int dev) {
     int cur = -1;
     ok = hipGetDevice(&cur) == hipSuccess && hipSetDevice(dev) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&start, hipEventDisableTiming) == hipSuccess;
-    for (unsigned k = 0; k + 1 < G; k++) {
-      ok = ok && hipStreamCreateWithFlags(&side[k], hipStreamNonBlocking) == hipSuccess;
-      ok = ok && hipEventCreateWithFlags(&first_done[k], hipEventDisableTiming) == hipSuccess;
-      ok = ok && hipEventCreateWithFlags(&done[k], hipEventDisableTiming) == hipSuccess;
-    }
+    ok = ok && hipStreamCreateWithFlags(&side, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&tables_done, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&rest_done, hipEventDisableTiming) == hipSuccess;
     if (cur >= 0) (void)hipSetDevice(cur);
-  }
-
-  // Enqueue group(k, s, after_first) for k = 0..G-1: group 0 on the caller's stream, the others
-  // on side streams ordered after everything already on it; group(...) records after_first
-  // (when non-null) once its first kernel is queued.  The caller's stream then waits for all.
-  template <class F>
-  void run(hipStream_t stream, F &&group) {
-    std::lock_guard<std::mutex> lk(mu);
-    (void)hipEventRecord(start, stream);
-    for (unsigned k = 0; k < G; k++) {
-      hipStream_t const s = k ? side[k - 1] : stream;
-      if (k) {
-        (void)hipStreamWaitEvent(s, start, 0);
-        (void)hipStreamWaitEvent(s, first_done[k - 1], 0);
-      }
-      group(k, s, k + 1 < G ? first_done[k] : nullptr);
-      if (k) (void)hipEventRecord(done[k - 1], s);
-    }
-    for (unsigned k = 1; k < G; k++) (void)hipStreamWaitEvent(stream, done[k - 1], 0);
   }
 };
 
@@ -64,15 +40,14 @@ inline int stream_device(hipStream_t s) {
   return dev;
 }
 
-// The pipe of (Tag, device of s); null if its streams could not be created
-template <class Tag, unsigned G>
-StreamPipe<G> *stream_pipe(hipStream_t s) {
+// The side pipe of the device of s; null if its stream or events could not be created
+inline SidePipe *side_pipe(hipStream_t s) {
   static std::mutex mu;
-  static std::map<int, std::unique_ptr<StreamPipe<G>>> pipes;
+  static std::map<int, std::unique_ptr<SidePipe>> pipes;
   int const dev = stream_device(s);
   std::lock_guard<std::mutex> lk(mu);
   auto &p = pipes[dev];
-  if (!p) p.reset(new StreamPipe<G>(dev));
+  if (!p) p.reset(new SidePipe(dev));
   return p->ok ? p.get() : nullptr;
 }
 

@@ -268,7 +268,7 @@ def test_c3_full_batch_decode(torch_cuda):
 def test_split_pipeline_mixed_batch_matches_small_batches(torch_cuda, mgr, libzstd):
     """Batches of >= 2048 buffers take the split pipeline (zh_decode.hip launch_decompress:
     a tables-only pass, the sequence kernel beside the literals pass, execution); smaller ones
-    the one-pass phase 1.  A 2,304-buffer batch mixing deferrable frames (this library's and
+    the one-pass walker.  A 2,304-buffer batch mixing deferrable frames (this library's and
     libzstd's), raw / RLE / multi-block frames, damaged frames (some fail only in the literals
     pass, after the tables pass deferred them) and truncated ones must give every buffer the
     same status and bytes as the same frames decoded 576 at a time, and agree with libzstd."""
@@ -313,3 +313,43 @@ def test_split_pipeline_mixed_batch_matches_small_batches(torch_cuda, mgr, libzs
         agree += (s == 0) == ok_ref
     assert agree >= len(frames) - 40, agree
     assert sum(1 for s in st if s == 0) >= 1900
+
+
+def test_split_pipeline_checksum_through_handoff(torch_cuda, mgr, libzstd):
+    """The content checksum of a deferred buffer travels in its hand-off record (`ipc`) and is
+    verified by zh_dec_exec_kernel; in the split pipeline the tables pass writes it.  2,048
+    buffers (the threshold, so the smallest batch that takes the split pipeline) of one 4 KiB
+    chunk cycle through this library's frame with the checksum enabled, libzstd's checksum=True
+    frame, and a copy of each with its last byte (the checksum's) flipped.  Intact frames give
+    status 0 and the chunk, flipped ones the checksum-failed status (libzstd rejects them too),
+    and the batch equals the same list decoded 512 at a time on the one-stream path."""
+    import cuda_zstd
+    import zh_frames as F
+
+    chunk = T.gen(T.DG_TEXT, 1, 2048, 4096)
+    own = cuda_zstd.Manager(3, checksum=True).compress(torch_cuda.from_numpy(chunk).cuda()).cpu().numpy().tobytes()
+    pool = [own, T.zstd_compress(chunk, level=3, checksum=True)]
+    for f in pool:  # deferrable: one compressed block with sequences, then the checksum
+        (b,) = F.walk(f)
+        assert b["type"] == "compressed" and b["checksum"] and b["nseq"] > 0
+        assert T.zstd_decompress(f, len(chunk)) == chunk.tobytes()
+    pool += [f[:-1] + bytes([f[-1] ^ 0xFF]) for f in pool]
+    for f in pool[2:]:
+        with pytest.raises(AssertionError, match="libzstd"):
+            T.zstd_decompress(f, len(chunk))
+    dev = [_dev(torch_cuda, f) for f in pool]
+
+    def decode(lo, hi):
+        outs, st = mgr.decompress_batch([dev[i % 4] for i in range(lo, hi)], [len(chunk)] * (hi - lo), raise_on_error=False)
+        return [o.cpu().numpy().tobytes() for o in outs], st
+
+    outs, st = decode(0, 2048)
+    assert st == [0, 0, CHECKSUM, CHECKSUM] * 512
+    assert all(o == chunk.tobytes() for o, s in zip(outs, st) if s == 0)
+    small_o, small_s = [], []
+    for k in range(0, 2048, 512):
+        o, s = decode(k, k + 512)
+        small_o += o
+        small_s += s
+    assert st == small_s
+    assert outs == small_o

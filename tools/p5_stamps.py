@@ -1,4 +1,4 @@
-"""Diagnostic: per-part cycle breakdown of the split pipeline's phase 5 (zh_decode_kernel) (s_memtime, lane 0 of each
+"""Diagnostic: per-part cycle breakdown of the split pipeline's Rest pass ("phase 5", zh_dec_rest_kernel) (s_memtime, lane 0 of each
 item) from the -DZH_STAMPS build (tools/libcuda_zstd_hip_stamps.so).  Not a benchmark.
 Phases: 0 frame/raw blocks, 1 literals (Huffman), 2 sequence tables, 3 sequence
 bitstream, 4 execution, 5 tail."""
