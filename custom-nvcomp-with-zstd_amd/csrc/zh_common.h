@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "zstd_hip_params.h"
+#include "zh_dict_ent.h"
 
 typedef uint8_t u8;
 typedef uint16_t u16;
@@ -35,7 +36,18 @@ enum : u32 {
                        // behind the last ZH_DEEP_PRE content bytes
   ZH_F_LDM = 64u,      // one-sequence block of a long-distance match (zh_ldm.hip): n = 0, so K1-K4 skip the slot; its
                        // bytes and staged size are already written, and the gather copies them like any block's
+  ZH_F_DICTENT = 128u, // CompressionConfig::dict_entropy with a formatted dictionary (ZhWorkspace::dent): the first
+                       // block of a frame starts from the dictionary's repcodes and may reuse its entropy tables
+                       // (treeless literals, Repeat_Mode sequence tables)
+  ZH_F_STATS = 256u,   // statistics pass of dictionary finalisation: the entropy kernel adds every block's literal
+                       // histogram and LL / OF / ML code counts to ZhWorkspace::stats (integer atomics)
 };
+// ZhWorkspace::stats: u32[ZH_STATS_WORDS] = literal byte counts | LL | OF | ML code counts (64 each)
+#define ZH_STATS_LIT 0u
+#define ZH_STATS_LL 256u
+#define ZH_STATS_OF 320u
+#define ZH_STATS_ML 384u
+#define ZH_STATS_WORDS 448u
 
 // Per-block workspace carved from the caller's temp buffer.
 //   seq   : ZH_SEQ_CAP u64 records (K1: walk literals before the match | len << 17 | catch-up << 24 |
@@ -77,6 +89,7 @@ static_assert(3u * ZH_K3_SEGS <= ZH_K3_SLOTS, "one lane per (table, segment)");
 #define ZH_FSE_BYTES 4096u
 #define ZH_FSE_TAB_BYTES 3528u  // stLL u16[512] | stOF u16[256] | stML u16[512] | symLL[36] | symOF[32] | symML[53] (8 B each)
 #define ZH_FSE_FIELDS 3840u
+static_assert(ZH_DENT_FSE_BYTES == ZH_FSE_TAB_BYTES, "the dictionary blob holds the tables in the hand-off layout");
 #define ZH_WS_BLOCK_BYTES (ZH_SEQ_BYTES + ZH_LIT_BYTES + ZH_META_BYTES + ZH_FSE_BYTES)
 enum : u32 {
   ZH_FT_STLL = 0, ZH_FT_STOF = 1024, ZH_FT_STML = 1536, ZH_FT_SYLL = 2560, ZH_FT_SYOF = 2848, ZH_FT_SYML = 3104,  // byte offsets
@@ -120,6 +133,10 @@ struct ZhWorkspace {
   // ZH_DEEP_LEVEL only): part of the caller's workspace, so independent calls never share them
   u8 *deep_slots;
   u32 deep_nslots;
+  // The batch dictionary's entropy section as the entropy kernel reads it (ZH_F_DICTENT; null: none)
+  const ZhDictEnt *dent;
+  // The statistics pass's four global histograms (ZH_F_STATS; null: none)
+  u32 *stats;
   __device__ u64 *seq(u32 b) const { return (u64 *)(base + (size_t)b * ZH_WS_BLOCK_BYTES); }
   __device__ u8 *lits(u32 b) const { return base + (size_t)b * ZH_WS_BLOCK_BYTES + ZH_SEQ_BYTES; }
   __device__ u32 *meta(u32 b) const { return (u32 *)(base + (size_t)b * ZH_WS_BLOCK_BYTES + ZH_SEQ_BYTES + ZH_LIT_BYTES); }

@@ -932,6 +932,56 @@ __device__ __forceinline__ void write_status(const ZhBlockDesc &d, u32 b, u32 to
   }
 }
 
+// ---------------- a formatted dictionary's entropy section (ZhDictEnt, ZH_F_DICTENT) ----------------
+constexpr u32 ZH_DENT_LITERALS_MIN = 6;  // libzstd's literal count from which a valid previous Huffman table is tried
+
+// Bits << 8 to code a symbol of normalised count nv with a table of 2^tableLog cells (per lane):
+// zh::dent::bit_cost, the rule the blob's costs were made with
+__device__ __forceinline__ u32 fse_cost8(int nv, u32 tableLog) {
+  if (nv == 0) return ZH_DENT_IMPOSSIBLE;
+  u32 const n = nv < 0 ? 1u : (u32)nv, T = 1u << tableLog;
+  u32 const mbo = n == 1 ? tableLog : tableLog - highbit32(n - 1);
+  u32 const dnb = (mbo << 16) - (n << mbo);
+  u32 const minNb = dnb >> 16;
+  u32 const delta = ((minNb + 1) << 16) - (dnb + T);
+  return ((minNb + 1) << ZH_DENT_COST_SHIFT) - ((delta << ZH_DENT_COST_SHIFT) >> tableLog);
+}
+
+// Treeless literals (Literals_Block_Type 3) with the dictionary's Huffman table against what the
+// literals section would be otherwise (cLit: 0 raw, 1 RLE, else the Huffman section's size after
+// its header).  The literals must be covered: every byte value that occurs has a code.  Takes the
+// smaller, ties to treeless; then the dictionary's code is in hval / hnb, the stream sizes in
+// ssz[0..3] and the section's size after its header in ssz[4].  Wave-uniform result.
+__device__ __noinline__ bool dict_literals(const ZhDictEnt *dent, const u32 *hist, const u8 *lits, u32 nl, u32 cLit, u32 minGain, u32 lhSize,
+                                           bool single, u16 *hval, u8 *hnb, u8 *dnb, u32 *ssz) {
+  u32 const lane = lane_id();
+  u32 bad = 0;
+  for (u32 i = lane; i < 256; i += 64) bad |= (hist[i] != 0 && !((dent->hmask[i >> 5] >> (i & 31u)) & 1u)) ? 1u : 0u;
+  if (__ballot(bad != 0)) return false;
+  ((u32 *)dnb)[lane] = ((const u32 *)dent->hnb)[lane];
+  wave_sync();
+  u32 const seg = (nl + 3) / 4, ns = single ? 1 : 4;
+  u32 cs = single ? 0 : 6;
+  u32 sz[4] = {0, 0, 0, 0};
+  for (u32 k = 0; k < ns; k++) {
+    u32 const a = single ? 0 : k * seg, e = single ? nl : (k < 3 ? (k + 1) * seg : nl);
+    u32 bits = 0;
+    for (u32 i = a + lane; i < e; i += 64) bits += dnb[lits[i]];
+    sz[k] = (wave_sum(bits) + 1 + 7) >> 3;
+    cs += sz[k];
+  }
+  u32 const fl = 1 + (nl > 31) + (nl > 4095);
+  u32 const other = (cLit == 0 || cLit >= nl - minGain) ? fl + nl : cLit == 1 ? fl + 1 : lhSize + cLit;
+  if (lhSize + cs > other) return false;
+  wave_sync();
+  ((u32 *)hnb)[lane] = ((const u32 *)dent->hnb)[lane];
+  ((u32 *)hval)[lane] = ((const u32 *)dent->hval)[lane];
+  ((u32 *)hval)[64 + lane] = ((const u32 *)dent->hval)[64 + lane];
+  if (lane == 0) { ssz[0] = sz[0]; ssz[1] = sz[1]; ssz[2] = sz[2]; ssz[3] = sz[3]; ssz[4] = cs; }
+  wave_sync();
+  return true;
+}
+
 extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const ZhBlockDesc *__restrict__ blocks, ZhWorkspace ws, u32 window_log,
                                                                              u32 cfg_block_size, u64 *__restrict__ item_size,
                                                                              u32 *__restrict__ item_status, u32 *__restrict__ blk_size) {
@@ -964,6 +1014,15 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
   const u32 *meta = ws.meta(b);
   u32 const nseq_raw = meta[0], nlit = meta[1], rle = meta[2] == 1u, k1hist = meta[2] == ZH_META_K1HIST;
   Out const o{d.dst, d.dst_cap};
+  // the dictionary's entropy section (CompressionConfig::dict_entropy): first block of a frame only
+  constexpr u32 DENT_FLAGS = ZH_F_FIRST | ZH_F_DICT | ZH_F_DICTENT;
+  const ZhDictEnt *const dent = (d.flags & DENT_FLAGS) == DENT_FLAGS ? ws.dent : nullptr;
+  // fewest literals worth an entropy-coded section: with the dictionary's Huffman table (no tree
+  // description to pay for) libzstd's 6, else its 64
+  // statistics pass of dictionary finalisation (ZH_F_STATS): every block's literal histogram and
+  // sequence code counts are added to ws.stats, so the histogram is built for any literal count
+  u32 *const stats = (d.flags & ZH_F_STATS) ? ws.stats : nullptr;
+  u32 const lit_min = stats ? 1u : (dent && !k1hist) ? ZH_DENT_LITERALS_MIN : ZH_COMPRESS_LITERALS_SIZE_MIN + 1u;
   if (wave == 0 && lane == 0) sw[0] = 0;  // (wave 1's SW overlaps wave 0's layout: never touched)
 #ifdef ZH_STAMPS
   u64 stamp_prev = __builtin_amdgcn_s_memtime();
@@ -1019,7 +1078,7 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
     u64 *seq = ws.seq(b);
     u32 op = body0;
     // the literal histogram, both waves (wave 1 before its sequence work), into wave 0's hist
-    if (nlit > ZH_COMPRESS_LITERALS_SIZE_MIN) {
+    if (nlit >= lit_min) {
       u32 *const hist0 = (u32 *)(smem_all + OFF_HIST);
       u32 const nl = nlit;
       if (k1hist) {
@@ -1077,6 +1136,9 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
       bool const single = nl < 256;
       u32 cLit = 0, hsz = 0, huffLog = 0;
       u32 *ssz = misc + 8;  // per-stream byte sizes (LDS, wave-uniform)
+      if (stats && nl)
+        for (u32 i = lane; i < 256; i += 64)
+          if (u32 const c = hist[i]) atomicAdd(&stats[ZH_STATS_LIT + i], c);
       if (nl > ZH_COMPRESS_LITERALS_SIZE_MIN) {
         u32 mx = 0, lg = 0;
         for (u32 i = lane; i < 256; i += 64) { u32 c = hist[i]; if (c) mx = max(mx, i); lg = max(lg, c); }
@@ -1115,7 +1177,10 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
         }
       }
       ZH_STAMP(2);  // stream sizes
-      if (cLit == 0 || cLit >= nl - minGain) {
+      bool treeless = false;
+      if (dent && nl >= lit_min) treeless = dict_literals(dent, hist, lits, nl, cLit, minGain, lhSize, single, hval, hnb, wts, ssz);
+      if (treeless) { cLit = ssz[4]; hsz = 0; }
+      if (!treeless && (cLit == 0 || cLit >= nl - minGain)) {
         // raw literals
         u32 const fl = 1 + (nl > 31) + (nl > 4095);
         u32 v = fl == 1 ? (nl << 3) : fl == 2 ? ((1u << 2) + (nl << 4)) : ((3u << 2) + (nl << 4));
@@ -1128,17 +1193,18 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
           copy_bytes(o, op + fl, lits, nl);
         }
         op += fl + nl;
-      } else if (cLit == 1) {
+      } else if (!treeless && cLit == 1) {
         u32 const fl = 1 + (nl > 31) + (nl > 4095);
         u32 v = fl == 1 ? (1 + (nl << 3)) : fl == 2 ? (1 + (1u << 2) + (nl << 4)) : (1 + (3u << 2) + (nl << 4));
         if (lane < fl) o.put(op + lane, (u8)(v >> (8 * lane)));
         if (lane == 0) o.put(op + fl, lits[0]);
         op += fl + 1;
       } else {
-        u64 lhc;
-        if (lhSize == 3) lhc = 2 + ((u64)(!single) << 2) + ((u64)nl << 4) + ((u64)cLit << 14);
-        else if (lhSize == 4) lhc = 2 + (2u << 2) + ((u64)nl << 4) + ((u64)cLit << 18);
-        else lhc = 2 + (3u << 2) + ((u64)nl << 4) + ((u64)cLit << 22);
+        u64 lhc;  // (Literals_Block_Type 2: Huffman with its tree, 3: treeless)
+        if (lhSize == 3) lhc = ((u64)(!single) << 2) + ((u64)nl << 4) + ((u64)cLit << 14);
+        else if (lhSize == 4) lhc = (2u << 2) + ((u64)nl << 4) + ((u64)cLit << 18);
+        else lhc = (3u << 2) + ((u64)nl << 4) + ((u64)cLit << 22);
+        lhc += treeless ? 3u : 2u;
         if (lane < lhSize) o.put(op + lane, (u8)(lhc >> (8 * lane)));
         op += lhSize;
         for (u32 i = lane; i < hsz; i += 64) o.put(op + i, hbuf[i]);
@@ -1215,6 +1281,7 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
       // (oracle/zstd_oracle.c orc_resolve_repcodes is the serial form.)
       u32 cr0 = 1, cr1 = 4, cr2 = 8;  // reps before the batch's first sequence
       if (!(d.flags & ZH_F_FIRST) || (d.flags & ZH_F_DICT)) { cr0 = cr1 = cr2 = 0; }  // dictionary frames: its repcodes never referenced
+      if (dent) { cr0 = dent->reps[0]; cr1 = dent->reps[1]; cr2 = dent->reps[2]; }      // ... unless asked to
       u64 const below = (1ull << lane) - 1ull;
       CodeTabs ct;
       ct.load();
@@ -1357,6 +1424,9 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
       wave_sync();
     }
     ZH_STAMP(4);  // merge + repcodes + codes + histograms
+    if (stats)
+      for (u32 i = lane; i < 192; i += 64)
+        if (u32 const c = hist[i]) atomicAdd(&stats[ZH_STATS_LL + i], c);
     if (nbSeq > 0) {
       ZH_STAMP(5);
       // tables: LL, OF, ML (ZSTD_selectEncodingType for strategy dfast + ZSTD_buildCTable)
@@ -1384,7 +1454,48 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
           else if (defAllowed && ((nbSeq < (1u << defLog)) || (mostFrequent < (nbSeq >> (defLog - 1))))) type = 0;
           else type = 2;
           u32 bmax = 0, blog = 0;
-          if (type == 1) {
+          // FSE_Compressed_Mode: normalised counts -> norm[], the table description -> hbuf + hposw
+          // (returns its size), the table's shape -> bmax / blog
+          auto fse_candidate = [&](int &nv) {
+            u32 nb1 = nbSeq;
+            u32 const tl = fse_optimal_table_log(fseLog, nbSeq, mx, 2);
+            u32 const lc = last_code[t];
+            if (lane_value(c, lc) > 1) {
+              if (lane == lc) c--;
+              nb1--;
+            }
+            nv = fse_normalize_wave(norm, tl, c, nb1, mx, nb1 >= 2048, lane, scr->cumul);
+            bmax = mx; blog = tl;
+            return fse_write_ncount_wave(hbuf + hposw, nv, mx, tl, lane);
+          };
+          u32 fse_hs = 0;
+          bool fse_done = false;
+          if (dent && type != 1) {
+            // by cost (bits << 8, integers) among Repeat_Mode with the dictionary's table, the
+            // predefined table where allowed and a table of the block's own; ties in that order
+            u32 const c0 = c, big = 0xFFFFFFFFu;
+            u32 const dc = dent->cost[t][lane];
+            u32 const costRep = __ballot(c0 != 0 && dc >= ZH_DENT_IMPOSSIBLE) ? big : wave_sum(c0 * dc);
+            u32 costDef = big, costFse = big;
+            if (defAllowed) costDef = wave_sum(c0 * fse_cost8(lane <= defMax ? (int)defNorm[lane] : 0, defLog));
+            if (mostFrequent < nbSeq) {
+              int nv;
+              fse_hs = fse_candidate(nv);
+              fse_done = true;
+              if (fse_hs) costFse = (fse_hs << (3 + ZH_DENT_COST_SHIFT)) + wave_sum(c0 * fse_cost8(nv, blog));
+            }
+            if (costRep != big && costRep <= costDef && costRep <= costFse) type = 3;
+            else if (costDef <= costFse) type = costDef != big ? 0 : type;
+            else type = 2;
+          }
+          if (type == 3) {
+            // the dictionary's table, as built at load (nothing goes to hbuf)
+            u32 const so = t == 0 ? ZH_FT_STLL : t == 1 ? ZH_FT_STOF : ZH_FT_STML, yo = t == 0 ? ZH_FT_SYLL : t == 1 ? ZH_FT_SYOF : ZH_FT_SYML;
+            const u32 *const src = (const u32 *)(dent->fse + so);
+            for (u32 i = lane; i < (t == 1 ? 128u : 256u); i += 64) ((u32 *)st)[i] = src[i];
+            if (lane <= maxSym) sy[lane] = ((const FseSym *)(dent->fse + yo))[lane];
+            logsw[t] = dent->logs[t];
+          } else if (type == 1) {
             u32 const fc = first_code[t];
             if (lane == 0) {
               st[0] = 0; st[1] = 0;
@@ -1398,21 +1509,14 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
             bmax = defMax; blog = defLog;
             logsw[t] = defLog;
           } else {
-            u32 nb1 = nbSeq;
-            u32 const tl = fse_optimal_table_log(fseLog, nbSeq, mx, 2);
-            u32 const lc = last_code[t];
-            if (lane_value(c, lc) > 1) {
-              if (lane == lc) c--;
-              nb1--;
-            }
-            int const nv = fse_normalize_wave(norm, tl, c, nb1, mx, nb1 >= 2048, lane, scr->cumul);
-            hposw += fse_write_ncount_wave(hbuf + hposw, nv, mx, tl, lane);
-            bmax = mx; blog = tl;
-            logsw[t] = tl;
+            int nv;
+            if (!fse_done) fse_hs = fse_candidate(nv);
+            hposw += fse_hs;
+            logsw[t] = blog;
           }
           typesw |= type << (6 - 2 * t);
           wave_sync();
-          if (type != 1) fse_build_ctable_par(st, sy, tsym, norm, bmax, blog, scr);
+          if (type == 0 || type == 2) fse_build_ctable_par(st, sy, tsym, norm, bmax, blog, scr);
           wave_sync();
         }
         if (lane == 0) {

@@ -33,6 +33,8 @@
 #include "cuda_zstd_nvcomp.h"
 #include "zh_adaptive.h"
 #include "zh_dict.h"
+#include "zh_dict_entropy.h"
+#include "zh_dict_finalize.h"
 #include "zh_dict_train.h"
 #include "zh_launch.h"
 #include "zh_seek.h"
@@ -421,6 +423,11 @@ struct DevDict {
   u32 *deep_prev = nullptr, *deep_head = nullptr;
   u8 *deep_stg = nullptr;
   u32 deep_P = 0, deep_split = 0;
+  // the entropy section of a formatted dictionary as the entropy kernel reads it (zh_dict_entropy.h),
+  // built at load (owned dictionaries only; has_ent false: raw content, or a section the encoder
+  // cannot use): CompressionConfig::dict_entropy
+  ZhDictEnt *ent = nullptr;
+  bool has_ent = false;
   std::vector<u8> host;  // the loaded bytes (a reload of the same dictionary keeps everything)
   // stream-ordered launches that may still read the buffers: one event per stream, recorded
   // after each launch (the blocking entry points have finished reading when they return)
@@ -437,6 +444,7 @@ struct DevDict {
     if (deep_prev) (void)hipFree(deep_prev);
     if (deep_head) (void)hipFree(deep_head);
     if (deep_stg) (void)hipFree(deep_stg);
+    if (ent) (void)hipFree(ent);
   }
   // raw-content view of device-resident history (never freed here)
   static void view(DevDict &v, const void *p, size_t bytes) {
@@ -447,6 +455,7 @@ struct DevDict {
     v.id = 0;
     v.tabs_P = 0;  // (a moving history window: hashed by every block)
     v.deep_P = 0;
+    v.has_ent = false;
   }
   const u8 *content() const { return d + off; }
   size_t content_n() const { return n - off; }
@@ -510,9 +519,20 @@ struct DevDict {
         deep_split = sp;
       }
     }
+    has_ent = false;
+    if (co) {  // a formatted dictionary: its Huffman code, FSE encoding tables, bit costs and repcodes
+      ZhDictEnt he;
+      size_t co2 = 0;
+      if (zh::dent::parse(h.data(), bytes, &he, &co2) && co2 == co) {
+        if (!ent && hipMalloc(&ent, sizeof(ZhDictEnt)) != hipSuccess) ent = nullptr;
+        if (ent && hipMemcpy(ent, &he, sizeof(he), hipMemcpyHostToDevice) == hipSuccess) has_ent = true;
+      }
+    }
     host.swap(h);
     return Status::SUCCESS;
   }
+  // the blob the entropy kernel takes when the configuration asks for the dictionary's entropy section
+  const ZhDictEnt *dent(const CompressionConfig &c) const { return c.dict_entropy && n && has_ent ? ent : nullptr; }
   void fill(ZhDecArgs &a) const {
     if (!n) return;
     a.dict = d;
@@ -573,6 +593,7 @@ class ZstdBatchManager::Impl {
   void *pinned = nullptr;
   size_t pinned_bytes = 0;
   DevDict mgr_dict, call_dict;  // set_dictionary()'s / compress()'s per-call dictionary
+  u32 *stats_dev = nullptr;     // collect_entropy_stats: run() asks the entropy kernel for its histograms (ZH_F_STATS)
   const DevDict *active() const { return mgr_dict.n ? &mgr_dict : nullptr; }
 
   explicit Impl(const CompressionConfig &c) : config(c) {}
@@ -631,8 +652,10 @@ class ZstdBatchManager::Impl {
     ZhItemDesc *hi = (ZhItemDesc *)(h + L.items);
     u8 *staging = base + L.staging;
     size_t b = 0;
+    const ZhDictEnt *const dent = dd ? dd->dent(config) : nullptr;
     u32 const frame_flags = (config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY ? ZH_F_CHECKSUM : 0u) |
-                            (config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u);
+                            (config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u) | (dent ? ZH_F_DICTENT : 0u) |
+                            (stats_dev ? ZH_F_STATS : 0u);
     for (size_t i = 0; i < count; i++) {
       bool const sd = split_dict_of(has_dict, config.level);
       size_t const n = in_sizes[i], nb = ldm ? 0 : blocks_of(n, sd), bs = block_size_of(n, sd);
@@ -667,6 +690,8 @@ class ZstdBatchManager::Impl {
     set_deep_dict(ws, dd);
     ws.deep_slots = L.deep_slots ? base + L.deep : nullptr;
     ws.deep_nslots = (u32)L.deep_slots;
+    ws.dent = dent;
+    ws.stats = stats_dev;
     hipError_t e = zh::launch_compress((const ZhBlockDesc *)(base + L.descs), (u32)nblocks, ws, config.window_log, config.block_size,
                                        (u64 *)(base + L.item_size), (u32 *)(base + L.item_status), (u32 *)(base + L.blk_size),
                                        (const ZhItemDesc *)(base + L.items), (u32)count, staged,
@@ -791,6 +816,39 @@ size_t ZstdBatchManager::get_compress_temp_size(size_t n) const {
   // long-distance matching: three slots per cell, the table and the sample lists (a dictionary
   // given at compress() switches it off: the plain layout must fit too)
   return ldm_applies(pimpl_->config, n, false) ? std::max(plain, ldm_layout(pimpl_->config, n).total) : plain;
+}
+
+Status ZstdBatchManager::collect_entropy_stats(const void *const *d_ptrs, const size_t *sizes, size_t count, unsigned int *counts,
+                                               hipStream_t stream) {
+  std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
+  if (!d_ptrs || !sizes || !counts || count == 0) return Status::ERROR_INVALID_PARAMETER;
+  std::vector<size_t> isz(sizes, sizes + count), osz(count), off(count + 1, 0);
+  for (size_t i = 0; i < count; i++) {
+    if (!d_ptrs[i] || sizes[i] == 0) return Status::ERROR_INVALID_PARAMETER;
+    osz[i] = estimate_compressed_size(sizes[i], pimpl_->config.level);
+    off[i + 1] = off[i] + ((osz[i] + 255) & ~(size_t)255);
+  }
+  bool const sd = split_dict_of(pimpl_->active() != nullptr, pimpl_->config.level);
+  size_t nb = 0;
+  bool staged = false;
+  for (size_t s : isz) { size_t const k = blocks_of(s, sd); nb += k; staged |= k > 1; }
+  size_t const temp_bytes = WsLayout::make(nb, count, staged, pimpl_->config.level >= ZH_DEEP_LEVEL).total + 256;
+  u8 *buf = nullptr;
+  size_t const stats_off = (off[count] + 255) & ~(size_t)255, temp_off = stats_off + 4096;
+  if (hipMalloc(&buf, temp_off + temp_bytes) != hipSuccess) return Status::ERROR_OUT_OF_MEMORY;
+  Status s = hipMemsetAsync(buf + stats_off, 0, ZH_STATS_WORDS * sizeof(u32), stream) == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
+  if (s == Status::SUCCESS) {
+    std::vector<void *> op(count);
+    for (size_t i = 0; i < count; i++) op[i] = buf + off[i];
+    std::vector<Status> st(count);
+    pimpl_->stats_dev = (u32 *)(buf + stats_off);
+    s = pimpl_->run(d_ptrs, isz.data(), count, op.data(), osz.data(), st.data(), buf + temp_off, temp_bytes, stream, pimpl_->active());
+    pimpl_->stats_dev = nullptr;
+  }
+  if (s == Status::SUCCESS && hipMemcpy(counts, buf + stats_off, ZH_STATS_WORDS * sizeof(u32), hipMemcpyDeviceToHost) != hipSuccess)
+    s = Status::ERROR_CUDA_ERROR;
+  (void)hipFree(buf);
+  return s;
 }
 
 Status ZstdBatchManager::ldm_plan(const void *d_src, size_t size, unsigned int *host_records, size_t capacity, size_t *num_records, void *temp,
@@ -1109,15 +1167,17 @@ Status ZstdBatchManager::compress_batch_device(const void *const *d_in_ptrs, con
   u32 *item_status = d_statuses ? (u32 *)d_statuses : (u32 *)(base + L.item_status);
   bool const ck = pimpl_->config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY;
   u32 const hist = pimpl_->config.window_log >= ZH_HIST_WINDOW_LOG ? 1u : 0u;
+  const ZhDictEnt *const dent = dd ? dd->dent(pimpl_->config) : nullptr;
   hipError_t e = zh::launch_plan(d_in_ptrs, d_in_sizes, (u32)count, (u32)bpi, d_out_ptrs, cap, base + L.staging, (ZhBlockDesc *)(base + L.descs),
                                  (ZhItemDesc *)(base + L.items), item_size, item_status,
-                                 (ck ? ZH_F_CHECKSUM : 0u) | (pimpl_->config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u),
+                                 (ck ? ZH_F_CHECKSUM : 0u) | (pimpl_->config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u) | (dent ? ZH_F_DICTENT : 0u),
                                  dd ? dd->content() : nullptr, dd ? (u32)dd->content_n() : 0u, dd ? dd->id : 0u, hist, stream);
   if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
   ZhWorkspace ws{base + L.blocks, (u32 *)(base + L.counter), dd && dd->tabs_P ? dd->tabs : nullptr, dd ? dd->tabs_P : 0u};
   set_deep_dict(ws, dd);
   ws.deep_slots = L.deep_slots ? base + L.deep : nullptr;
   ws.deep_nslots = (u32)L.deep_slots;
+  ws.dent = dent;
   e = zh::launch_compress((const ZhBlockDesc *)(base + L.descs), (u32)nblocks, ws, pimpl_->config.window_log, pimpl_->config.block_size, item_size,
                           item_status, (u32 *)(base + L.blk_size), (const ZhItemDesc *)(base + L.items), (u32)count, bpi > 1, ck,
                           pimpl_->config.level, stream);
@@ -1503,6 +1563,52 @@ Status create_dictionary_from_samples(const void *samples_buffer, const size_t *
     sizes.push_back(e - a);
   }
   return train_dictionary(samples, sizes, dict_buffer, dict_size, params, stream);
+}
+Status finalize_dictionary(const void *content, size_t content_size, const std::vector<const void *> &samples,
+                           const std::vector<size_t> &sample_sizes, int level, u32 dict_id, void *out, size_t *out_size, hipStream_t stream) {
+  if (!content || !out || !out_size || samples.empty() || samples.size() != sample_sizes.size()) return Status::ERROR_INVALID_PARAMETER;
+  if (content_size < MIN_DICT_SIZE || content_size > MAX_DICT_SIZE || !is_valid_compression_level(level)) return Status::ERROR_INVALID_PARAMETER;
+  std::vector<u8> c(content_size);
+  Status s = copy_any(c.data(), content, content_size, stream);
+  if (s != Status::SUCCESS) return s;
+  u32 id0 = 0;
+  size_t co = 0;
+  if (!zh::dict_layout(c.data(), c.size(), id0, co)) return Status::ERROR_DICTIONARY_FAILED;
+  c.erase(c.begin(), c.begin() + (ptrdiff_t)co);  // (a formatted dictionary: its content)
+  if (c.size() < MIN_DICT_SIZE) return Status::ERROR_INVALID_PARAMETER;
+  // the samples back to back on the device (16-byte aligned starts), host samples uploaded
+  size_t const n = samples.size();
+  std::vector<size_t> off(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    if (!samples[i] || sample_sizes[i] == 0) return Status::ERROR_INVALID_PARAMETER;
+    off[i + 1] = off[i] + ((sample_sizes[i] + 15) & ~(size_t)15);
+  }
+  u8 *dev = nullptr;
+  if (hipMalloc(&dev, off[n] + 16) != hipSuccess) return Status::ERROR_OUT_OF_MEMORY;
+  std::vector<const void *> ptrs(n);
+  for (size_t i = 0; i < n && s == Status::SUCCESS; i++) {
+    ptrs[i] = dev + off[i];
+    s = copy_any(dev + off[i], samples[i], sample_sizes[i], stream);
+  }
+  std::vector<u32> counts(ZH_STATS_WORDS, 0);
+  if (s == Status::SUCCESS) {
+    ZstdBatchManager m(CompressionConfig::from_level(level));
+    Dictionary view;
+    view.raw_content = c.data();
+    view.raw_size = (u32)c.size();
+    s = m.set_dictionary(view);
+    view.raw_content = nullptr;  // (a view: nothing to free)
+    view.raw_size = 0;
+    if (s == Status::SUCCESS) s = m.collect_entropy_stats(ptrs.data(), sample_sizes.data(), n, counts.data(), stream);
+  }
+  (void)hipFree(dev);
+  if (s != Status::SUCCESS) return s;
+  std::vector<u8> const fd = zh::dfin::finalize(c.data(), c.size(), counts.data(), dict_id);
+  if (fd.empty() || fd.size() > MAX_DICT_SIZE) return Status::ERROR_DICTIONARY_FAILED;
+  if (fd.size() > *out_size) return Status::ERROR_BUFFER_TOO_SMALL;
+  memcpy(out, fd.data(), fd.size());
+  *out_size = fd.size();
+  return Status::SUCCESS;
 }
 u32 get_optimal_dict_size(size_t total) {
   size_t const s = total / 100;
@@ -2325,6 +2431,28 @@ void cuda_zstd_hip_dict_train_profile(int on, double *ms3) {
   if (ms3)
     for (int i = 0; i < 3; i++) ms3[i] = dictionary::g_train_phase_ms[i];
 }
+int cuda_zstd_finalize_dictionary(const cuda_zstd_dict_t *content, const void *const *samples, const size_t *sizes, size_t num, int level,
+                                  unsigned dict_id, hipStream_t stream, cuda_zstd_dict_t **dict_out) {
+  if (!dict_out) return c_err(Status::ERROR_INVALID_PARAMETER);
+  *dict_out = nullptr;
+  if (!content || !content->dict || !samples || !sizes || num == 0) return c_err(Status::ERROR_INVALID_PARAMETER);
+  try {
+    std::vector<u8> out(content->bytes.size() + 512);
+    size_t n = out.size();
+    Status const st = dictionary::finalize_dictionary(content->bytes.data(), content->bytes.size(), std::vector<const void *>(samples, samples + num),
+                                                      std::vector<size_t>(sizes, sizes + num), level, dict_id, out.data(), &n, stream);
+    if (st != Status::SUCCESS) return c_err(st);
+    out.resize(n);
+    u32 id = 0;
+    memcpy(&id, out.data() + 4, 4);
+    auto *h = new cuda_zstd_dict_t;
+    h->set(std::move(out), id);
+    *dict_out = h;
+    return 0;
+  } catch (...) {
+    return c_err(Status::ERROR_OUT_OF_MEMORY);
+  }
+}
 void cuda_zstd_destroy_dictionary(cuda_zstd_dict_t *d) { delete d; }
 // reference DictionaryManager::load_dictionary (include/cuda_zstd_dictionary.h:292-310): a host
 // buffer with raw content or a formatted dictionary (e.g. ZDICT_trainFromBuffer's)
@@ -2565,6 +2693,21 @@ int cuda_zstd_set_long_distance(cuda_zstd_manager_t *m, int enable, unsigned win
   if (window_log) c.window_log = window_log;
   if (hash_log) c.ldm_hash_log = hash_log;
   return c_err(m->manager->configure(c));
+}
+// CompressionConfig::dict_entropy (Dictionaries): the first block of a frame made with a
+// formatted dictionary starts from its repcodes and may reuse its entropy tables.  Off by default;
+// no effect without a dictionary, with raw content or on streaming-history frames.
+int cuda_zstd_set_dict_entropy(cuda_zstd_manager_t *m, int enable) {
+  if (!m || !m->manager) return c_err(Status::ERROR_INVALID_PARAMETER);
+  CompressionConfig c = m->manager->get_config();
+  c.dict_entropy = enable != 0;
+  return c_err(m->manager->configure(c));
+}
+int nvcomp_zstd_batch_set_dict_entropy_v5(nvcomp_zstd_batch_manager_t *m, int enable) {
+  if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
+  CompressionConfig c = m->mgr->batch_manager().get_config();
+  c.dict_entropy = enable != 0;
+  return c_err(m->mgr->batch_manager().configure(c));
 }
 // Content checksum of the manager's frames (0: none, the default)
 int cuda_zstd_set_checksum(cuda_zstd_manager_t *m, int enable) {

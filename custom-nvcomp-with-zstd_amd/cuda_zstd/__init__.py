@@ -70,6 +70,7 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_train_dictionary_device": (i, [vp, psz, sz, sz, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, pvp]),
             "cuda_zstd_hip_dict_train_profile": (None, [i, ctypes.POINTER(ctypes.c_double)]),
             "cuda_zstd_load_dictionary": (vp, [vp, sz]),
+            "cuda_zstd_finalize_dictionary": (i, [vp, pvp, psz, sz, i, ctypes.c_uint, vp, pvp]),
             "cuda_zstd_destroy_dictionary": (None, [vp]),
             "cuda_zstd_set_dictionary": (i, [vp, vp]),
             "cuda_zstd_clear_dictionary": (i, [vp]),
@@ -117,6 +118,8 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_seekable_read": (i, [vp, vp, sz, ctypes.c_ulonglong, sz, vp, psz, i, vp, sz, vp]),
             "cuda_zstd_set_long_distance": (i, [vp, i, ctypes.c_uint, ctypes.c_uint]),
             "cuda_zstd_set_checksum": (i, [vp, i]),
+            "cuda_zstd_set_dict_entropy": (i, [vp, i]),
+            "nvcomp_zstd_batch_set_dict_entropy_v5": (i, [vp, i]),
             "cuda_zstd_hip_ldm_plan": (ctypes.c_longlong, [vp, vp, sz, vp, sz, vp, sz, vp]),
             "cuda_zstd_hip_ldm_profile": (None, [i, ctypes.POINTER(ctypes.c_double)]),
             "cuda_zstd_adaptive_get_temp_size": (sz, [sz]),
@@ -197,9 +200,12 @@ class Manager:
 
     Device tensors in -> device tensors out; host bytes / numpy in -> bytes out."""
 
-    def __init__(self, level: int = 3, long_distance=False, hash_log: int = 0, checksum: bool = False):
+    def __init__(self, level: int = 3, long_distance=False, hash_log: int = 0, checksum: bool = False, dict_entropy: bool = False):
         """long_distance: True = long-distance matching with a 2^27 window (`zstd --long`), an int =
-        that window log (16..31); it applies to compress() of one buffer over 64 KiB."""
+        that window log (16..31); it applies to compress() of one buffer over 64 KiB.
+        dict_entropy: with a formatted dictionary set, the first block of every frame starts from
+        the dictionary's repcodes and may reuse its Huffman / FSE tables (treeless literals,
+        Repeat_Mode); off, frames are what they were."""
         self.level = level
         self._h = lib().cuda_zstd_create_manager(level)
         if not self._h:
@@ -212,6 +218,8 @@ class Manager:
                 raise ZstdError(rc, "cuda_zstd_set_long_distance")
         if checksum:
             lib().cuda_zstd_set_checksum(self._h, 1)
+        if dict_entropy:
+            lib().cuda_zstd_set_dict_entropy(self._h, 1)
 
     def close(self):
         if self._h:
@@ -398,11 +406,15 @@ class Dictionary:
         self._h = handle
 
     @classmethod
-    def train(cls, samples, dict_size: int, k: int = 0, d: int = 0, stream=None) -> "Dictionary":
+    def train(cls, samples, dict_size: int, k: int = 0, d: int = 0, stream=None, finalize: bool = False, level: int = 3) -> "Dictionary":
         """COVER training -> raw content; k = segment bytes, d = d-mer bytes (0: 1024 / 8).
+        finalize=True: the trained content goes through finalize(samples, level), so the result is
+        a formatted dictionary (dict_size bytes of content plus its entropy section).
         Host samples (bytes-like / uint8 arrays) train on the host.  Torch CUDA tensors -- a list
         or tuple of them, or one 2-D uint8 tensor with a sample per row -- train on the device
         (cuda_zstd_train_dictionary_device), ordered on `stream`; the bytes are the same."""
+        if finalize:
+            return cls.train(samples, dict_size, k, d, stream).finalize(samples, level, stream=stream)
         if _is_cuda_tensor(samples) or (isinstance(samples, (list, tuple)) and len(samples) and all(_is_cuda_tensor(t) for t in samples)):
             return cls._train_device(samples, dict_size, k, d, stream)
         raw = [bytes(s) for s in samples]
@@ -438,6 +450,42 @@ class Dictionary:
         if rc:
             raise ZstdError(rc, "cuda_zstd_train_dictionary_device")
         return cls(h.value, "cuda_zstd_train_dictionary_device")
+
+    def finalize(self, samples, level: int = 3, dict_id: int = 0, stream=None) -> "Dictionary":
+        """This dictionary's content plus entropy tables -> a formatted RFC 8878 dictionary
+        (libzstd's ZDICT_finalizeDictionary; cuda_zstd_finalize_dictionary).  The tables come from
+        compressing the samples against the content at `level` on the device: host samples
+        (bytes-like / uint8 arrays) are uploaded, torch CUDA tensors (a list, or one 2-D uint8
+        tensor with a sample per row) are read in place.  dict_id 0: libzstd's hash rule.  Use the
+        result with Manager(..., dict_entropy=True)."""
+        keep = []
+        if _is_cuda_tensor(samples):
+            torch = _torch()
+            if samples.dim() != 2 or samples.dtype != torch.uint8:
+                raise TypeError("Dictionary.finalize: a single tensor must be 2-D uint8, one sample per row")
+            samples = list(samples.contiguous())
+        ptrs, sizes = [], []
+        for s in samples:
+            if _is_cuda_tensor(s):
+                t = s.contiguous().view(_torch().uint8).view(-1)
+                keep.append(t)
+                ptrs.append(t.data_ptr())
+                sizes.append(t.numel())
+            else:
+                b = bytes(s)
+                cb = ctypes.create_string_buffer(b, max(len(b), 1))
+                keep.append(cb)
+                ptrs.append(ctypes.addressof(cb))
+                sizes.append(len(b))
+        n = len(ptrs)
+        h = ctypes.c_void_p()
+        if keep and any(_is_cuda_tensor(t) for t in keep):
+            _torch().cuda.synchronize()  # the samples' producers have finished
+        rc = lib().cuda_zstd_finalize_dictionary(self._h, (ctypes.c_void_p * max(n, 1))(*ptrs), (ctypes.c_size_t * max(n, 1))(*sizes), n, level,
+                                                 dict_id, _stream_ptr(stream), ctypes.byref(h))
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_finalize_dictionary")
+        return Dictionary(h.value, "cuda_zstd_finalize_dictionary")
 
     @classmethod
     def load(cls, buf) -> "Dictionary":
@@ -509,11 +557,14 @@ class BatchedCompressor:
     """Stream-ordered batched compression of equal-capacity chunk slots
     (nvcomp_zstd_batched_compress_async_v5).  Used by bench.py."""
 
-    def __init__(self, level: int = 3, chunk_size: int = 64 * 1024, checksum: bool = False):
+    def __init__(self, level: int = 3, chunk_size: int = 64 * 1024, checksum: bool = False, dict_entropy: bool = False):
+        """dict_entropy: as Manager's (nvcomp_zstd_batch_set_dict_entropy_v5)."""
         self._h = lib().nvcomp_zstd_batch_create_v5(level, chunk_size, 1 if checksum else 0)
         if not self._h:
             raise ZstdError(INVALID, "nvcomp_zstd_batch_create_v5")
         self.chunk_size = chunk_size
+        if dict_entropy:
+            lib().nvcomp_zstd_batch_set_dict_entropy_v5(self._h, 1)
 
     def close(self):
         if self._h:
@@ -573,6 +624,9 @@ class BatchedCompressor:
             out.data_ptr(), out.numel(), d_out_size.data_ptr(), d_status.data_ptr(), temp.data_ptr(), temp.numel(), _stream_ptr(stream))
         if rc:
             raise ZstdError(rc, "cuda_zstd_seekable_pack_async")
+
+
+BatchManager = BatchedCompressor  # the batch manager of the C ABI (nvcomp_zstd_batch_*_v5) under its other name
 
 
 class StreamingManager:

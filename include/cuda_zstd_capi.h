@@ -55,6 +55,12 @@ size_t cuda_zstd_train_dictionary_device_get_temp_size(size_t total_sample_bytes
 int cuda_zstd_train_dictionary_device(const void *d_samples, const size_t *sample_sizes, size_t num_samples, size_t dict_size,
                                       unsigned k, unsigned d, void *d_temp, size_t temp_bytes, hipStream_t stream,
                                       cuda_zstd_dict_t **dict_out);
+/* dictionary::finalize_dictionary: the content of `content` (raw, or a formatted dictionary's) plus
+ * entropy tables gathered by compressing the samples (an array of num_samples host or device
+ * pointers) against it at `level` on the device -> a new formatted dictionary handle in *dict_out
+ * (Dictionary_ID dict_id, or libzstd's hash rule when 0).  Use it with cuda_zstd_set_dict_entropy. */
+int cuda_zstd_finalize_dictionary(const cuda_zstd_dict_t *content, const void *const *samples, const size_t *sample_sizes, size_t num_samples,
+                                  int level, unsigned dict_id, hipStream_t stream, cuda_zstd_dict_t **dict_out);
 void cuda_zstd_destroy_dictionary(cuda_zstd_dict_t *dict);
 int cuda_zstd_set_dictionary(cuda_zstd_manager_t *manager, cuda_zstd_dict_t *dict);
 /* dictionaries: cuda_zstd_train_dictionary is COVER training (raw content);
@@ -128,6 +134,8 @@ size_t nvcomp_zstd_batch_get_batched_temp_size_v5(nvcomp_zstd_batch_manager_t *m
  * manager's set_dictionary).  With a dictionary, chunks over 32 KiB take two history blocks:
  * size the workspace with nvcomp_zstd_batch_get_batched_temp_size_v5 after setting it. */
 int nvcomp_zstd_batch_set_dictionary_v5(nvcomp_zstd_batch_manager_t *mgr, cuda_zstd_dict_t *dict);
+/* cuda_zstd_set_dict_entropy for a batch manager (both batch compress entries) */
+int nvcomp_zstd_batch_set_dict_entropy_v5(nvcomp_zstd_batch_manager_t *mgr, int enable);
 int nvcomp_zstd_batched_compress_async_v5(nvcomp_zstd_batch_manager_t *mgr, const void *const *d_uncompressed_ptrs,
                                           const size_t *d_uncompressed_sizes, size_t max_uncompressed_chunk_bytes,
                                           size_t num_chunks, void *const *d_compressed_ptrs, size_t *d_compressed_sizes,
@@ -293,6 +301,11 @@ int cuda_zstd_adaptive_finalize_host(const unsigned *hist256, unsigned sample_si
  * this feature.  Returns 2 for a window_log outside 16..31; the table size is clamped to
  * 2^10..2^30.  Batch, dictionary and streaming entry points ignore it. */
 int cuda_zstd_set_long_distance(cuda_zstd_manager_t *manager, int enable, unsigned window_log, unsigned hash_log);
+/* Use a formatted dictionary's entropy section when compressing (CompressionConfig::dict_entropy):
+ * the first block of a frame starts from the dictionary's repcodes and may reuse its Huffman and
+ * FSE tables (treeless literals, Repeat_Mode).  0 (the default): frames as before.  No effect
+ * without a dictionary, with raw content, or on streaming-history frames. */
+int cuda_zstd_set_dict_entropy(cuda_zstd_manager_t *manager, int enable);
 /* Content checksum on the manager's frames (0: none, the default). */
 int cuda_zstd_set_checksum(cuda_zstd_manager_t *manager, int enable);
 /* Inspection: the finder's decision per 32 KiB cell of a device buffer, as cuda_zstd_compress would

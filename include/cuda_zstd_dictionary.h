@@ -114,6 +114,20 @@ Status train_dictionary(const std::vector<const void *> &samples, const std::vec
 // sample_offsets[num_samples - 1] + 8192 bytes, whatever the last sample's real length
 Status create_dictionary_from_samples(const void *samples_buffer, const size_t *sample_offsets, size_t num_samples, void *dict_buffer,
                                       size_t dict_size, const DictionaryTrainingParams *params = nullptr, hipStream_t stream = 0);
+// Raw content -> a formatted RFC 8878 section 5 dictionary (libzstd's ZDICT_finalizeDictionary): magic,
+// Dictionary_ID, a Huffman table for the literals, FSE table descriptions for offsets, match
+// lengths and literal lengths, the repcodes 1 / 4 / 8 and the content, unchanged.  The tables
+// come from this library's own compressor: every sample (host or device memory; host samples
+// are uploaded) is compressed as a record against the content at `level` and the entropy
+// kernel's histograms of all blocks are summed on the device.  Every count starts at 1, so the
+// result loads in libzstd; Huffman codes are at most 11 bits, table logs 8 / 9 / 9.  dict_id 0:
+// libzstd's rule, XXH64(content) % (2^31 - 32768) + 32768.  content (host or device memory,
+// MIN_DICT_SIZE bytes or more) may itself be a formatted dictionary: its content is taken.
+// *out_size: capacity of `out` (host memory) in, bytes written out; content_size + 512 always
+// suffices, and the result must fit MAX_DICT_SIZE.  Deterministic; blocks until done.
+// Compress with it and CompressionConfig::dict_entropy to use the tables.
+Status finalize_dictionary(const void *content, size_t content_size, const std::vector<const void *> &samples,
+                           const std::vector<size_t> &sample_sizes, int level, u32 dict_id, void *out, size_t *out_size, hipStream_t stream = 0);
 // ~1 % of the data, clamped to [MIN_DICT_SIZE, MAX_DICT_SIZE], rounded up to a KiB
 u32 get_optimal_dict_size(size_t total_data_size);
 bool is_valid_dictionary_size(size_t size);

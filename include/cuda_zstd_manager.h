@@ -123,6 +123,14 @@ class ZstdBatchManager : public ZstdManager {
   // not split), distance}, three u32 each, copied to host_records (capacity in records).
   // *num_records = cells.  temp_workspace as for compress() of the same size with enable_ldm set.
   // Frames the long-distance plan does not apply to (one block, or over 4 GiB) report 0 records.
+  // Statistics pass of dictionary finalisation (dictionary::finalize_dictionary): the device
+  // buffers in d_ptrs (a host array of `count` device pointers; sizes[i] > 0 bytes each) are
+  // compressed as records against the manager's dictionary at its level, and the entropy kernel
+  // adds every block's literal histogram and LL / OF / ML code counts into counts[448] (host):
+  // literal bytes [0, 256), LL [256, 320), OF [320, 384), ML [384, 448).  The frames are dropped.
+  // Integer atomics: the counts do not depend on scheduling.  Blocks until done; temp memory is
+  // the function's own.
+  Status collect_entropy_stats(const void *const *d_ptrs, const size_t *sizes, size_t count, unsigned int *counts, hipStream_t stream = 0);
   Status ldm_plan(const void *d_src, size_t size, unsigned int *host_records, size_t capacity, size_t *num_records, void *temp_workspace,
                   size_t temp_size, hipStream_t stream = 0);
 
