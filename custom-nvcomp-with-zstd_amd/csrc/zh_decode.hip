@@ -29,7 +29,8 @@
 // ERROR_DICTIONARY_MISMATCH.  With a dictionary (RFC 8878 §5) its content precedes every frame
 // and a formatted one's tables and repcodes seed the frame state.
 // Kernels: the walker decode_body<Pass> (zh_decode_kernel = Whole; split pipeline: zh_dec_tables_kernel
-// = Tables, zh_dec_rest_kernel = Rest), zh_dec_seq_kernel, zh_dec_exec_kernel ("the walker's passes" below).
+// = Tables, zh_dec_rest_kernel = Rest), zh_dec_seq_kernel, zh_dec_exec_kernel ("the walker's passes" below);
+// zh_dec_size_kernel = the walker's Size pass: the decompressed size of every buffer, nothing decoded.
 #include "zh_common.h"
 #include "zh_launch.h"
 #include "zh_pipe.h"
@@ -41,6 +42,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 
 typedef int64_t s64;
 
@@ -84,7 +86,8 @@ constexpr u32 TAB_NONE = 0xFFFFu, TAB_PREDEF = 0xFFFEu;  // tkind; else RLE symb
 // sequence bitstream, execution window.  TAB = the layout of the split pipeline's Tables pass
 // (zh_dec_tables_kernel): no literals, no execution, so the union shrinks to the 320-byte stage
 // of the table descriptions and the window arrays to stubs (7.8 KB instead of 16.8: twice the
-// workgroups per CU).
+// workgroups per CU).  The Size pass (zh_dec_size_kernel) has the same needs and the same layout; the
+// 320 bytes are then also the stage of its sequence bitstream.
 template <bool TAB>
 struct DecLdsT {
   static constexpr bool kStartMap = false;
@@ -761,6 +764,16 @@ __device__ u32 skip_literals(const u8 *bp, u32 bsz) {
   return hs + cs;
 }
 
+// Regenerated_Size of a literals section skip_literals accepted (the Size pass: the section's
+// header lies inside the block)
+__device__ __forceinline__ u32 literals_regen(const u8 *bp) {
+  u32 const h0 = ub(bp);
+  u32 const lt = h0 & 3u, sf = (h0 >> 2) & 3u;
+  if (lt <= 1) return sf == 1 ? rd16(bp) >> 4 : sf == 3 ? rd24(bp) >> 4 : h0 >> 3;
+  u32 const hv = sf <= 1 ? rd24(bp) : rd32(bp);
+  return (hv >> 4) & (sf <= 1 ? 0x3FFu : sf == 2 ? 0x3FFFu : 0x3FFFFu);
+}
+
 __device__ u32 decode_literals(DecLds &L, const u8 *bp, u32 bsz, const Slot &sl, LitSrc &lits, u32 &st) {
   u32 const lane = lane_id();
   if (bsz < 1) { st = ST_CORRUPT; return 0; }
@@ -1224,8 +1237,18 @@ __device__ bool execute_block(LDS &L, const Slot &sl, u8 *ob, s64 fpos, const Li
 // The split pipeline (launch_decompress) cuts it in two: Tables visits only the deferrable
 // buffers, skips their literals and writes the record (no status, no output); Rest decodes the
 // deferred buffers' literals into their records and every other buffer whole.
-enum class Pass { Whole, Tables, Rest };
-template <Pass P> using PassLds = DecLdsT<P == Pass::Tables>;
+// Size (launch_decompress_sizes) is the same walk with nothing decoded: it answers how many bytes
+// the buffer's frames regenerate.  A frame that states its size (Frame_Content_Size) is believed and
+// only its block headers are walked, to find the next frame; one that does not is summed block by
+// block: Block_Size of a raw or RLE block, the literals' Regenerated_Size plus the match lengths of a
+// compressed one (sum_sequences).  No output, no slot, no hand-off record: the Item of this pass
+// has only the input.
+enum class Pass { Whole, Tables, Rest, Size };
+// (Size has Tables' layout under a type of its own: the helpers that are real functions, seq_table and
+// huf_read_weights, are then instantiated for it apart, and the copies Tables calls keep their one
+// caller and their code -- with a second caller they compiled differently and cost Tables 2 VGPRs)
+struct SizeLds : DecLdsT<true> {};
+template <Pass P> using PassLds = std::conditional_t<P == Pass::Size, SizeLds, DecLdsT<P == Pass::Tables>>;
 
 struct DecHandoff {
   u32 tabs[1280];  // DecLds::fse of the block
@@ -1270,6 +1293,17 @@ __device__ __forceinline__ Item item_view(const ZhDecArgs &a, u32 idx) {
   it.ho = handoff(a, idx);
   it.dend = a.dict ? a.dict + a.dict_n : nullptr;
   it.dlen = a.dict ? (s64)(a.dict_n - a.dict_off) : 0;
+  return it;
+}
+// The Size pass's item: the input alone.  Its capacity is unbounded and its sequence count limit
+// the one of a full-size slot, so no check of the walk answers ST_SMALL.
+__device__ __forceinline__ Item size_item_view(const ZhDecArgs &a, u32 idx) {
+  Item it{};
+  it.idx = idx;
+  it.src = (const u8 *)(a.in_ptrs ? a.in_ptrs[idx] : a.one_in);
+  it.srcn = a.in_ptrs ? (u64)a.in_sizes[idx] : a.one_in_size;
+  it.cap = ~0ull;
+  it.sl.seq_cap = BLOCKSIZE_MAX / 3 + 2;
   return it;
 }
 // The item's size and status, by whichever kernel finishes it
@@ -1535,28 +1569,86 @@ __device__ __forceinline__ bool decode_sequences(DecLds &L, const u8 *sp, u32 re
   return r.pos <= 0 && !big;
 }
 
+// ---- the Size pass's reading of the same bitstream: the literal and match lengths summed, nothing
+// kept.  The three state chains step as in decode_sequences and every length's extra bits are read;
+// an offset's extra bits are passed over (its value decides nothing here), no repcodes, no records.
+// The stage is the layout's 320 bytes.  Accepts and rejects as decode_sequences does on what it still
+// sees: the start mark, and a stream that does not end at (or before) its first bit.
+template <class LDS>
+__device__ __forceinline__ bool sum_sequences(LDS &L, const u8 *sp, u32 rem, u32 nseq, u64 &sumLL, u64 &sumML) {
+  constexpr u32 CAP = (u32)sizeof(L.u.sstage) - 16u;
+  BitRevS r;
+  if (!r.start<true>(sp, rem)) return false;
+  u8 *const stg = L.u.sstage;
+  // The container is refilled (and the stage, when it runs out) once per group of fields, not per
+  // field: a refill leaves at least 57 bits below pos, and a step's two length fields take at most
+  // 32 bits, its three state fields at most 26 (as the three initial states).
+  auto need = [&](u32 k) {
+    if (!r.ensure<true>(stg, k)) {
+      u32 lo, hi;
+      r.stage_range((s32)CAP, lo, hi);
+      stage_copy(stg, sp, lo, hi);
+      __syncthreads();
+      r.slo = (s32)uni(lo);
+      r.ensure<true>(stg, k);
+    }
+  };
+  auto take = [&](u32 k) -> u32 {
+    u32 const v = (u32)r.bits(k);
+    r.pos -= (s32)k;
+    return v;
+  };
+  u32 const lgLL = uni(L.tlog[TAB_LL]), lgOF = uni(L.tlog[TAB_OF]), lgML = uni(L.tlog[TAB_ML]);
+  const u32 *TLL = L.fse + tab_off(TAB_LL), *TOF = L.fse + tab_off(TAB_OF), *TML = L.fse + tab_off(TAB_ML);
+  need(lgLL + lgOF + lgML);
+  u32 sLL = take(lgLL), sOF = take(lgOF), sML = take(lgML);
+  for (u32 i = 0; i < nseq; i++) {
+    u32 const eLL = __builtin_amdgcn_readfirstlane(TLL[sLL]), eOF = __builtin_amdgcn_readfirstlane(TOF[sOF]),
+              eML = __builtin_amdgcn_readfirstlane(TML[sML]);
+    r.pos -= (s32)(eOF & 0xFFu);  // the offset's extra bits
+    u32 const mi = __builtin_amdgcn_readfirstlane(L.info[1][eML & 0xFFu]), li = __builtin_amdgcn_readfirstlane(L.info[0][eLL & 0xFFu]);
+    need((mi >> 24) + (li >> 24));
+    sumML += (mi & 0xFFFFFFu) + take(mi >> 24);
+    sumLL += (li & 0xFFFFFFu) + take(li >> 24);
+    if (i + 1 < nseq) {
+      u32 const nLL = (eLL >> 8) & 0xFFu, nML = (eML >> 8) & 0xFFu, nOF = (eOF >> 8) & 0xFFu;
+      need(nLL + nML + nOF);
+      sLL = (eLL >> 16) + take(nLL);
+      sML = (eML >> 16) + take(nML);
+      sOF = (eOF >> 16) + take(nOF);
+    }
+  }
+  return r.pos <= 0;
+}
+
 // ---- the walker: one workgroup (one wave) per input buffer walks its frames and blocks.
 // ST_ELSEWHERE (never reported): the buffer was deferred, zh_dec_exec_kernel finishes it.
 constexpr u32 ST_ELSEWHERE = ~0u;
 template <Pass P>
 __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
   u32 const lane = lane_id();
-  Item const it = item_view(a, blockIdx.x);
+  constexpr bool SZ = P == Pass::Size;  // nothing is decoded: `produced` counts what would be
+  constexpr u32 ST_FULL = SZ ? ST_CORRUPT : ST_SMALL;  // past the capacity (Size: past 64 bits)
+  Item const it = SZ ? size_item_view(a, blockIdx.x) : item_view(a, blockIdx.x);
   const u8 *const src = it.src;
   u64 const srcn = it.srcn, cap = it.cap;
-  if constexpr (P != Pass::Tables) {
+  if constexpr (P != Pass::Tables && !SZ) {
     if (lane < 4) L.wvs[64 + lane] = 0x7FFFFFFF;
   }
   if (lane < 36) L.info[0][lane] = c_LL_info[lane];
   if (lane < 53) L.info[1][lane] = c_ML_info[lane];
   __syncthreads();
-  if constexpr (P != Pass::Rest) {
+  if constexpr (P != Pass::Rest && !SZ) {
     if (lane == 0) it.ho->flag = 0;
   }
 
   u32 st = ST_OK;
   u64 produced = 0, ip = 0;
-  if (!src || (!it.dst && cap)) st = ST_INVALID;
+  if constexpr (SZ) {
+    if (!src || !srcn) st = ST_INVALID;  // (an empty input has no size to report)
+  } else {
+    if (!src || (!it.dst && cap)) st = ST_INVALID;
+  }
 #ifdef ZH_STAMPS
   u64 stv[8] = {}, stp = __builtin_amdgcn_s_memtime();
 #endif
@@ -1566,11 +1658,13 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
     if (st != ST_OK) break;
     ip += fh.size;
     if (fh.skip) continue;
-    if (fh.fcs != ~0ull && fh.fcs > cap - produced) { st = ST_SMALL; break; }
+    // (Size: cap is 2^64 - 1, so this is the sum of the frames' sizes overflowing)
+    if (fh.fcs != ~0ull && fh.fcs > cap - produced) { st = ST_FULL; break; }
     u64 const fstart = produced;
+    bool const stated = SZ && fh.fcs != ~0ull;  // Size: the frame's size is its Frame_Content_Size
     // frame state: repcodes, table kinds
     u32 rep0 = 1, rep1 = 4, rep2 = 8;
-    bool const fdict = a.dict && a.dict_off;  // formatted dictionary: its tables and repcodes
+    bool const fdict = a.dict && a.dict_off && !stated;  // formatted dictionary: its tables and repcodes
     if (lane == 0) {
       L.tkind[0] = L.tkind[1] = L.tkind[2] = TAB_NONE;
       L.hvalid = 0;
@@ -1590,7 +1684,16 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
       u32 const bh = rd24(src + ip);
       u32 const last = bh & 1u, bt = (bh >> 1) & 3u, bsz = bh >> 3;
       ip += 3;
-      u8 *const ob = it.dst + produced;  // this block's first output byte
+      if constexpr (SZ) {
+        if (stated) {  // only the block's extent: where the frame ends
+          u64 const n = bt == 1 ? 1u : bsz;
+          if (bt == 3 || (bt == 2 && bsz >= BLOCKSIZE_MAX) || srcn - ip < n) { st = ST_CORRUPT; break; }
+          ip += n;
+          if (last) break;
+          continue;
+        }
+      }
+      u8 *const ob = SZ ? nullptr : it.dst + produced;  // this block's first output byte
       // the buffer's only block, compressed: its sequences can go to zh_dec_seq_kernel
       bool const only = bt == 2 && produced == 0 && last && ip + bsz + (fh.chk ? 4ull : 0ull) == srcn;
       if constexpr (P == Pass::Tables) {
@@ -1598,14 +1701,14 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
       }
       if (bt == 0) {
         if (srcn - ip < bsz) { st = ST_CORRUPT; break; }
-        if (bsz > cap - produced) { st = ST_SMALL; break; }
-        wave_copy(ob, src + ip, bsz);
+        if (bsz > cap - produced) { st = ST_FULL; break; }
+        if constexpr (!SZ) wave_copy(ob, src + ip, bsz);
         ip += bsz;
         produced += bsz;
       } else if (bt == 1) {
         if (srcn - ip < 1) { st = ST_CORRUPT; break; }
-        if (bsz > cap - produced) { st = ST_SMALL; break; }
-        wave_fill(ob, ub(src + ip), bsz);
+        if (bsz > cap - produced) { st = ST_FULL; break; }
+        if constexpr (!SZ) wave_fill(ob, ub(src + ip), bsz);
         ip += 1;
         produced += bsz;
       } else if (bt == 2) {
@@ -1614,9 +1717,13 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
         LitSrc lits;
         DSTAMP(0);
         u32 ls;
-        if constexpr (P == Pass::Tables) ls = skip_literals(bp, bsz);
+        if constexpr (P == Pass::Tables || SZ) ls = skip_literals(bp, bsz);
         else ls = decode_literals(L, bp, bsz, it.sl, lits, st);
         DSTAMP(1);
+        if constexpr (SZ) {  // all it needs of the literals (nobody else reports a corrupt section)
+          if (ls) lits.n = literals_regen(bp);
+          else st = ST_CORRUPT;
+        }
         if constexpr (P == Pass::Rest) {
           if (produced == 0 && uni(it.ho->flag) == 1) {  // deferred by Tables
             rest_literals(it.ho, ls, lits);
@@ -1643,14 +1750,16 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
           DSTAMP(2);
           sp += tused;
           rem -= tused;
-          if constexpr (P != Pass::Rest) {
+          if constexpr (P != Pass::Rest && !SZ) {
             if (only) {
               defer_block<P>(L, it.ho, sp, rem, nseq, lits, fh.fcs, fh.chk ? ip + bsz : ~0ull, rep0, rep1, rep2);
               st = ST_ELSEWHERE;
               break;
             }
           }
-          if constexpr (P != Pass::Tables) {
+          if constexpr (SZ) {
+            if (!sum_sequences(L, sp, rem, nseq, sumLL, sumML)) { st = ST_CORRUPT; break; }
+          } else if constexpr (P != Pass::Tables) {
             if (!decode_sequences(L, sp, rem, nseq, it.sl.seq, rep0, rep1, rep2, sumLL, sumML)) { st = ST_CORRUPT; break; }
             DSTAMP(3);
           }
@@ -1663,13 +1772,18 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
           // RFC 8878 §3.1.1.2.4: a block regenerates at most Block_Maximum_Size (128 KiB), which
           // also keeps execute_block's u32 window arithmetic in range
           if (total > BLOCKSIZE_MAX) { st = ST_CORRUPT; break; }
-          if (total > cap - produced) { st = ST_SMALL; break; }
-          __threadfence_block();  // the records (and Huffman literals) are read back below
-          __syncthreads();
-          u32 const tl = lits.n - (u32)sumLL;
-          s64 const fpos = (s64)(produced - fstart);  // frame bytes before this block
-          bool const bad = !execute_block(L, it.sl, ob, fpos, lits, nseq, tl, it.dend, it.dlen);
-          DSTAMP(4);
+          if (total > cap - produced) { st = ST_FULL; break; }
+          // (the verdict leaves the `if constexpr` block before it breaks, here and at the checksum:
+          // with the break inside the block the other passes compiled to reordered code)
+          bool bad = false;
+          if constexpr (!SZ) {
+            __threadfence_block();  // the records (and Huffman literals) are read back below
+            __syncthreads();
+            u32 const tl = lits.n - (u32)sumLL;
+            s64 const fpos = (s64)(produced - fstart);  // frame bytes before this block
+            bad = !execute_block(L, it.sl, ob, fpos, lits, nseq, tl, it.dend, it.dlen);
+            DSTAMP(4);
+          }
           if (bad) { st = ST_CORRUPT; break; }
           produced += total;
           ip += bsz;
@@ -1682,11 +1796,16 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
       if (last) break;
     }
     if (P == Pass::Tables || st != ST_OK) break;  // (Tables looks at one block)
-    if (fh.fcs != ~0ull && produced - fstart != fh.fcs) { st = ST_CORRUPT; break; }
+    if constexpr (SZ) {
+      if (stated) produced += fh.fcs;  // believed, as libzstd's ZSTD_findDecompressedSize does; a decode checks it
+    } else {
+      if (fh.fcs != ~0ull && produced - fstart != fh.fcs) { st = ST_CORRUPT; break; }
+    }
     if (fh.chk) {
       if (srcn - ip < 4) { st = ST_CORRUPT; break; }
-      u64 const hx = zh_xxh64(it.dst + fstart, produced - fstart);
-      if ((u32)hx != rd32(src + ip)) { st = ST_CHECKSUM; break; }
+      bool differs = false;  // (Size has no bytes to hash)
+      if constexpr (!SZ) differs = (u32)zh_xxh64(it.dst + fstart, produced - fstart) != rd32(src + ip);
+      if (differs) { st = ST_CHECKSUM; break; }
       ip += 4;
     }
   }
@@ -1695,7 +1814,7 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
     if (st == ST_ELSEWHERE) return;
 #ifdef ZH_STAMPS
     DSTAMP(5);
-    if (lane < 8) ((u64 *)it.sl.lit)[lane] = stv[lane];
+    if (!SZ && lane < 8) ((u64 *)it.sl.lit)[lane] = stv[lane];
 #endif
     finish_item(a, it, st, produced);
   }
@@ -1932,6 +2051,14 @@ extern "C" __global__ __launch_bounds__(64) void zh_dec_seq_kernel(ZhDecArgs a, 
   if (q == 3) ho->sbad = (bad || pos != 0 || big) ? 1u : 0u;
 }
 
+// The walker's Size pass: the decompressed size of every buffer.  Reads in_ptrs / in_sizes (or
+// one_in), the dictionary fields and nvcomp_codes, writes out_sizes and statuses, touches nothing
+// else of the arguments.  (Defined after the decoder's kernels: they keep their places in the code object.)
+extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_size_kernel(ZhDecArgs a) {
+  __shared__ PassLds<Pass::Size> L;
+  decode_body<Pass::Size>(L, a);
+}
+
 namespace zh {
 u32 dec_lds_bytes() { return (u32)sizeof(DecLds); }
 hipError_t launch_decompress(const ZhDecArgs &a, u32 nitems, hipStream_t stream) {
@@ -1967,6 +2094,11 @@ hipError_t launch_decompress(const ZhDecArgs &a, u32 nitems, hipStream_t stream)
   check("sequences");
   hipLaunchKernelGGL(zh_dec_exec_kernel, items, wave, 0, stream, a);
   check("execution");
+  return hipGetLastError();
+}
+hipError_t launch_decompress_sizes(const ZhDecArgs &a, u32 nitems, hipStream_t stream) {
+  if (!nitems) return hipSuccess;
+  hipLaunchKernelGGL(zh_dec_size_kernel, dim3(nitems), dim3(DEC_THREADS), 0, stream, a);
   return hipGetLastError();
 }
 }  // namespace zh

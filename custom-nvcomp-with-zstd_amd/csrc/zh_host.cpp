@@ -1215,6 +1215,27 @@ Status ZstdBatchManager::decompress_batch_device(const void *const *d_in_ptrs, c
   return pimpl_->mgr_dict.n ? pimpl_->mgr_dict.note_use(stream) : Status::SUCCESS;
 }
 
+// The decompressed size of every buffer, on the device (zh_dec_size_kernel): one launch, no
+// workspace, no allocation, no synchronisation.  The manager's dictionary goes in as it does for
+// decompress_batch_device (Dictionary_ID checks; a formatted one's tables serve first blocks).
+Status ZstdBatchManager::get_decompressed_sizes_async(const void *const *d_ptrs, const size_t *d_sizes, size_t count, size_t *d_out_sizes,
+                                                      int *d_statuses, hipStream_t stream, bool nvcomp_codes) {
+  std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
+  Status s = ensure_kernels();
+  if (s != Status::SUCCESS) return s;
+  if (!count) return Status::SUCCESS;
+  if (!d_ptrs || !d_sizes || !d_out_sizes || count > 0xFFFFFFFFull) return Status::ERROR_INVALID_PARAMETER;
+  ZhDecArgs a{};
+  pimpl_->mgr_dict.fill(a);
+  a.in_ptrs = d_ptrs;
+  a.in_sizes = d_sizes;
+  a.out_sizes = d_out_sizes;
+  a.statuses = (u32 *)d_statuses;
+  a.nvcomp_codes = nvcomp_codes ? 1u : 0u;
+  if (zh::launch_decompress_sizes(a, (u32)count, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+  return pimpl_->mgr_dict.n ? pimpl_->mgr_dict.note_use(stream) : Status::SUCCESS;
+}
+
 // ============================================================================
 // Streaming manager (reference src/cuda_zstd_manager.cu:6043-6455).  compress_chunk: each chunk
 // an independent frame (:6306-6310).  compress_chunk_with_history: the chunk is compressed with
@@ -1948,6 +1969,13 @@ Status NvcompV5BatchManager::decompress_async(const void *const *d_in, const siz
   return r != Status::SUCCESS ? r : w;
 }
 
+// nvcompBatchedZstdGetDecompressSizeAsync: device arrays only, stream-ordered, nvcomp codes
+Status NvcompV5BatchManager::get_decompress_sizes_async(const void *const *d_compressed_ptrs, const size_t *d_compressed_bytes,
+                                                        size_t *d_uncompressed_bytes, int *d_statuses, size_t num_chunks, hipStream_t stream) {
+  return pimpl_->mgr.get_decompressed_sizes_async(d_compressed_ptrs, d_compressed_bytes, num_chunks, d_uncompressed_bytes, d_statuses, stream,
+                                                  true);
+}
+
 Status get_metadata_async(const void *d, size_t n, NvcompV5Metadata *m, hipStream_t) {
   if (!m) return Status::ERROR_INVALID_PARAMETER;
   size_t s;
@@ -2621,6 +2649,16 @@ int nvcomp_zstd_batched_decompress_async_v5(nvcomp_zstd_batch_manager_t *m, cons
   if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
   return c_err(
       m->mgr->batch_manager().decompress_batch_device(d_in, d_in_sizes, d_out_caps, max_out, n, d_out, d_out_sizes, d_statuses, t, tb, s));
+}
+int nvcomp_zstd_batched_get_decompress_size_async_v5(nvcomp_zstd_batch_manager_t *m, const void *const *d_in, const size_t *d_in_sizes,
+                                                     size_t *d_out_sizes, int *d_statuses, size_t n, hipStream_t s) {
+  if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
+  return c_err(m->mgr->get_decompress_sizes_async(d_in, d_in_sizes, d_out_sizes, d_statuses, n, s));
+}
+int cuda_zstd_get_decompressed_sizes_async(cuda_zstd_manager_t *m, const void *const *d_ptrs, const size_t *d_sizes, size_t count,
+                                           size_t *d_out_sizes, int *d_statuses, hipStream_t stream) {
+  if (!m || !m->manager) return c_err(Status::ERROR_INVALID_PARAMETER);
+  return c_err(m->manager->get_decompressed_sizes_async(d_ptrs, d_sizes, count, d_out_sizes, d_statuses, stream));
 }
 
 cuda_zstd_hybrid_engine_t *cuda_zstd_hybrid_create(const cuda_zstd_hybrid_config_t *c) {

@@ -43,6 +43,10 @@ namespace zh {
 u32 dec_lds_bytes();
 // Walker (one pass; from 2,048 items a tables and a rest pass), sequence kernel, execution kernel.
 hipError_t launch_decompress(const ZhDecArgs &a, u32 nitems, hipStream_t stream);
+// Size pass of the walker: out_sizes[i] = the bytes item i's frames regenerate (exact with or without
+// a Frame_Content_Size), statuses[i] (optional) as in decode.  Reads in_ptrs / in_sizes (or one_in),
+// the dictionary fields and nvcomp_codes; no workspace, no output pointers.  One launch, no sync.
+hipError_t launch_decompress_sizes(const ZhDecArgs &a, u32 nitems, hipStream_t stream);
 hipError_t init_kernels();
 u32 lz_lds_bytes();
 u32 entropy_lds_bytes();

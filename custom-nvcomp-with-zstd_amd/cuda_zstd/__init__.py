@@ -91,6 +91,8 @@ def lib() -> ctypes.CDLL:
             "nvcomp_zstd_batch_decompress_async_v5": (i, [vp, vp, vp, sz, vp, vp, vp, sz, vp]),
             "nvcomp_zstd_batched_decompress_get_temp_size_v5": (sz, [sz, sz]),
             "nvcomp_zstd_batched_decompress_async_v5": (i, [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
+            "nvcomp_zstd_batched_get_decompress_size_async_v5": (i, [vp, vp, vp, vp, vp, sz, vp]),
+            "cuda_zstd_get_decompressed_sizes_async": (i, [vp, vp, vp, sz, vp, vp, vp]),
             "cuda_zstd_write_metadata_frame": (i, [vp, sz, i, psz, vp]),
             "cuda_zstd_stream_create": (vp, [i]),
             "cuda_zstd_stream_destroy": (None, [vp]),
@@ -334,24 +336,25 @@ class Manager:
 
     def decompress(self, frame, capacity: int = None, stream=None):
         """GPU-decode one device buffer (frames, concatenated) into a new device tensor of
-        at most `capacity` bytes (cuda_zstd_decompress); capacity None: the frame header's
-        content size.  Host bytes in -> bytes out (reference PyManager.decompress)."""
+        at most `capacity` bytes (cuda_zstd_decompress); capacity None: the exact size from
+        decompressed_sizes (frames without a content size and concatenated frames included).
+        Host bytes in -> bytes out (reference PyManager.decompress)."""
         if _is_host(frame):
             return _host_bytes(self.decompress(_to_device(frame), capacity, stream))
-        auto = capacity is None
-        if auto:
-            capacity = _frame_size(frame)
         torch = _torch()
         frame = frame.contiguous().view(torch.uint8)
-        # a derived capacity (the first frame's content size, or 16x the input without one)
-        # grows on BUFFER_TOO_SMALL: concatenated frames, frames without a content size
-        for _ in range(4 if auto else 1):
+        guess = False
+        if capacity is None:
+            capacity, guess = self._capacities([frame], stream)[0]
+        # a guessed capacity (the size query rejected the buffer: the first frame's content size, or
+        # 16x the input without one) grows on BUFFER_TOO_SMALL, and the decoder reports the error
+        for _ in range(4 if guess else 1):
             out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=frame.device)
             ws = self._workspace(lib().cuda_zstd_get_decompress_workspace_size(self._h, frame.numel()))
             size = ctypes.c_size_t(capacity)
             rc = lib().cuda_zstd_decompress(self._h, frame.data_ptr(), frame.numel(), out.data_ptr(), ctypes.byref(size), ws.data_ptr(),
                                             ws.numel(), _stream_ptr(stream))
-            if rc == TOO_SMALL and auto:
+            if rc == TOO_SMALL and guess:
                 capacity *= 4
                 continue
             if rc:
@@ -362,17 +365,19 @@ class Manager:
     def decompress_batch(self, frames: Sequence, capacities: Sequence[int] = None, stream=None, raise_on_error=True):
         """ZstdBatchManager::decompress_batch over device tensors: one GPU launch for all.
         Returns the decoded tensors (and, with raise_on_error=False, the nvcomp codes).
-        capacities None: each frame header's content size; host inputs give bytes back."""
+        capacities None: the exact sizes from one decompressed_sizes launch for the batch (a buffer
+        that query rejects gets a guessed capacity, and the decoder's status for it is reported);
+        host inputs give bytes back."""
         if len(frames) and all(_is_host(f) for f in frames):
             outs = self.decompress_batch([_to_device(f) for f in frames], capacities, stream, raise_on_error)
             if raise_on_error:
                 return [_host_bytes(o) for o in outs]
             return [_host_bytes(o) for o in outs[0]], outs[1]
-        if capacities is None:
-            capacities = [_frame_size(f) for f in frames]
         torch = _torch()
         n = len(frames)
         ins = [f.contiguous().view(torch.uint8) for f in frames]
+        if capacities is None:
+            capacities = [c for c, _ in self._capacities(ins, stream)]
         offs = [0]
         for c in capacities:
             offs.append(offs[-1] + ((max(c, 1) + 255) // 256) * 256)
@@ -393,6 +398,42 @@ class Manager:
                     raise ZstdError(st[k], f"cuda_zstd_decompress_batch item {k}")
             return res
         return res, list(st)
+
+    def decompressed_sizes(self, frames: Sequence, stream=None, raise_on_error=True):
+        """The decompressed size of every buffer (frames, concatenated), computed on the device
+        (cuda_zstd_get_decompressed_sizes_async): one launch and one copy back for the whole batch.
+        Exact whether or not a frame states its content size -- frames of streaming writers do not.
+        Returns a list of ints (and, with raise_on_error=False, the status values: 0, or what a
+        decode of that buffer reports, its size then 0).  Host inputs are uploaded first."""
+        torch = _torch()
+        n = len(frames)
+        if n == 0:
+            return [] if raise_on_error else ([], [])
+        ins = [(_to_device(f) if _is_host(f) else f).contiguous().view(torch.uint8) for f in frames]
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            args = torch.tensor([t.data_ptr() for t in ins] + [t.numel() for t in ins], dtype=torch.int64).cuda()
+            res = torch.empty(2 * n, dtype=torch.int64, device="cuda")  # n sizes, then n int32 statuses
+            rc = lib().cuda_zstd_get_decompressed_sizes_async(self._h, args.data_ptr(), args.data_ptr() + 8 * n, n, res.data_ptr(),
+                                                              res.data_ptr() + 8 * n, s.cuda_stream)
+            if rc:
+                raise ZstdError(rc, "cuda_zstd_get_decompressed_sizes_async")
+            host = res.cpu()
+        sizes = [v & 0xFFFFFFFFFFFFFFFF for v in host[:n].tolist()]
+        st = host[n:].view(torch.int32)[:n].tolist()
+        if raise_on_error:
+            for k in range(n):
+                if st[k] != OK:
+                    raise ZstdError(st[k], f"cuda_zstd_get_decompressed_sizes_async item {k}")
+            return sizes
+        return sizes, st
+
+    def _capacities(self, ins, stream):
+        """(capacity, guessed) per device buffer for a decode without given capacities: the exact
+        size from one decompressed_sizes launch; where that rejects a buffer, _frame_size's guess, so
+        that the decoder is the one to report the buffer's error."""
+        sizes, st = self.decompressed_sizes(ins, stream, raise_on_error=False)
+        return [(max(sz, 1), False) if c == OK else (_frame_size(f), True) for f, sz, c in zip(ins, sizes, st)]
 
 
 class Dictionary:
@@ -551,6 +592,18 @@ class BatchedDecompressor:
             _stream_ptr(stream))
         if rc:
             raise ZstdError(rc, "nvcomp_zstd_batched_decompress_async_v5")
+
+    def get_sizes_async(self, d_in_ptrs, d_in_sizes, d_out_sizes, d_status, stream=None):
+        """The decompressed size of every buffer, on the device
+        (nvcomp_zstd_batched_get_decompress_size_async_v5): int64 device tensors of pointers and
+        sizes in, sizes (int64) and nvcomp codes (int32, or None) out; one launch, stream-ordered,
+        no workspace.  Exact whether or not a frame states its content size."""
+        n = d_in_ptrs.numel()
+        rc = lib().nvcomp_zstd_batched_get_decompress_size_async_v5(
+            self._h, d_in_ptrs.data_ptr(), d_in_sizes.data_ptr(), d_out_sizes.data_ptr(), d_status.data_ptr() if d_status is not None else None, n,
+            _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batched_get_decompress_size_async_v5")
 
 
 class BatchedCompressor:
@@ -806,6 +859,10 @@ def decompress(frame, capacity: int = None, stream=None):
 
 def decompress_batch(frames, capacities=None, stream=None):
     return Manager(3).decompress_batch(frames, capacities, stream)
+
+
+def decompressed_sizes(frames, stream=None, raise_on_error=True):
+    return Manager(3).decompressed_sizes(frames, stream, raise_on_error)
 
 
 def seekable_compress(data, frame_size: int = 65536, level: int = 3, checksums: bool = False, stream=None):

@@ -162,6 +162,24 @@ int nvcomp_zstd_batched_decompress_async_v5(nvcomp_zstd_batch_manager_t *mgr, co
                                             size_t *d_actual_sizes, int *d_statuses, void *d_temp_storage, size_t temp_storage_bytes,
                                             hipStream_t stream);
 
+/* Batched decompressed-size query on the device (nvCOMP nvcompBatchedZstdGetDecompressSizeAsync
+ * shape).  All arrays are DEVICE arrays; one launch; nothing is synchronised or allocated and no
+ * workspace is needed; num_chunks / count == 0 succeeds and launches nothing.
+ * d_uncompressed_bytes[i] receives the bytes that all frames of buffer i regenerate (skippable frames
+ * skipped): a frame's Frame_Content_Size where present (believed, as ZSTD_findDecompressedSize
+ * does; a decode rejects a frame whose field lies), otherwise the sum over its blocks, found by
+ * reading the sequence bitstreams without decoding anything -- exact for frames of streaming
+ * writers, which carry no size.  For every buffer the decoder accepts, the size is exactly what it
+ * produces.  d_statuses (optional, may be NULL) receives per buffer the code a decode reports: the
+ * nvcomp-style code (the _v5 entry) or the cuda_zstd status value (the manager entry); 2 for an empty
+ * or null buffer; the size is 0 wherever the status is not 0.  The handle's dictionary, if set,
+ * is used as by the batched decompress entry. */
+int nvcomp_zstd_batched_get_decompress_size_async_v5(nvcomp_zstd_batch_manager_t *mgr, const void *const *d_compressed_ptrs,
+                                                     const size_t *d_compressed_bytes, size_t *d_uncompressed_bytes, int *d_statuses,
+                                                     size_t num_chunks, hipStream_t stream);
+int cuda_zstd_get_decompressed_sizes_async(cuda_zstd_manager_t *manager, const void *const *d_ptrs, const size_t *d_sizes, size_t count,
+                                           size_t *d_out_sizes, int *d_statuses, hipStream_t stream);
+
 /* ---------------- hybrid API (reference include/cuda_zstd_hybrid.h:296-359) ---------------- */
 typedef struct cuda_zstd_hybrid_engine_t cuda_zstd_hybrid_engine_t;
 typedef struct {

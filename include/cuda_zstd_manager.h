@@ -108,6 +108,17 @@ class ZstdBatchManager : public ZstdManager {
                                  size_t max_uncompressed_chunk_bytes, size_t count, void *const *d_out_ptrs, size_t *d_out_sizes,
                                  int *d_statuses, void *temp_workspace, size_t temp_size, hipStream_t stream);
   static size_t get_batch_device_decompress_temp_size(size_t count, size_t max_uncompressed_chunk_bytes);
+  // The decompressed size of every buffer, computed on the device (nvCOMP's
+  // nvcompBatchedZstdGetDecompressSizeAsync): all arrays are device arrays, one launch, no
+  // workspace, no allocation, no synchronisation.  d_out_sizes[i] = the bytes all frames of buffer i
+  // regenerate: a frame's Frame_Content_Size where it has one (believed, as libzstd's
+  // ZSTD_findDecompressedSize does), else summed from its blocks, so frames of streaming writers
+  // are answered exactly too.  d_statuses[i] (optional) = Status value, or nvcomp code when
+  // nvcomp_codes; the size is 0 where the status is not success.  For every buffer the decoder
+  // accepts this is exactly what it produces; an empty or null buffer is ERROR_INVALID_PARAMETER.
+  // The manager's dictionary is used as in decompress_batch_device.
+  Status get_decompressed_sizes_async(const void *const *d_ptrs, const size_t *d_sizes, size_t count, size_t *d_out_sizes, int *d_statuses,
+                                      hipStream_t stream, bool nvcomp_codes = false);
 
   // Streaming history (what the reference's compress_chunk_with_history does by
   // passing its device window as a raw-content dictionary, src/cuda_zstd_manager.cu:6327-6418):

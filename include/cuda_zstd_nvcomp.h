@@ -44,6 +44,11 @@ class NvcompV5BatchManager {
   Status decompress_async(const void *const *d_compressed_ptrs, const size_t *compressed_sizes, size_t num_chunks,
                           void *const *d_uncompressed_ptrs, size_t *uncompressed_sizes, void *d_temp_storage,
                           size_t temp_storage_bytes, hipStream_t stream = 0);
+  // nvcompBatchedZstdGetDecompressSizeAsync: device arrays only, stream-ordered, nothing is
+  // synchronised or allocated; d_statuses (optional) gets nvcomp codes
+  // (ZstdBatchManager::get_decompressed_sizes_async)
+  Status get_decompress_sizes_async(const void *const *d_compressed_ptrs, const size_t *d_compressed_bytes, size_t *d_uncompressed_bytes,
+                                    int *d_statuses, size_t num_chunks, hipStream_t stream = 0);
   const CompressionStats &get_stats() const;
   ZstdBatchManager &batch_manager();
 
