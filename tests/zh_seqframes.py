@@ -150,8 +150,9 @@ def rle(byte, n):
 
 
 def comp(lits, seqs, modes=("predefined",) * 3, surplus=False, zero_last=False):
-    """Compressed block.  lits: bytes (raw literals) or ("rle", byte, n).  modes (LL, OF, ML): "predefined",
-    "rle", ("fse", counts, log) or "repeat".  surplus / zero_last damage the bitstream (rejects)."""
+    """Compressed block.  lits: bytes (raw literals), ("rle", byte, n) or a Huffman description
+    (zh_hufframes.huf).  modes (LL, OF, ML): "predefined", "rle", ("fse", counts, log) or "repeat".
+    surplus / zero_last damage the bitstream (rejects)."""
     return {"type": "comp", "lits": lits, "seqs": [tuple(s) for s in seqs], "modes": tuple(modes), "surplus": surplus, "zero_last": zero_last}
 
 
@@ -165,11 +166,18 @@ def skippable(data, nibble=3):
 
 
 def _lits_len(lits):
+    if isinstance(lits, dict):
+        return len(lits["data"])
     return lits[2] if isinstance(lits, tuple) else len(lits)
 
 
 # ---- assembler --------------------------------------------------------------------------------
-def _literals_section(lits):
+def _literals_section(lits, prev=None):
+    """prev: the frame's current tables; prev[3] = the weights of its Huffman table (updated)."""
+    if isinstance(lits, dict):
+        import zh_hufframes as H
+
+        return H.literals_section(lits, prev)
     t, n = (1, lits[2]) if isinstance(lits, tuple) else (0, len(lits))
     body = bytes([lits[1]]) if t else bytes(lits)
     if n < 32:
@@ -237,7 +245,7 @@ def _block_bytes(b, last, prev):
     elif b["type"] == "rle":
         body, t, size = bytes([b["byte"]]), 1, b["n"]
     else:
-        body = _literals_section(b["lits"]) + _sequences_section(b, prev)
+        body = _literals_section(b["lits"], prev) + _sequences_section(b, prev)
         t, size = 2, len(body)
         assert size < BLOCK_MAX, "compressed block too large"
     assert size < 1 << 21
@@ -267,7 +275,7 @@ def assemble(buf, content=None):
         hdr = bytes([fhd | int(f["checksum"]) << 2 | didf]) + (b"" if f["fcs"] else bytes([(wlog - 10) << 3]))
         hdr += did.to_bytes((0, 1, 2, 4)[didf], "little") + tail
         out += MAGIC.to_bytes(4, "little") + hdr
-        prev = [None, None, None]
+        prev = [None, None, None, None]  # LL, OF, ML tables; the Huffman table's weights
         for i, b in enumerate(f["blocks"]):
             out += _block_bytes(b, i == len(f["blocks"]) - 1, prev)
         if f["checksum"]:
@@ -318,10 +326,19 @@ def _run_block(b, out, pos, hist0, rep, tags, ctx, limit=BLOCK_MAX):
     n = len(seqs)
     if b["surplus"] or b["zero_last"]:
         return None
+    if isinstance(lits, dict):  # Huffman literals: the bytes are the description's data
+        import zh_hufframes as H
+
+        if not H.model_accepts(lits, ctx):
+            return None
     if sum(s[0] for s in seqs) > nlit or nlit + sum(s[1] for s in seqs) > limit:
         return None
-    L = np.full(nlit, lits[1], np.uint8) if isinstance(lits, tuple) else np.frombuffer(lits, np.uint8)
-    tags.add("lit_rle" if isinstance(lits, tuple) else "lit_raw")
+    if isinstance(lits, dict):
+        L = np.frombuffer(lits["data"], np.uint8)
+        tags.add(f"lit_huf{lits['streams']}" if lits["tree"] else f"lit_treeless{lits['streams']}")
+    else:
+        L = np.full(nlit, lits[1], np.uint8) if isinstance(lits, tuple) else np.frombuffer(lits, np.uint8)
+        tags.add("lit_rle" if isinstance(lits, tuple) else "lit_raw")
     for t, nm in enumerate(("ll", "of", "ml")):
         m = b["modes"][t]
         tags.add(f"{nm}_{m if isinstance(m, str) else 'fse'}")
@@ -456,7 +473,7 @@ def model(buf, dictionary=b"", limit=BLOCK_MAX):
             tags.add("dict_id")
         out = np.zeros(_claimed_size(f) + 8, np.uint8)
         pos, rep = 0, [1, 4, 8]
-        ctx = {"first_seq": True, "frame": nf, "comp_blocks": 0, "between": [], "last_modes": None}
+        ctx = {"first_seq": True, "frame": nf, "comp_blocks": 0, "between": [], "last_modes": None, "huf": False}
         nf += 1
         for b in f["blocks"]:
             if b["type"] == "raw":
