@@ -147,6 +147,17 @@ struct ZhWorkspace {
 
 #define ZH_DTAB_MARGIN 256u  // tail positions a block inserts itself (>= one inserter batch)
 
+// Mixed-level batch (zh_plan.hip zh_rank_kernel): the class partition the device leaves in the
+// workspace.  Blocks are laid out sorted by parse class (ZH_LEVEL_CLASS), so class c owns block
+// slots [range[c][0], range[c][1]); a ranged matcher launch reads its end from here and takes
+// block indices from its own counter, which the rank kernel preset to the range's begin.  The deep
+// matcher runs classes ZH_CLASS_DEEP0 .. ZH_CLASS_INVALID - 1 as one range (heaviest depth first).
+struct ZhClassRanges {
+  u32 range[ZH_NCLASSES][2];  // [begin, end) in block units
+  u32 ctr[4];                 // block counters: K1 mode 2, 1, 0 (class 0, 1, 2), deep matcher
+};
+#define ZH_RANGE_CTR_DEEP 3u
+
 // Element index of step e of table t in the chain layout (see ZH_K3_SEGS); m = zh_k3_magic(L)
 // gives e / L as umulhi(e << 8, m) exactly for e < 2^14, L <= 1024
 __host__ __device__ __forceinline__ u32 zh_k3_magic(u32 L) { return ((1u << 24) + L - 1u) / L; }

@@ -984,7 +984,8 @@ __device__ __noinline__ bool dict_literals(const ZhDictEnt *dent, const u32 *his
 
 extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const ZhBlockDesc *__restrict__ blocks, ZhWorkspace ws, u32 window_log,
                                                                              u32 cfg_block_size, u64 *__restrict__ item_size,
-                                                                             u32 *__restrict__ item_status, u32 *__restrict__ blk_size) {
+                                                                             u32 *__restrict__ item_status, u32 *__restrict__ blk_size,
+                                                                             const u8 *__restrict__ blk_level) {
   extern __shared__ __attribute__((aligned(16))) u8 smem_all[];
   // Two waves per block, each with its own copy of the LDS layout: wave 0 builds the literals
   // section, wave 1 (concurrently) the sequences section's merge / repcodes / codes / FSE
@@ -1053,7 +1054,9 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
       u32 p = 0;
       o.put(p++, 0x28); o.put(p++, 0xB5); o.put(p++, 0x2F); o.put(p++, 0xFD);
       o.put(p++, (u8)((fcs_flag << 6) | (ss ? 0x20 : 0) | ((d.flags & ZH_F_CHECKSUM) ? 0x04 : 0) | didf));
-      if (!ss) o.put(p++, (u8)((window_log - 10) << 3));
+      // mixed-level batch (blk_level: one level byte per block slot): the level's own window log
+      u32 const wlog = blk_level ? (u32)ZH_LEVEL_WINDOW_LOG((u32)blk_level[b]) : window_log;
+      if (!ss) o.put(p++, (u8)((wlog - 10) << 3));
       for (u32 k = 0; k < didn; k++) o.put(p++, (u8)(did >> (8 * k)));
       u64 v = fcs_size == 2 ? content - 256 : content;
       for (u32 k = 0; k < fcs_size; k++) o.put(p++, (u8)(v >> (8 * k)));
@@ -1926,9 +1929,9 @@ hipError_t entropy_init() {
   return e;
 }
 void entropy_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
-                    u32 *d_item_status, u32 *d_blk_size, hipStream_t stream) {
+                    u32 *d_item_status, u32 *d_blk_size, const u8 *d_blk_level, hipStream_t stream) {
   hipLaunchKernelGGL(zh_entropy_kernel, dim3(nblocks), dim3(K2_THREADS), K2_LDS, stream, d_descs, ws, window_log, cfg_block_size, d_item_size,
-                     d_item_status, d_blk_size);
+                     d_item_status, d_blk_size, d_blk_level);
   // (persistent K3 / K4 waves taking blocks from a counter measured slower: entropy stage
   // 3.04 -> 3.22 ms at 16,384 blocks, 0.75 -> 0.80 ms at 2,048)
   u32 const g3 = (nblocks + K3_BPW - 1) / K3_BPW, g4 = (nblocks + K4_WAVES - 1) / K4_WAVES;

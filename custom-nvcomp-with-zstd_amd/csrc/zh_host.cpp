@@ -164,6 +164,11 @@ void apply_level_parameters(CompressionConfig &c) {
   else if (level <= 15) { c.window_log = 23; c.hash_log = level <= 14 ? 19 : 20; c.chain_log = 19; c.search_log = level <= 14 ? 256 : 512; c.target_length = 128; }
   else if (level <= 18) { c.window_log = 23; c.hash_log = 20; c.chain_log = 20; c.search_log = level <= 17 ? 512 : 999; c.target_length = 256; }
   else { c.window_log = 23; c.hash_log = 20; c.chain_log = 20; c.search_log = 999; c.target_length = 999; }
+  // the window logs above, as the table the device shares (a mixed-level batch's frame headers)
+  static_assert(ZH_LEVEL_WINDOW_LOG(1) == 18 && ZH_LEVEL_WINDOW_LOG(3) == 19 && ZH_LEVEL_WINDOW_LOG(6) == 20 && ZH_LEVEL_WINDOW_LOG(9) == 22 &&
+                    ZH_LEVEL_WINDOW_LOG(10) == 23 && ZH_LEVEL_WINDOW_LOG(22) == 23,
+                "one window log per level");
+  c.window_log = ZH_LEVEL_WINDOW_LOG(level);
 }
 CompressionConfig CompressionConfig::from_level(int level) {
   CompressionConfig c;
@@ -332,6 +337,24 @@ struct WsLayout {
 // Device blocks of a frame of n bytes (ZH_FRAME_BLOCK: 64 KiB, or 32 KiB history blocks for
 // larger frames and for dictionary frames over 32 KiB below ZH_DEEP_LEVEL: split_dict)
 inline size_t block_size_of(size_t n, bool split_dict) { return ZH_FRAME_BLOCK(n, split_dict); }
+// Workspace of a mixed-level batch (compress_batch_device_levels): the layout of a deep-level call
+// (any item may take the deep matcher) and behind it the items' ranks, one level byte per block slot
+// and the class ranges with the matchers' counters
+struct LevelsLayout {
+  WsLayout ws;
+  size_t rank, blk_level, ranges, total;
+  static LevelsLayout make(size_t nblocks, size_t nitems, bool staged) {
+    LevelsLayout L{};
+    L.ws = WsLayout::make(nblocks, nitems, staged, true);
+    size_t o = L.ws.total - 256;
+    L.rank = o; o = align256(o + nitems * 4);
+    L.blk_level = o; o = align256(o + nblocks);
+    L.ranges = o; o = align256(o + sizeof(ZhClassRanges));
+    L.total = o + 256;  // slack for base alignment
+    return L;
+  }
+};
+
 inline bool split_dict_of(bool has_dict, int level) { return has_dict && level < ZH_DEEP_LEVEL; }
 inline size_t blocks_of(size_t n, bool split_dict = false) {
   size_t const bs = block_size_of(n, split_dict);
@@ -1183,6 +1206,47 @@ Status ZstdBatchManager::compress_batch_device(const void *const *d_in_ptrs, con
                           pimpl_->config.level, stream);
   if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
   return dd ? dd->note_use(stream) : Status::SUCCESS;
+}
+
+size_t ZstdBatchManager::get_batch_device_levels_temp_size(size_t count, size_t max_chunk) {
+  size_t const bpi = std::max<size_t>(1, blocks_of(max_chunk));
+  return LevelsLayout::make(count * bpi, count, bpi > 1).total;
+}
+
+// compress_batch_device with one level per item, read on the device: the rank kernel sorts the
+// items by parse class, the plan writes the descriptors at their sorted slots, and the matchers run
+// over class ranges they read from the workspace.  The manager's level is not used.
+Status ZstdBatchManager::compress_batch_device_levels(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int *d_levels, size_t max_chunk,
+                                                      size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp,
+                                                      size_t temp_size, hipStream_t stream) {
+  std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
+  Status s = ensure_kernels();
+  if (s != Status::SUCCESS) return s;
+  if (!count) return Status::SUCCESS;
+  if (!d_in_ptrs || !d_in_sizes || !d_levels || !d_out_ptrs || !d_out_sizes || max_chunk == 0) return Status::ERROR_INVALID_PARAMETER;
+  // a dictionary frame's block split depends on its level (split_dict_of): no one bpi per batch
+  if (pimpl_->active()) return Status::ERROR_INVALID_PARAMETER;
+  size_t const bpi = blocks_of(max_chunk), nblocks = count * bpi;
+  if (count > ZH_RANK_MAX_ITEMS || nblocks > 0xFFFFFFFFull) return Status::ERROR_INVALID_PARAMETER;
+  LevelsLayout const L = LevelsLayout::make(nblocks, count, bpi > 1);
+  if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
+  u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
+  u64 const cap = estimate_compressed_size(max_chunk, pimpl_->config.level);
+  u64 *item_size = (u64 *)d_out_sizes;
+  u32 *item_status = d_statuses ? (u32 *)d_statuses : (u32 *)(base + L.ws.item_status);
+  bool const ck = pimpl_->config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY;
+  ZhClassRanges *const ranges = (ZhClassRanges *)(base + L.ranges);
+  hipError_t e = zh::launch_plan_levels(d_in_ptrs, d_in_sizes, d_levels, (u32)count, (u32)bpi, d_out_ptrs, cap, base + L.ws.staging,
+                                        (ZhBlockDesc *)(base + L.ws.descs), base + L.blk_level, (u32 *)(base + L.rank), ranges,
+                                        (ZhItemDesc *)(base + L.ws.items), item_size, item_status, ck ? ZH_F_CHECKSUM : 0u, stream);
+  if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
+  ZhWorkspace ws{base + L.ws.blocks, (u32 *)(base + L.ws.counter), nullptr, 0u};
+  ws.deep_slots = base + L.ws.deep;
+  ws.deep_nslots = (u32)L.ws.deep_slots;
+  e = zh::launch_compress_levels((const ZhBlockDesc *)(base + L.ws.descs), (u32)nblocks, ws, pimpl_->config.block_size, item_size, item_status,
+                                 (u32 *)(base + L.ws.blk_size), (const ZhItemDesc *)(base + L.ws.items), (u32)count, bpi > 1, ck, ranges,
+                                 base + L.blk_level, stream);
+  return e == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
 }
 
 size_t ZstdBatchManager::get_batch_device_decompress_temp_size(size_t count, size_t max_out) {
@@ -2631,6 +2695,16 @@ int nvcomp_zstd_batched_compress_async_v5(nvcomp_zstd_batch_manager_t *m, const 
                                           size_t n, void *const *d_out, size_t *d_out_sizes, int *d_statuses, void *t, size_t tb, hipStream_t s) {
   if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
   return c_err(m->mgr->batch_manager().compress_batch_device(d_in, d_in_sizes, max_chunk, n, d_out, d_out_sizes, d_statuses, t, tb, s));
+}
+size_t nvcomp_zstd_batched_compress_levels_get_temp_size_v5(size_t n, size_t max_chunk) {
+  return ZstdBatchManager::get_batch_device_levels_temp_size(n, max_chunk);
+}
+int nvcomp_zstd_batched_compress_levels_async_v5(nvcomp_zstd_batch_manager_t *m, const void *const *d_in, const size_t *d_in_sizes,
+                                                 const int *d_levels, size_t max_chunk, size_t n, void *const *d_out, size_t *d_out_sizes,
+                                                 int *d_statuses, void *t, size_t tb, hipStream_t s) {
+  if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
+  return c_err(
+      m->mgr->batch_manager().compress_batch_device_levels(d_in, d_in_sizes, d_levels, max_chunk, n, d_out, d_out_sizes, d_statuses, t, tb, s));
 }
 size_t nvcomp_zstd_batch_get_decompress_temp_size_v5(nvcomp_zstd_batch_manager_t *m, const size_t *sizes, size_t n) {
   return (m && m->mgr) ? m->mgr->get_decompress_temp_size(sizes, n) : 0;

@@ -62,6 +62,18 @@ int profile_collect(double *totals);
 hipError_t launch_plan(const void *const *d_in_ptrs, const size_t *d_in_sizes, u32 nitems, u32 bpi, void *const *d_out_ptrs, u64 out_cap,
                        u8 *staging, ZhBlockDesc *d_descs, ZhItemDesc *d_items, u64 *d_item_size, u32 *d_item_status, u32 extra_flags,
                        const u8 *dict, u32 dict_n, u32 dict_id, u32 hist, hipStream_t stream);
+// Mixed-level batch (zh_plan.hip): d_levels[i] = item i's level, a device array.  launch_plan_levels
+// ranks the items by parse class (one workgroup, up to ZH_RANK_MAX_ITEMS items) and writes the
+// descriptors at their sorted slots with one level byte per slot; launch_compress_levels runs the
+// matchers over the class ranges left in *d_ranges, then the same entropy / gather / checksum stages.
+#define ZH_RANK_MAX_ITEMS (1u << 20)
+hipError_t launch_plan_levels(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int *d_levels, u32 nitems, u32 bpi,
+                              void *const *d_out_ptrs, u64 out_cap, u8 *staging, ZhBlockDesc *d_descs, u8 *d_blk_level, u32 *d_rank,
+                              ZhClassRanges *d_ranges, ZhItemDesc *d_items, u64 *d_item_size, u32 *d_item_status, u32 extra_flags,
+                              hipStream_t stream);
+hipError_t launch_compress_levels(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 cfg_block_size, u64 *d_item_size,
+                                  u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum,
+                                  ZhClassRanges *d_ranges, const u8 *d_blk_level, hipStream_t stream);
 // Long-distance matching (zh_ldm.hip): index + per-cell split of one frame, three descriptor slots per cell
 hipError_t ldm_launch(const u8 *src, u64 size, u32 ncells, u32 table_log, u32 max_dist, u32 flags, u64 *table, u64 *skey, u32 *sslot,
                       u32 *scount, ZhBlockDesc *descs, u8 *staging, u32 *blk_size, ZhLdmRecord *rec, hipStream_t stream);

@@ -1905,6 +1905,27 @@ extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_short_kernel(cons
 extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_greedy_kernel(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws) {
   lz_blocks<2>(blocks, nblocks, ws);
 }
+// Ranged launches of a mixed-level batch: the parse's blocks are class `cls`'s slots
+// [begin, end) of the sorted layout, known only on the device (ZhClassRanges).  The block loop is
+// lz_blocks' own: its bound is the class's end and its counter the class's, preset to begin, so
+// the first index a workgroup takes is already inside the range; an empty class returns at once.
+template <u32 MODE>
+__device__ __forceinline__ void lz_blocks_ranged(const ZhBlockDesc *__restrict__ blocks, ZhClassRanges *cr, ZhWorkspace ws) {
+  constexpr u32 cls = 2u - MODE;
+  u32 const begin = cr->range[cls][0], end = cr->range[cls][1];
+  if (begin >= end) return;
+  ws.ctr = &cr->ctr[cls];
+  lz_blocks<MODE>(blocks, end, ws);
+}
+extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_ranged_kernel(const ZhBlockDesc *__restrict__ blocks, ZhClassRanges *cr, ZhWorkspace ws) {
+  lz_blocks_ranged<0>(blocks, cr, ws);
+}
+extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_short_ranged_kernel(const ZhBlockDesc *__restrict__ blocks, ZhClassRanges *cr, ZhWorkspace ws) {
+  lz_blocks_ranged<1>(blocks, cr, ws);
+}
+extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_greedy_ranged_kernel(const ZhBlockDesc *__restrict__ blocks, ZhClassRanges *cr, ZhWorkspace ws) {
+  lz_blocks_ranged<2>(blocks, cr, ws);
+}
 
 extern "C" u32 zh_lz_lds_bytes() { return K1_LDS; }
 
@@ -1926,7 +1947,8 @@ extern "C" __global__ void zh_dict_pack_kernel(const u32 *__restrict__ t32, u16 
 
 namespace zh {
 hipError_t lz_init() {
-  for (const void *f : {(const void *)zh_lz_kernel, (const void *)zh_lz_short_kernel, (const void *)zh_lz_greedy_kernel}) {
+  for (const void *f : {(const void *)zh_lz_kernel, (const void *)zh_lz_short_kernel, (const void *)zh_lz_greedy_kernel,
+                        (const void *)zh_lz_ranged_kernel, (const void *)zh_lz_short_ranged_kernel, (const void *)zh_lz_greedy_ranged_kernel}) {
     hipError_t const e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_LDS);
     if (e != hipSuccess) return e;
   }
@@ -1954,6 +1976,17 @@ void lz_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 mode
   u32 const grid = std::min(nblocks, (u32)cus);
   auto *const k = mode == 2 ? zh_lz_greedy_kernel : mode == 1 ? zh_lz_short_kernel : zh_lz_kernel;
   hipLaunchKernelGGL(k, dim3(grid), dim3(K1_THREADS), K1_LDS, stream, d_descs, nblocks, ws);
+}
+// The three parses of a mixed-level batch over their class ranges (ZhClassRanges, device only):
+// the host knows no more than nblocks, so each launch is sized as if the class held every block.
+void lz_launch_ranged(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, ZhClassRanges *d_ranges, hipStream_t stream) {
+  int dev = 0, cus = 0;
+  if (stream) (void)hipStreamGetDevice(stream, &dev);
+  else (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  u32 const grid = std::min(nblocks, (u32)cus);
+  for (auto *const k : {zh_lz_greedy_ranged_kernel, zh_lz_short_ranged_kernel, zh_lz_ranged_kernel})
+    hipLaunchKernelGGL(k, dim3(grid), dim3(K1_THREADS), K1_LDS, stream, d_descs, d_ranges, ws);
 }
 }  // namespace zh
 

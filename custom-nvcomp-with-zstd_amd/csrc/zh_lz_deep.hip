@@ -821,6 +821,33 @@ extern "C" __global__ __launch_bounds__(DT) void zh_lz_deep_kernel(const ZhBlock
   }
 }
 
+// The deep classes of a mixed-level batch (zh_plan.hip zh_rank_kernel): block slots [begin of class
+// ZH_CLASS_DEEP0, end of the last deep class) of the sorted layout, the deepest search first, taken
+// from the deep counter the rank kernel preset to that begin; each block's depth comes from its
+// level byte.  An empty range returns at once.
+extern "C" __global__ __launch_bounds__(DT) void zh_lz_deep_ranged_kernel(const ZhBlockDesc *__restrict__ blocks, ZhClassRanges *cr, ZhWorkspace ws,
+                                                                         u8 *scratch, const u8 *__restrict__ blk_level) {
+  extern __shared__ __attribute__((aligned(16))) u8 smem[];
+  u32 *misc = (u32 *)(smem + L_MISC);
+  u32 const tid = threadIdx.x;
+  u32 const begin = cr->range[ZH_CLASS_DEEP0][0], end = cr->range[ZH_CLASS_INVALID - 1][1];
+  if (begin >= end) return;
+  u8 *const slot = scratch + (size_t)blockIdx.x * SLOT_BYTES;
+  if (tid == 0) misc[0] = 0;
+  for (;;) {
+    if (tid == 0) misc[1] = atomicAdd(&cr->ctr[ZH_RANGE_CTR_DEEP], 1u);
+    __syncthreads();
+    u32 const b = misc[1];
+    __syncthreads();
+    if (b >= end) break;
+    ZhBlockDesc const d = blocks[b];
+    // (the depth is the same in every lane: kept in an SGPR, like the single-level kernel's argument)
+    u32 const depth = (u32)__builtin_amdgcn_readfirstlane((int)ZH_DEEP_DEPTH((u32)blk_level[b]));
+    if (d.n) deep_block(d, ws, b, slot, depth, tid);
+    __syncthreads();  // the slot and LDS are free for the next block
+  }
+}
+
 #ifdef ZH_STAMPS
 extern "C" __global__ void zh_read_deep_fix(u32 *out) { *out = g_deep_fix; g_deep_fix = 0; }
 extern "C" u32 zh_deep_fix_host() {
@@ -866,7 +893,21 @@ hipError_t lz_deep_dict_tables(const u8 *content, size_t cn, u8 *stg, u32 *dprev
 hipError_t lz_deep_init() {
   hipError_t e = hipFuncSetAttribute((const void *)zh_lz_deep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_deep_dict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_lz_deep_ranged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   return e;
+}
+
+// the deep classes of a mixed-level batch (d_blk_level: one level byte per block slot)
+hipError_t lz_deep_launch_ranged(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, ZhClassRanges *d_ranges, const u8 *d_blk_level,
+                                 hipStream_t stream) {
+  int dev = 0, cus = 0;
+  if (stream) (void)hipStreamGetDevice(stream, &dev);
+  else (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  if (!ws.deep_slots || !ws.deep_nslots) return hipErrorInvalidValue;
+  u32 const grid = std::min(std::min(nblocks, (u32)cus), ws.deep_nslots);
+  hipLaunchKernelGGL(zh_lz_deep_ranged_kernel, dim3(grid), dim3(DT), DEEP_LDS, stream, d_descs, d_ranges, ws, ws.deep_slots, d_blk_level);
+  return hipGetLastError();
 }
 
 static hipError_t deep_launch_depth(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 depth, hipStream_t stream) {

@@ -9,6 +9,7 @@
 //                  src/cuda_zstd_manager.cu:2765-3027).
 #include "zh_common.h"
 #include "zh_launch.h"
+#include "zh_scan.h"
 #include "zh_xxh64.h"
 
 #include <mutex>
@@ -19,11 +20,14 @@ extern "C" u32 zh_entropy_lds_bytes();
 namespace zh {
 hipError_t lz_init();
 void lz_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 mode, hipStream_t stream);
+void lz_launch_ranged(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, ZhClassRanges *d_ranges, hipStream_t stream);
 hipError_t lz_deep_init();
 hipError_t lz_deep_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, int level, hipStream_t stream);
+hipError_t lz_deep_launch_ranged(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, ZhClassRanges *d_ranges, const u8 *d_blk_level,
+                                 hipStream_t stream);
 hipError_t entropy_init();
 void entropy_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
-                    u32 *d_item_status, u32 *d_blk_size, hipStream_t stream);
+                    u32 *d_item_status, u32 *d_blk_size, const u8 *d_blk_level, hipStream_t stream);
 }  // namespace zh
 
 extern "C" __global__ void zh_plan_kernel(const void *const *__restrict__ in_ptrs, const size_t *__restrict__ in_sizes, u32 nitems,
@@ -75,6 +79,114 @@ extern "C" __global__ void zh_plan_kernel(const void *const *__restrict__ in_ptr
     if (size == 0) { item_size[it] = 0; item_status[it] = ZH_ST_INVALID; }
   }
 }
+
+// ---- mixed-level batch: one level per item, on the device ----------------------
+// zh_rank_kernel: a stable counting sort of the items by parse class (ZH_LEVEL_CLASS), one
+// workgroup.  Thread t owns the contiguous items [t * per, (t + 1) * per), so thread order is item
+// order; it counts its items per class, the counts are scanned across the workgroup (three classes
+// packed into one u64 of ZH_RANK_FIELD-bit fields, block_scan_excl64), and a second pass over the
+// same items hands out the ranks.  rank[i] = item i's place in the sorted order; cr = every class's
+// block range and the matchers' counters preset to their ranges' begins.
+#define ZH_RANK_FIELD 21u
+#define ZH_RANK_MASK ((1u << ZH_RANK_FIELD) - 1u)
+static_assert(ZH_RANK_MAX_ITEMS <= ZH_RANK_MASK, "a class count fits its field");
+static_assert(ZH_NCLASSES <= 12, "four packed words of three classes");
+extern "C" __global__ __launch_bounds__(ZH_SCAN_THREADS) void zh_rank_kernel(const int *__restrict__ levels, u32 nitems, u32 bpi,
+                                                                             u32 *__restrict__ rank, ZhClassRanges *__restrict__ cr) {
+  __shared__ u64 lds[4];
+  u32 const tid = threadIdx.x;
+  u32 const per = (nitems + ZH_SCAN_THREADS - 1) / ZH_SCAN_THREADS;
+  u32 const i0 = min(tid * per, nitems), i1 = min(i0 + per, nitems);
+  u64 cnt[4] = {0, 0, 0, 0};
+  for (u32 i = i0; i < i1; i++) {
+    int const lv = levels[i];
+    u32 const c = (u32)ZH_LEVEL_CLASS(lv);
+    u64 const one = 1ull << (ZH_RANK_FIELD * (c % 3u));
+#pragma unroll
+    for (u32 w = 0; w < 4; w++) cnt[w] += c / 3u == w ? one : 0ull;
+  }
+  u64 run[4], tot[4];
+#pragma unroll
+  for (u32 w = 0; w < 4; w++) run[w] = block_scan_excl64(cnt[w], lds, tot[w]);
+  // class begins (in items): every thread derives them from the totals
+  u32 begin[ZH_NCLASSES + 1];
+  begin[0] = 0;
+#pragma unroll
+  for (u32 c = 0; c < ZH_NCLASSES; c++) begin[c + 1] = begin[c] + ((u32)(tot[c / 3u] >> (ZH_RANK_FIELD * (c % 3u))) & ZH_RANK_MASK);
+#pragma unroll
+  for (u32 c = 0; c < ZH_NCLASSES; c++) run[c / 3u] += (u64)begin[c] << (ZH_RANK_FIELD * (c % 3u));  // begin + earlier threads' < nitems
+  for (u32 i = i0; i < i1; i++) {
+    int const lv = levels[i];
+    u32 const c = (u32)ZH_LEVEL_CLASS(lv), sh = ZH_RANK_FIELD * (c % 3u);
+    u64 r = 0;
+#pragma unroll
+    for (u32 w = 0; w < 4; w++) {
+      r = c / 3u == w ? run[w] : r;
+      run[w] += c / 3u == w ? 1ull << sh : 0ull;
+    }
+    rank[i] = (u32)(r >> sh) & ZH_RANK_MASK;
+  }
+  if (tid < ZH_NCLASSES) {
+    u32 b0 = 0, b1 = 0;
+#pragma unroll
+    for (u32 c = 0; c < ZH_NCLASSES; c++) { b0 = tid == c ? begin[c] : b0; b1 = tid == c ? begin[c + 1] : b1; }
+    cr->range[tid][0] = b0 * bpi;
+    cr->range[tid][1] = b1 * bpi;
+    if (tid <= ZH_CLASS_DEEP0) cr->ctr[tid] = b0 * bpi;  // K1 mode 2, 1, 0; the deep range starts at its first class
+  }
+}
+
+// zh_plan_kernel's sibling for a mixed-level batch: item i's bpi descriptors go to block slots
+// rank[i] * bpi .. (sorted by parse class), d.item stays i -- everything downstream of K1 indexes by
+// block and writes results by d.item, so outputs land in input order -- and the item's level is
+// stored per block slot.  A level outside 1..22: size 0, status invalid, inactive slots.  No dictionary.
+extern "C" __global__ void zh_plan_levels_kernel(const void *const *__restrict__ in_ptrs, const size_t *__restrict__ in_sizes,
+                                                 const int *__restrict__ levels, const u32 *__restrict__ rank, u32 nitems, u32 bpi,
+                                                 void *const *__restrict__ out_ptrs, u64 out_cap, u8 *staging, ZhBlockDesc *descs, u8 *blk_level,
+                                                 ZhItemDesc *items, u64 *item_size, u32 *item_status, u32 extra_flags) {
+  u32 const t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nitems * bpi) return;
+  u32 const it = t / bpi, k = t % bpi;
+  u32 const b = rank[it] * bpi + k;
+  int const level = levels[it];
+  bool const valid = ZH_LEVEL_VALID(level);
+  u64 const size = in_sizes[it];
+  u64 const bs = ZH_FRAME_BLOCK(size, false);
+  u64 const nb = (size + bs - 1) / bs;
+  ZhBlockDesc d;
+  d.src = (const u8 *)in_ptrs[it] + (u64)k * bs;
+  d.frame_size = size;
+  d.item = it;
+  d.n = (valid && k < nb) ? (u32)min(bs, size - (u64)k * bs) : 0u;
+  d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) | extra_flags |
+            (level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u);
+  d.pre = nullptr;
+  d.pre_n = 0;
+  d.dict_id = 0;
+  if (k > 0) {  // history frame: the previous 32 KiB block is staged in front (every level's window reaches it)
+    d.pre = d.src - ZH_HIST_BLOCK;
+    d.pre_n = ZH_HIST_BLOCK;
+  }
+  if (nb == 1) {
+    d.dst = (u8 *)out_ptrs[it];
+    d.dst_cap = (u32)min(out_cap, (u64)0xFFFFFFFFu);
+  } else {
+    d.dst = staging + (size_t)b * ZH_STAGE_SLOT;
+    d.dst_cap = ZH_STAGE_SLOT;
+  }
+  descs[b] = d;
+  blk_level[b] = valid ? (u8)level : (u8)0;
+  if (k == 0) {
+    ZhItemDesc id;
+    id.dst = (u8 *)out_ptrs[it];
+    id.cap = out_cap;
+    id.first_block = b;
+    id.nblocks = (u32)nb;
+    items[it] = id;
+    if (size == 0 || !valid) { item_size[it] = 0; item_status[it] = ZH_ST_INVALID; }
+  }
+}
+static_assert(ZH_LEVEL_WINDOW_LOG(1) >= ZH_HIST_WINDOW_LOG, "every level's frames may reach the previous block");
 
 // One workgroup per block: a block of a multi-block frame sums the staged sizes of its
 // frame's blocks (its output offset and the frame's total), the frame's first block sets the
@@ -201,9 +313,12 @@ int profile_collect(double *totals) {
   return n;
 }
 
-hipError_t launch_compress(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
-                           u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum, int level,
-                           hipStream_t stream) {
+// The stages of one batch.  d_ranges null: every block at `level` (launch_compress); else a
+// mixed-level batch (launch_compress_levels): the matchers run over the class ranges the rank kernel
+// left in *d_ranges, counters included, and d_blk_level holds every block slot's level.
+static hipError_t compress_stages(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
+                                  u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum,
+                                  int level, ZhClassRanges *d_ranges, const u8 *d_blk_level, hipStream_t stream) {
   if (nblocks == 0) return hipSuccess;
   std::vector<hipEvent_t> ev;
   {
@@ -211,16 +326,23 @@ hipError_t launch_compress(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace 
     if (prof().on) for (int k = 0; k < 4; k++) ev.push_back(prof_event());
   }
   if (!ev.empty()) (void)hipEventRecord(ev[0], stream);
-  (void)hipMemsetAsync(ws.ctr, 0, 4, stream);  // K1's block counter
-  // levels >= ZH_DEEP_LEVEL: the deep chain matcher; below: K1's dual-hash parse
-  if (level >= ZH_DEEP_LEVEL) {
+  if (d_ranges) {
+    // four launches whatever the mix (the host cannot see which classes are empty): the three K1
+    // parses, then the deep matcher over all its depths
+    lz_launch_ranged(d_descs, nblocks, ws, d_ranges, stream);
+    hipError_t const e = lz_deep_launch_ranged(d_descs, nblocks, ws, d_ranges, d_blk_level, stream);
+    if (e != hipSuccess) return e;
+  } else if (level >= ZH_DEEP_LEVEL) {
+    // levels >= ZH_DEEP_LEVEL: the deep chain matcher; below: K1's dual-hash parse
+    (void)hipMemsetAsync(ws.ctr, 0, 4, stream);  // the matcher's block counter
     hipError_t const e = lz_deep_launch(d_descs, nblocks, ws, level, stream);
     if (e != hipSuccess) return e;
   } else {
+    (void)hipMemsetAsync(ws.ctr, 0, 4, stream);  // K1's block counter
     lz_launch(d_descs, nblocks, ws, (u32)ZH_K1_MODE(level), stream);
   }
   if (!ev.empty()) (void)hipEventRecord(ev[1], stream);
-  entropy_launch(d_descs, nblocks, ws, window_log, cfg_block_size, d_item_size, d_item_status, d_blk_size, stream);
+  entropy_launch(d_descs, nblocks, ws, window_log, cfg_block_size, d_item_size, d_item_status, d_blk_size, d_blk_level, stream);
   if (!ev.empty()) (void)hipEventRecord(ev[2], stream);
   if (gather && nitems) hipLaunchKernelGGL(zh_gather_kernel, dim3(nblocks), dim3(256), 0, stream, d_items, d_descs, d_blk_size, d_item_size, d_item_status);
   if (checksum && nitems) hipLaunchKernelGGL(zh_checksum_kernel, dim3(nitems), dim3(64), 0, stream, d_items, d_descs, d_item_size, d_item_status);
@@ -229,6 +351,33 @@ hipError_t launch_compress(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace 
     std::lock_guard<std::mutex> g(prof().mu);
     prof().pending.push_back(ev);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_compress(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
+                           u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum, int level,
+                           hipStream_t stream) {
+  return compress_stages(d_descs, nblocks, ws, window_log, cfg_block_size, d_item_size, d_item_status, d_blk_size, d_items, nitems, gather,
+                         checksum, level, nullptr, nullptr, stream);
+}
+
+hipError_t launch_compress_levels(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 cfg_block_size, u64 *d_item_size,
+                                  u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum,
+                                  ZhClassRanges *d_ranges, const u8 *d_blk_level, hipStream_t stream) {
+  return compress_stages(d_descs, nblocks, ws, 0, cfg_block_size, d_item_size, d_item_status, d_blk_size, d_items, nitems, gather, checksum, 0,
+                         d_ranges, d_blk_level, stream);
+}
+
+hipError_t launch_plan_levels(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int *d_levels, u32 nitems, u32 bpi,
+                              void *const *d_out_ptrs, u64 out_cap, u8 *staging, ZhBlockDesc *d_descs, u8 *d_blk_level, u32 *d_rank,
+                              ZhClassRanges *d_ranges, ZhItemDesc *d_items, u64 *d_item_size, u32 *d_item_status, u32 extra_flags,
+                              hipStream_t stream) {
+  u32 const total = nitems * bpi;
+  if (!total) return hipSuccess;
+  if (nitems > ZH_RANK_MAX_ITEMS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(zh_rank_kernel, dim3(1), dim3(ZH_SCAN_THREADS), 0, stream, d_levels, nitems, bpi, d_rank, d_ranges);
+  hipLaunchKernelGGL(zh_plan_levels_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, d_in_ptrs, d_in_sizes, d_levels, d_rank, nitems, bpi,
+                     d_out_ptrs, out_cap, staging, d_descs, d_blk_level, d_items, d_item_size, d_item_status, extra_flags);
   return hipGetLastError();
 }
 

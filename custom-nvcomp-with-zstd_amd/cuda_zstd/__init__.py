@@ -85,6 +85,8 @@ def lib() -> ctypes.CDLL:
             "nvcomp_zstd_batch_get_batched_temp_size_v5": (sz, [vp, sz, sz]),
             "nvcomp_zstd_batch_set_dictionary_v5": (i, [vp, vp]),
             "nvcomp_zstd_batched_compress_async_v5": (i, [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
+            "nvcomp_zstd_batched_compress_levels_get_temp_size_v5": (sz, [sz, sz]),
+            "nvcomp_zstd_batched_compress_levels_async_v5": (i, [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
             "cuda_zstd_get_batch_decompress_workspace_size": (sz, [vp, psz, sz]),
             "cuda_zstd_decompress_batch": (i, [vp, pvp, psz, sz, pvp, psz, pi, vp, sz, vp]),
             "nvcomp_zstd_batch_get_decompress_temp_size_v5": (sz, [vp, psz, sz]),
@@ -657,6 +659,24 @@ class BatchedCompressor:
             raise ZstdError(rc, "nvcomp_zstd_batched_compress_async_v5")
 
     @staticmethod
+    def temp_size_levels(num_chunks: int, max_chunk: int) -> int:
+        """Workspace of compress_levels_async (nvcomp_zstd_batched_compress_levels_get_temp_size_v5)."""
+        return lib().nvcomp_zstd_batched_compress_levels_get_temp_size_v5(num_chunks, max_chunk)
+
+    def compress_levels_async(self, d_in_ptrs, d_in_sizes, d_levels, max_chunk, d_out_ptrs, d_out_sizes, d_status, temp, stream=None):
+        """compress_async at one level per chunk: d_levels is a device int32 tensor (such as
+        analyze_batch_device's), read on the device in stream order; the handle's level is not
+        used, its checksum setting is (nvcomp_zstd_batched_compress_levels_async_v5).  No
+        dictionary."""
+        n = d_in_ptrs.numel()
+        rc = lib().nvcomp_zstd_batched_compress_levels_async_v5(
+            self._h, d_in_ptrs.data_ptr(), d_in_sizes.data_ptr(), d_levels.data_ptr() if d_levels is not None else None, max_chunk, n,
+            d_out_ptrs.data_ptr(), d_out_sizes.data_ptr(), d_status.data_ptr() if d_status is not None else None, temp.data_ptr(),
+            temp.numel(), _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batched_compress_levels_async_v5")
+
+    @staticmethod
     def seekable_max_size(num_frames: int, max_compressed_chunk: int, checksums: bool = False) -> int:
         return lib().cuda_zstd_seekable_max_size(num_frames, max_compressed_chunk, 1 if checksums else 0)
 
@@ -1051,17 +1071,57 @@ def adaptive_finalize_host(hist, repeated_pairs: int, max_run_length: int, patte
     return _stats_dict(out)
 
 
+def compress_batch_levels(chunks: Sequence, levels, checksum: bool = False, stream=None) -> List:
+    """Compress chunk i (uint8 device tensors) at levels[i] in one stream-ordered call
+    (nvcomp_zstd_batched_compress_levels_async_v5) -> the frames in input order, each the bytes
+    Manager(levels[i]) writes for it.  levels: a device int32 tensor, read on the device in stream
+    order and never copied to the host, or a sequence of ints.  Waits once, for the frames' sizes;
+    a chunk whose level is outside 1..22 raises ZstdError."""
+    torch = _torch()
+    n = len(chunks)
+    if n == 0:
+        return []
+    s = stream if stream is not None else torch.cuda.current_stream()
+    ins = [c.contiguous().view(torch.uint8) for c in chunks]
+    sizes = [t.numel() for t in ins]
+    max_chunk = max(max(sizes), 1)
+    slot = ((max_compressed_size(max_chunk) + 255) // 256) * 256
+    bc = BatchedCompressor(3, checksum=checksum)  # (the level of the handle is not used)
+    with torch.cuda.stream(s):
+        if _is_cuda_tensor(levels):
+            d_levels = levels.to(torch.int32).contiguous()
+        else:
+            d_levels = torch.tensor([int(v) for v in levels], dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
+        if d_levels.numel() != n:
+            raise ZstdError(INVALID, "compress_batch_levels: one level per chunk")
+        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
+        table = torch.tensor([[t.data_ptr() for t in ins], sizes, [out.data_ptr() + k * slot for k in range(n)]], dtype=torch.int64)
+        d_table = table.pin_memory().to("cuda", non_blocking=True)
+        if s != torch.cuda.current_stream():  # (the inputs' allocator stream is the current one)
+            for t in ins:
+                t.record_stream(s)
+        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
+        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
+        temp = torch.empty(bc.temp_size_levels(n, max_chunk), dtype=torch.uint8, device="cuda")
+        bc.compress_levels_async(d_table[0], d_table[1], d_levels, max_chunk, d_table[2], d_sizes, d_status, temp, s)
+        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()  # the one wait (stream-ordered copy)
+    bc.close()
+    res = []
+    for k in range(n):
+        if got_status[k] != OK:
+            raise ZstdError(got_status[k], f"compress_batch_levels item {k}")
+        res.append(out[k * slot : k * slot + got_sizes[k]])
+    return res
+
+
 def compress_batch_adaptive(chunks: Sequence, preference: int = BALANCED, stream=None):
     """Compress every chunk (uint8 device tensors) at the level the selector gives it ->
-    (frames, levels): one analysis of the batch, one copy of the levels to the host, then one
-    Manager(level).compress_batch per distinct level; frames in input order."""
-    levels = [int(v) for v in analyze_batch(chunks, preference, stream=stream)[0].cpu()]
-    frames = [None] * len(chunks)
-    for level in sorted(set(levels)):
-        idx = [k for k, v in enumerate(levels) if v == level]
-        for k, f in zip(idx, Manager(level).compress_batch([chunks[k] for k in idx], stream)):
-            frames[k] = f
-    return frames, levels
+    (frames, levels): one analysis of the batch, then one compress_batch_levels call fed the
+    analysis' device tensor on the same stream; the levels are copied to the host only for the
+    return value.  Frames in input order."""
+    d_levels = analyze_batch(chunks, preference, stream=stream)[0]
+    frames = compress_batch_levels(chunks, d_levels, stream=stream)
+    return frames, [int(v) for v in d_levels.cpu()]
 
 
 def hybrid_compress(data, level: int = 3) -> bytes:

@@ -142,6 +142,29 @@ int nvcomp_zstd_batched_compress_async_v5(nvcomp_zstd_batch_manager_t *mgr, cons
                                           int *d_statuses, void *d_temp_storage, size_t temp_storage_bytes,
                                           hipStream_t stream);
 
+/* The same call at one level per chunk: d_levels[i] is chunk i's level, a DEVICE int array such as
+ * the one cuda_zstd_adaptive_analyze_batch_async leaves behind, read on the device.  Stream-ordered
+ * like the call above: every array is a device array, nothing is allocated, synchronised or copied
+ * to the host.  Frame i is byte-identical to what a handle at level d_levels[i] writes for chunk i
+ * through nvcomp_zstd_batched_compress_async_v5 with the same max_uncompressed_chunk_bytes.  The
+ * handle's level is ignored; its checksum setting applies.  A level outside 1..22 gives that chunk
+ * size 0 and status 2 and leaves its output buffer untouched; its neighbours are unaffected.
+ * Returns 2 for a null array, max_uncompressed_chunk_bytes == 0, a handle with a dictionary set or
+ * more than 1,048,576 chunks (the one workgroup that ranks the chunks by level is kept to that),
+ * 7 for a workspace below nvcomp_zstd_batched_compress_levels_get_temp_size_v5 (nothing is
+ * launched); num_chunks == 0 succeeds and launches nothing.
+ * Out of scope: dictionaries (a dictionary frame's block split depends on its level, so one block
+ * count per chunk does not hold for the batch), dict_entropy, long-distance matching and the
+ * streaming manager.
+ * The workspace is that of a handle at a level >= 5 plus the chunks' ranks, one level byte per block
+ * and the class ranges: at least what any dictionary-less handle needs for the call above. */
+size_t nvcomp_zstd_batched_compress_levels_get_temp_size_v5(size_t num_chunks, size_t max_uncompressed_chunk_bytes);
+int nvcomp_zstd_batched_compress_levels_async_v5(nvcomp_zstd_batch_manager_t *mgr, const void *const *d_uncompressed_ptrs,
+                                                 const size_t *d_uncompressed_sizes, const int *d_levels,
+                                                 size_t max_uncompressed_chunk_bytes, size_t num_chunks, void *const *d_compressed_ptrs,
+                                                 size_t *d_compressed_sizes, int *d_statuses, void *d_temp_storage,
+                                                 size_t temp_storage_bytes, hipStream_t stream);
+
 /* NvcompV5BatchManager::decompress_async as a C handle call (reference include/cuda_zstd_nvcomp.h:97-99,
  * 119-125): host or device arrays, uncompressed_sizes[i] capacity in, bytes out; blocking on return. */
 size_t nvcomp_zstd_batch_get_decompress_temp_size_v5(nvcomp_zstd_batch_manager_t *mgr, const size_t *compressed_sizes, size_t num_chunks);

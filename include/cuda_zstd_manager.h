@@ -98,6 +98,24 @@ class ZstdBatchManager : public ZstdManager {
   // the same for this manager's level and dictionary (levels >= 5 add the deep matcher's scratch
   // slots, ~1.2 MB per persistent workgroup; a dictionary over 32 KiB chunks adds history blocks)
   size_t get_batch_device_temp_size_for(size_t count, size_t max_chunk_bytes) const;
+  // The same call with one level per chunk, read on the device: d_levels[i] (a device int array,
+  // such as the one cuda_zstd_adaptive_analyze_batch_async leaves behind) is chunk i's level, and
+  // frame i is byte-identical to what a manager at that level writes for chunk i through
+  // compress_batch_device with the same max_chunk_bytes.  Stream-ordered like it: no allocation, no
+  // synchronisation, no copy to the host.  The manager's level is not used; its checksum setting
+  // applies.  A level outside 1..22 gives that chunk size 0 and status ERROR_INVALID_PARAMETER and
+  // leaves its output untouched; the other chunks are unaffected.  ERROR_INVALID_PARAMETER for a null
+  // array, max_chunk_bytes == 0, a manager with a dictionary set or count > 1,048,576;
+  // ERROR_BUFFER_TOO_SMALL for a
+  // workspace below get_batch_device_levels_temp_size (nothing is launched); count == 0 succeeds.
+  // Not covered: dictionaries (a dictionary frame's block split depends on its level), dict_entropy,
+  // long-distance matching, the streaming manager.
+  Status compress_batch_device_levels(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int *d_levels, size_t max_chunk_bytes,
+                                      size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp_workspace,
+                                      size_t temp_size, hipStream_t stream);
+  // its workspace: get_batch_device_temp_size_for of a level >= 5 plus the items' ranks, one level
+  // byte per block and the class ranges; at least what any dictionary-less manager's call needs
+  static size_t get_batch_device_levels_temp_size(size_t count, size_t max_chunk_bytes);
 
   // Stream-ordered batched decompression over device arrays (no host sync; GPU decoder,
   // any RFC 8878 frames); used by nvcomp_zstd_batched_decompress_async_v5.

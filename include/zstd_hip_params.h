@@ -97,6 +97,22 @@
 #define ZH_DEEP_PRE 65536
 #define ZH_DEEP_MAXOFF 65535       /* links stored as u16 distances (zh_lz_deep.hip) are exact */
 #define ZH_DEEP_DEPTH(level) ((level) <= 5 ? 4 : (level) == 6 ? 8 : (level) == 7 ? 16 : (level) <= 9 ? 32 : (level) == 10 ? 64 : 128)
+/* Window log a level's frames declare (the reference's level table, src/cuda_zstd_types.cpp:147-210):
+ * the one table behind apply_level_parameters (host) and the entropy kernel's per-block window
+ * descriptor of a mixed-level batch. */
+#define ZH_LEVEL_WINDOW_LOG(level) ((level) <= 1 ? 18 : (level) <= 3 ? 19 : (level) <= 6 ? 20 : (level) <= 9 ? 22 : 23)
+/* Parse classes of a mixed-level batch (zh_rank_kernel), in the order their blocks are laid out:
+ * K1 mode 2, 1, 0, then the deep matcher by descending search depth (128, 64, 32, 16, 8, 4); items
+ * with a level outside 1..22 come last (ZH_CLASS_INVALID) and are never compressed. */
+#define ZH_CLASS_DEEP0 3
+#define ZH_CLASS_INVALID 9
+#define ZH_NCLASSES 10
+#define ZH_LEVEL_VALID(level) ((level) >= 1 && (level) <= 22)
+#define ZH_LEVEL_CLASS(level)                                                                          \
+  (!ZH_LEVEL_VALID(level) ? ZH_CLASS_INVALID                                                           \
+   : (level) < ZH_DEEP_LEVEL ? 2 - ZH_K1_MODE(level)                                                   \
+   : ZH_DEEP_DEPTH(level) == 128 ? 3 : ZH_DEEP_DEPTH(level) == 64 ? 4 : ZH_DEEP_DEPTH(level) == 32 ? 5 \
+   : ZH_DEEP_DEPTH(level) == 16 ? 6 : ZH_DEEP_DEPTH(level) == 8 ? 7 : 8)
 #define ZH_COMPRESS_LITERALS_SIZE_MIN 63
 #define ZH_LONGNBSEQ 0x7F00
 #define ZH_MAGIC 0xFD2FB528u
