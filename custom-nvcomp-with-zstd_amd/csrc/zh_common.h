@@ -4,44 +4,11 @@
 #include <stdint.h>
 #include "zstd_hip_params.h"
 #include "zh_dict_ent.h"
+#include "zh_block_plan.h"  // ZhBlockDesc, ZhItemDesc, ZH_F_*, ZH_ST_*, u8 .. u64
 
-typedef uint8_t u8;
-typedef uint16_t u16;
-typedef uint32_t u32;
-typedef uint64_t u64;
 typedef int16_t s16;
 typedef int32_t s32;
 
-// One device block (<= ZH_BLOCK_MAX input bytes) = one K1 workgroup = one K2 wave.
-struct ZhBlockDesc {
-  const u8 *src;     // first input byte of this block
-  u8 *dst;           // where this block's output goes (item output if DIRECT, else staging slot)
-  u64 frame_size;    // content size of the frame this block belongs to
-  u32 n;             // input bytes (0 = inactive slot)
-  u32 item;          // batch item index
-  u32 dst_cap;       // bytes available at dst
-  u32 flags;         // ZH_F_* below
-  const u8 *pre;     // ZH_F_DICT first block: dictionary content tail staged before the block
-  u32 pre_n;         // its length (pre_n + n <= ZH_BLOCK_MAX; ZH_F_DEEP: pre_n <= ZH_DEEP_PRE), 0 without one
-  u32 dict_id;       // Dictionary_ID written to the frame header (0: none)
-};
-
-enum : u32 {
-  ZH_F_FIRST = 1u,   // first block of its frame: writes the frame header, starts with reps {1,4,8}
-  ZH_F_LAST = 2u,    // last block of its frame: Last_Block bit
-  ZH_F_DIRECT = 4u,  // single-block frame written straight into the item's output
-  ZH_F_CHECKSUM = 8u,  // frame carries a content checksum (first block: FHD bit; zh_checksum_kernel appends it)
-  ZH_F_DICT = 16u,     // dictionary frame: Dictionary_ID in the header, repcodes start unknown
-  ZH_F_DEEP = 32u,     // level >= ZH_DEEP_LEVEL (zh_lz_deep.hip): a dictionary frame's first block is staged
-                       // behind the last ZH_DEEP_PRE content bytes
-  ZH_F_LDM = 64u,      // one-sequence block of a long-distance match (zh_ldm.hip): n = 0, so K1-K4 skip the slot; its
-                       // bytes and staged size are already written, and the gather copies them like any block's
-  ZH_F_DICTENT = 128u, // CompressionConfig::dict_entropy with a formatted dictionary (ZhWorkspace::dent): the first
-                       // block of a frame starts from the dictionary's repcodes and may reuse its entropy tables
-                       // (treeless literals, Repeat_Mode sequence tables)
-  ZH_F_STATS = 256u,   // statistics pass of dictionary finalisation: the entropy kernel adds every block's literal
-                       // histogram and LL / OF / ML code counts to ZhWorkspace::stats (integer atomics)
-};
 // ZhWorkspace::stats: u32[ZH_STATS_WORDS] = literal byte counts | LL | OF | ML code counts (64 each)
 #define ZH_STATS_LIT 0u
 #define ZH_STATS_LL 256u
@@ -165,9 +132,6 @@ __device__ __forceinline__ u32 zh_k3_index(u32 e, u32 t, u32 L, u32 m) {
   u32 const g = __umulhi(e << 8, m), r = e - g * L;
   return ((r / ZH_K3_RUN) * ZH_K3_SLOTS + ZH_K3_SLOT(t, g)) * ZH_K3_RUN + (r & (ZH_K3_RUN - 1u));
 }
-
-// Status codes written per item (values of cuda_zstd::Status).
-enum : u32 { ZH_ST_OK = 0, ZH_ST_INVALID = 2, ZH_ST_TOO_SMALL = 7 };
 
 // ---------------- wave64 cross-lane helpers on DPP (VALU only, no LDS round trip) ----------------
 // Inclusive prefix with row_shr 1/2/4/8 inside 16-lane rows, then row_bcast:15 / row_bcast:31

@@ -299,77 +299,85 @@ Status cpu_decompress(const void *in, size_t n, void *out, size_t *out_size, hip
 }
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Workspace layout inside the caller's temp buffer
-struct WsLayout {
-  size_t descs, items, blk_size, item_size, item_status, staging, counter, blocks, deep, deep_slots, total;
-  // deep: a level >= ZH_DEEP_LEVEL call (the deep matcher's scratch slots, one per persistent
-  // workgroup, follow the block areas)
-  // ldm_cells > 0: a long-distance-matching call (zh_ldm.hip) over one frame of that many cells
-  // -- nblocks is then three slots per cell -- with its table of 2^ldm_tlog entries, the per-cell
-  // sample lists and the per-cell records behind everything else
-  size_t ldm_table, ldm_skey, ldm_sslot, ldm_scount, ldm_rec;
-  static WsLayout make(size_t nblocks, size_t nitems, bool staged, bool deep = false, size_t ldm_cells = 0, u32 ldm_tlog = 0) {
-    WsLayout L{};
-    size_t o = 0;
-    L.descs = o; o = align256(o + nblocks * sizeof(ZhBlockDesc));
-    L.items = o; o = align256(o + nitems * sizeof(ZhItemDesc));
-    L.blk_size = o; o = align256(o + nblocks * 4);
-    L.item_size = o; o = align256(o + nitems * 8);
-    L.item_status = o; o = align256(o + nitems * 4);
-    L.staging = o; o = align256(o + (staged ? nblocks * (size_t)ZH_STAGE_SLOT : 0));
-    L.counter = o; o = align256(o + 4);
-    L.blocks = o; o = align256(o + nblocks * (size_t)ZH_WS_BLOCK_BYTES);
-    L.deep_slots = deep ? std::min(nblocks, (size_t)ZH_DEEP_SLOTS_MAX) : 0;
-    L.deep = o; o = align256(o + L.deep_slots * ZH_DEEP_SLOT_BYTES);
-    if (ldm_cells) {
-      L.ldm_table = o; o = align256(o + (sizeof(u64) << ldm_tlog));
-      L.ldm_skey = o; o = align256(o + ldm_cells * ZH_LDM_CELL_SAMPLES * sizeof(u64));
-      L.ldm_sslot = o; o = align256(o + ldm_cells * ZH_LDM_CELL_SAMPLES * sizeof(u32));
-      L.ldm_scount = o; o = align256(o + ldm_cells * sizeof(u32));
-      L.ldm_rec = o; o = align256(o + ldm_cells * sizeof(ZhLdmRecord));
-    }
-    L.total = o + 256;  // slack for base alignment
-    return L;
-  }
-};
-
-// Device blocks of a frame of n bytes (ZH_FRAME_BLOCK: 64 KiB, or 32 KiB history blocks for
-// larger frames and for dictionary frames over 32 KiB below ZH_DEEP_LEVEL: split_dict)
-inline size_t block_size_of(size_t n, bool split_dict) { return ZH_FRAME_BLOCK(n, split_dict); }
-// Workspace of a mixed-level batch (compress_batch_device_levels): the layout of a deep-level call
-// (any item may take the deep matcher) and behind it the items' ranks, one level byte per block slot
-// and the class ranges with the matchers' counters
-struct LevelsLayout {
-  WsLayout ws;
-  size_t rank, blk_level, ranges, total;
-  static LevelsLayout make(size_t nblocks, size_t nitems, bool staged) {
-    LevelsLayout L{};
-    L.ws = WsLayout::make(nblocks, nitems, staged, true);
-    size_t o = L.ws.total - 256;
-    L.rank = o; o = align256(o + nitems * 4);
-    L.blk_level = o; o = align256(o + nblocks);
-    L.ranges = o; o = align256(o + sizeof(ZhClassRanges));
-    L.total = o + 256;  // slack for base alignment
-    return L;
-  }
-};
-
-inline bool split_dict_of(bool has_dict, int level) { return has_dict && level < ZH_DEEP_LEVEL; }
-inline size_t blocks_of(size_t n, bool split_dict = false) {
-  size_t const bs = block_size_of(n, split_dict);
-  return (n + bs - 1) / bs;
-}
+// A caller's temp buffer starts at its first 256-byte boundary (every layout's total holds the slack)
+inline u8 *aligned_base(void *temp) { return (u8 *)align256((uintptr_t)temp); }
 
 // Long-distance matching applies to a frame of n bytes: asked for, no dictionary or history, a
 // window that reaches past one block, more than one device block, 32-bit positions
 inline bool ldm_applies(const CompressionConfig &c, size_t n, bool has_dict) {
   return c.enable_ldm && !has_dict && c.window_log >= ZH_HIST_WINDOW_LOG && n > (size_t)ZH_BLOCK_MAX && n <= ZH_LDM_MAX_FRAME;
 }
-inline WsLayout ldm_layout(const CompressionConfig &c, size_t n) {
-  size_t const cells = blocks_of(n);
-  return WsLayout::make(3 * cells, 1, true, c.level >= ZH_DEEP_LEVEL, cells, zh_ldm_table_log(n, c.ldm_hash_log));
-}
+
+// What a compress call's workspace depends on.  Every size query and every compress entry builds
+// its shape here, so a query and the call it sizes for cannot disagree.
+struct BatchShape {
+  size_t nblocks = 0, nitems = 0;
+  bool staged = false;   // some frame has more than one block: staging slots, the gather
+  bool deep = false;     // a level >= ZH_DEEP_LEVEL call: the deep matcher's scratch slots
+  bool levels = false;   // a mixed-level batch: ranks, level bytes, class ranges
+  size_t ldm_cells = 0;  // a long-distance-matching call over one frame of that many cells (three block slots each)
+  u32 ldm_tlog = 0;      // with its table of 2^ldm_tlog entries
+  // the host plan: frames of these sizes, one after the other
+  BatchShape(const size_t *sizes, size_t count, const CompressionConfig &c, bool has_dict) : nitems(count), deep(c.level >= ZH_DEEP_LEVEL) {
+    for (size_t i = 0; i < count; i++) {
+      size_t const nb = zh_frame_blocks(sizes[i], zh_split_dict(c.level, has_dict));
+      nblocks += nb;
+      staged |= nb > 1;
+    }
+  }
+  // the device plans: every item takes the block slots of a frame of max_chunk bytes (at least one)
+  BatchShape(size_t count, size_t max_chunk, int level, bool split_dict) : nitems(count), deep(level >= ZH_DEEP_LEVEL) {
+    size_t const bpi = std::max<size_t>(1, zh_frame_blocks(max_chunk, split_dict));
+    nblocks = count * bpi;
+    staged = bpi > 1;
+  }
+  // a mixed-level batch: any item may be deep; no dictionary
+  static BatchShape mixed_levels(size_t count, size_t max_chunk) { BatchShape s(count, max_chunk, ZH_DEEP_LEVEL, false); s.levels = true; return s; }
+  // compress() of one frame long-distance matching applies to
+  static BatchShape ldm_frame(const CompressionConfig &c, size_t n) {
+    BatchShape s(1, n, c.level, false);
+    s.ldm_cells = s.nblocks;
+    s.nblocks *= 3;
+    s.staged = true;
+    s.ldm_tlog = zh_ldm_table_log(n, c.ldm_hash_log);
+    return s;
+  }
+};
+
+// Workspace layout inside the caller's temp buffer: the regions every call has, then the deep
+// matcher's scratch slots (one per persistent workgroup), then the long-distance finder's table,
+// per-cell sample lists and records, then a mixed-level batch's ranks, level bytes and class ranges
+// (the optional regions are empty when the shape does not ask for them)
+struct WsLayout {
+  size_t descs, items, blk_size, item_size, item_status, staging, counter, blocks, deep, deep_slots, total;
+  size_t ldm_table, ldm_skey, ldm_sslot, ldm_scount, ldm_rec;
+  size_t rank, blk_level, ranges;
+  BatchShape shape;
+  explicit WsLayout(const BatchShape &s) : shape(s) {
+    size_t const nblocks = s.nblocks, nitems = s.nitems, cells = s.ldm_cells;
+    size_t o = 0;
+    auto take = [&o](size_t bytes) { size_t const at = o; o = align256(o + bytes); return at; };  // (0 bytes: an empty region)
+    descs = take(nblocks * sizeof(ZhBlockDesc));
+    items = take(nitems * sizeof(ZhItemDesc));
+    blk_size = take(nblocks * 4);
+    item_size = take(nitems * 8);
+    item_status = take(nitems * 4);
+    staging = take(s.staged ? nblocks * (size_t)ZH_STAGE_SLOT : 0);
+    counter = take(4);
+    blocks = take(nblocks * (size_t)ZH_WS_BLOCK_BYTES);
+    deep_slots = s.deep ? std::min(nblocks, (size_t)ZH_DEEP_SLOTS_MAX) : 0;
+    deep = take(deep_slots * ZH_DEEP_SLOT_BYTES);
+    ldm_table = take(cells ? sizeof(u64) << s.ldm_tlog : 0);
+    ldm_skey = take(cells * ZH_LDM_CELL_SAMPLES * sizeof(u64));
+    ldm_sslot = take(cells * ZH_LDM_CELL_SAMPLES * sizeof(u32));
+    ldm_scount = take(cells * sizeof(u32));
+    ldm_rec = take(cells * sizeof(ZhLdmRecord));
+    rank = take(s.levels ? nitems * 4 : 0);
+    blk_level = take(s.levels ? nblocks : 0);
+    ranges = take(s.levels ? sizeof(ZhClassRanges) : 0);
+    total = o + 256;  // slack for base alignment
+  }
+};
 
 // Decoder workspace (zh_decode.hip): per-item arrays (host-array entry points upload
 // them), then one slot per item holding the literals and sequence records of the block
@@ -565,37 +573,56 @@ struct DevDict {
   }
 };
 
-// Descriptor fields of a block: a dictionary frame's first block gets the content tail that
-// fits in front of it in K1's 64 KiB of LDS; a later block of a history frame gets the 32 KiB
-// of input before it (when the window reaches that far)
-void set_dict_block(ZhBlockDesc &d, const DevDict *dd, bool first, bool hist, bool deep) {
-  d.pre = nullptr;
-  d.pre_n = 0;
-  d.dict_id = 0;
-  if (!first && hist) {
-    d.pre = d.src - ZH_HIST_BLOCK;
-    d.pre_n = ZH_HIST_BLOCK;
+// The batch of layout L bound to its (aligned) workspace: every pointer the plan and the stages
+// take, the descriptor rule's batch constants (plan.out_cap is the caller's: one per batch on the
+// device routes, one per item on the host route) and the filled ZhWorkspace.  dd: the batch's
+// dictionary or null; stats: collect_entropy_stats' histograms or null.
+ZhBatch bind_batch(const WsLayout &L, u8 *base, const DevDict *dd, const CompressionConfig &c, u32 *stats = nullptr) {
+  if (dd && !dd->n) dd = nullptr;
+  ZhBatch b{};
+  b.descs = (ZhBlockDesc *)(base + L.descs);
+  b.items = (ZhItemDesc *)(base + L.items);
+  b.item_size = (u64 *)(base + L.item_size);
+  b.item_status = (u32 *)(base + L.item_status);
+  b.blk_size = (u32 *)(base + L.blk_size);
+  b.nblocks = (u32)L.shape.nblocks;
+  b.nitems = (u32)L.shape.nitems;
+  b.block_size = c.block_size;
+  b.level = c.level;
+  b.gather = L.shape.staged;
+  b.checksum = c.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY;
+  // a mixed-level batch: every level's window reaches the previous block, and the entropy kernel
+  // takes each block's window descriptor from its level byte
+  b.window_log = L.shape.levels ? 0u : c.window_log;
+  const ZhDictEnt *const dent = dd ? dd->dent(c) : nullptr;
+  b.plan.flags = (b.checksum ? ZH_F_CHECKSUM : 0u) | (dent ? ZH_F_DICTENT : 0u) | (stats ? ZH_F_STATS : 0u);
+  b.plan.hist = L.shape.levels || c.window_log >= ZH_HIST_WINDOW_LOG;
+  if (dd) {
+    b.plan.dict = dd->content();
+    b.plan.dict_n = (u32)dd->content_n();
+    b.plan.dict_id = dd->id;
   }
-  if (!dd || !dd->n) return;
-  d.flags |= ZH_F_DICT;
-  d.dict_id = dd->id;
-  if (!first) return;
-  size_t const cn = dd->content_n();
-  // (the deep matcher of levels >= ZH_DEEP_LEVEL stages up to ZH_DEEP_PRE content bytes: it keeps
-  // the staged bytes in global memory, not in K1's 64 KiB of LDS)
-  d.pre_n = (u32)std::min(cn, deep ? (size_t)ZH_DEEP_PRE : (size_t)ZH_BLOCK_MAX - d.n);
-  d.pre = dd->content() + cn - d.pre_n;
-}
-
-// the deep matcher's precomputed dictionary chains, when the dictionary has them
-void set_deep_dict(ZhWorkspace &ws, const DevDict *dd) {
-  ws.dd_prev = ws.dd_head = nullptr;
-  ws.dd_pre = ws.dd_split = 0;
-  if (!dd || !dd->deep_P) return;
-  ws.dd_prev = dd->deep_prev;
-  ws.dd_head = dd->deep_head;
-  ws.dd_pre = dd->deep_P;
-  ws.dd_split = dd->deep_split;
+  b.plan.staging = base + L.staging;
+  b.ws.base = base + L.blocks;
+  b.ws.ctr = (u32 *)(base + L.counter);
+  b.ws.dtab = dd && dd->tabs_P ? dd->tabs : nullptr;  // K1's tables of the dictionary's content tail
+  b.ws.dtab_P = dd ? dd->tabs_P : 0u;
+  if (dd && dd->deep_P) {  // the deep matcher's precomputed dictionary chains, when the dictionary has them
+    b.ws.dd_prev = dd->deep_prev;
+    b.ws.dd_head = dd->deep_head;
+    b.ws.dd_pre = dd->deep_P;
+    b.ws.dd_split = dd->deep_split;
+  }
+  b.ws.deep_slots = L.deep_slots ? base + L.deep : nullptr;
+  b.ws.deep_nslots = (u32)L.deep_slots;
+  b.ws.dent = dent;
+  b.ws.stats = stats;
+  if (L.shape.levels) {
+    b.rank = (u32 *)(base + L.rank);
+    b.blk_level = base + L.blk_level;
+    b.ranges = (ZhClassRanges *)(base + L.ranges);
+  }
+  return b;
 }
 
 Status from_item_status(u32 s) {
@@ -633,7 +660,12 @@ class ZstdBatchManager::Impl {
     return pinned;
   }
 
-  // The long-distance finder over one frame (layout L = ldm_layout): descriptors, one-sequence
+  // compress_batch_device's shape, for the manager's level and dictionary as set now
+  BatchShape device_shape(size_t count, size_t max_chunk) const {
+    return BatchShape(count, max_chunk, config.level, zh_split_dict(config.level, active() != nullptr));
+  }
+
+  // The long-distance finder over one frame (layout L of BatchShape::ldm_frame): descriptors, one-sequence
   // blocks, staged sizes and records of all its cells
   hipError_t launch_ldm(const WsLayout &L, u8 *base, const void *src, size_t n, size_t cells, u32 flags, hipStream_t stream) {
     return zh::ldm_launch((const u8 *)src, n, (u32)cells, zh_ldm_table_log(n, config.ldm_hash_log), zh_ldm_max_dist(config.window_log), flags,
@@ -642,30 +674,54 @@ class ZstdBatchManager::Impl {
                           stream);
   }
 
+  // The device-planned entries: plan and stages, stream-ordered, nothing synchronised.  Sizes land
+  // in d_out_sizes, statuses in d_statuses (or the workspace); every item's capacity is the bound of
+  // max_chunk.  levels: one level per item in a.levels, read on the device -- the rank kernel sorts
+  // the items by parse class, the plan writes the descriptors at their sorted slots, and the matchers
+  // run over class ranges they read from the workspace; the manager's level is not used.
+  Status run_device(const ZhPlanArrays &a, bool levels, size_t max_chunk, size_t count, size_t *d_out_sizes, int *d_statuses, void *temp,
+                    size_t temp_size, hipStream_t stream) {
+    // one manager serialises calls (the dictionary's use events: set_dictionary waits on them)
+    std::lock_guard<std::mutex> lock(api_mutex);
+    Status s = ensure_kernels();
+    if (s != Status::SUCCESS) return s;
+    if (!count) return Status::SUCCESS;
+    if (!a.in_ptrs || !a.in_sizes || !a.out_ptrs || !d_out_sizes || max_chunk == 0) return Status::ERROR_INVALID_PARAMETER;
+    // (with a dictionary set, chunks over 32 KiB take two history blocks: a larger workspace
+    // than get_batch_device_temp_size's, from nvcomp_zstd_batch_get_compress_temp_size_v5)
+    const DevDict *dd = active();
+    // a dictionary frame's block split depends on its level (zh_split_dict): no one bpi per mixed-level batch
+    if (levels && (!a.levels || dd)) return Status::ERROR_INVALID_PARAMETER;
+    BatchShape const shape = levels ? BatchShape::mixed_levels(count, max_chunk) : device_shape(count, max_chunk);
+    if (levels && (count > ZH_RANK_MAX_ITEMS || shape.nblocks > 0xFFFFFFFFull)) return Status::ERROR_INVALID_PARAMETER;
+    WsLayout const L(shape);
+    if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
+    ZhBatch b = bind_batch(L, aligned_base(temp), dd, config);
+    b.plan.out_cap = estimate_compressed_size(max_chunk, config.level);
+    b.item_size = (u64 *)d_out_sizes;
+    if (d_statuses) b.item_status = (u32 *)d_statuses;
+    hipError_t e = zh::launch_plan(b, a, stream);
+    if (e == hipSuccess) e = zh::launch_compress(b, stream);
+    if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
+    return dd ? dd->note_use(stream) : Status::SUCCESS;
+  }
+
   // Run the device pipeline over a list of frames given as host arrays.
   // out_sizes: in = capacity, out = bytes; statuses out.
   Status run(const void *const *in_ptrs, const size_t *in_sizes, size_t count, void *const *out_ptrs, size_t *out_sizes, Status *statuses,
              void *temp, size_t temp_size, hipStream_t stream, const DevDict *dd = nullptr, bool allow_ldm = false) {
     Status s = ensure_kernels();
     if (s != Status::SUCCESS) return s;
-    size_t nblocks = 0;
-    bool staged = false;
     bool const has_dict = dd && dd->n;
-    bool const hist = config.window_log >= ZH_HIST_WINDOW_LOG;
-    for (size_t i = 0; i < count; i++) {
-      size_t nb = blocks_of(in_sizes[i], split_dict_of(has_dict, config.level));
-      nblocks += nb;
-      staged |= nb > 1;
-    }
     // long-distance matching (allow_ldm: compress() of one frame, whose workspace query sized for
     // it; the batch entries never ask): three slots per cell, the cells' descriptors come from
     // zh_ldm_cell_kernel instead of the loop below
     bool const ldm = allow_ldm && count == 1 && ldm_applies(config, in_sizes[0], has_dict);
-    size_t const ldm_cells = ldm ? nblocks : 0;
-    if (ldm) nblocks *= 3;
-    WsLayout L = ldm ? ldm_layout(config, in_sizes[0]) : WsLayout::make(nblocks, count, staged, config.level >= ZH_DEEP_LEVEL);
+    WsLayout const L(ldm ? BatchShape::ldm_frame(config, in_sizes[0]) : BatchShape(in_sizes, count, config, has_dict));
+    size_t const nblocks = L.shape.nblocks, ldm_cells = L.shape.ldm_cells;
     if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
-    u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
+    u8 *base = aligned_base(temp);
+    ZhBatch batch = bind_batch(L, base, dd, config, stats_dev);
 
     // host plan -> one pinned upload
     size_t const up_bytes = L.blk_size;  // descs + items
@@ -673,52 +729,23 @@ class ZstdBatchManager::Impl {
     if (!h) return Status::ERROR_OUT_OF_MEMORY;
     ZhBlockDesc *hd = (ZhBlockDesc *)(h + L.descs);
     ZhItemDesc *hi = (ZhItemDesc *)(h + L.items);
-    u8 *staging = base + L.staging;
-    size_t b = 0;
-    const ZhDictEnt *const dent = dd ? dd->dent(config) : nullptr;
-    u32 const frame_flags = (config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY ? ZH_F_CHECKSUM : 0u) |
-                            (config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u) | (dent ? ZH_F_DICTENT : 0u) |
-                            (stats_dev ? ZH_F_STATS : 0u);
+    u32 b = 0;
     for (size_t i = 0; i < count; i++) {
-      bool const sd = split_dict_of(has_dict, config.level);
-      size_t const n = in_sizes[i], nb = ldm ? 0 : blocks_of(n, sd), bs = block_size_of(n, sd);
-      hi[i].dst = (u8 *)out_ptrs[i];
-      hi[i].cap = out_sizes[i];
-      hi[i].first_block = (u32)b;
-      hi[i].nblocks = (u32)(ldm ? nblocks : nb);
-      for (size_t k = 0; k < nb; k++, b++) {
-        ZhBlockDesc &d = hd[b];
-        d.src = (const u8 *)in_ptrs[i] + k * bs;
-        d.frame_size = n;
-        d.n = (u32)std::min(bs, n - k * bs);
-        d.item = (u32)i;
-        d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) | frame_flags;
-        set_dict_block(d, dd, k == 0, hist, config.level >= ZH_DEEP_LEVEL);
-        if (nb == 1) {
-          d.dst = (u8 *)out_ptrs[i];
-          d.dst_cap = (u32)std::min(out_sizes[i], (size_t)0xFFFFFFFFu);
-        } else {
-          d.dst = staging + b * (size_t)ZH_STAGE_SLOT;
-          d.dst_cap = ZH_STAGE_SLOT;
-        }
-      }
+      ZhPlanItem const it{(const u8 *)in_ptrs[i], in_sizes[i], (u32)i, config.level, (u8 *)out_ptrs[i]};
+      batch.plan.out_cap = out_sizes[i];
+      bool invalid;  // (an empty item never gets here: the entries reject it)
+      hi[i] = zh_item_desc(batch.plan, it, b, &invalid);
+      if (ldm) hi[i].nblocks = (u32)nblocks;  // every slot of every cell; the finder writes the block descriptors
+      else for (u32 k = 0; k < hi[i].nblocks; k++, b++) hd[b] = zh_block_desc(batch.plan, it, k, b);
     }
-    if (ldm) {  // the item descriptor only; the finder writes the block descriptors, stream-ordered in front of K1
+    if (ldm) {  // the item descriptor only; the finder's launch is stream-ordered in front of K1
+      u32 const flags = batch.plan.flags | (config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u);
       if (hipMemcpyAsync(base + L.items, h + L.items, up_bytes - L.items, hipMemcpyHostToDevice, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
-      if (launch_ldm(L, base, in_ptrs[0], in_sizes[0], ldm_cells, frame_flags, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+      if (launch_ldm(L, base, in_ptrs[0], in_sizes[0], ldm_cells, flags, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
     } else if (hipMemcpyAsync(base, h, up_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
       return Status::ERROR_CUDA_ERROR;
     }
-    ZhWorkspace ws{base + L.blocks, (u32 *)(base + L.counter), dd && dd->tabs_P ? dd->tabs : nullptr, dd ? dd->tabs_P : 0u};
-    set_deep_dict(ws, dd);
-    ws.deep_slots = L.deep_slots ? base + L.deep : nullptr;
-    ws.deep_nslots = (u32)L.deep_slots;
-    ws.dent = dent;
-    ws.stats = stats_dev;
-    hipError_t e = zh::launch_compress((const ZhBlockDesc *)(base + L.descs), (u32)nblocks, ws, config.window_log, config.block_size,
-                                       (u64 *)(base + L.item_size), (u32 *)(base + L.item_status), (u32 *)(base + L.blk_size),
-                                       (const ZhItemDesc *)(base + L.items), (u32)count, staged,
-                                       config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY, config.level, stream);
+    hipError_t e = zh::launch_compress(batch, stream);
     if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
     u64 *h_size = (u64 *)(h + up_bytes);
     u32 *h_status = (u32 *)(h_size + count);
@@ -749,7 +776,7 @@ class ZstdBatchManager::Impl {
     for (size_t i = 0; i < count; i++) maxcap = std::max(maxcap, out_sizes[i]);
     DecLayout L = DecLayout::make(count, maxcap);
     if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
-    u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
+    u8 *base = aligned_base(temp);
     size_t const up = L.out_sizes, down = L.slots - L.out_sizes;
     u8 *h = (u8 *)host_scratch(up + down);
     if (!h) return Status::ERROR_OUT_OF_MEMORY;
@@ -795,7 +822,7 @@ class ZstdBatchManager::Impl {
     if (s != Status::SUCCESS) return s;
     DecLayout L = DecLayout::make(1, cap);
     if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
-    u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
+    u8 *base = aligned_base(temp);
     ZhDecArgs a = L.args(base);
     (dd ? *dd : mgr_dict).fill(a);
     a.one_in = in;
@@ -834,11 +861,10 @@ CompressionConfig ZstdBatchManager::get_config() const { return pimpl_->config; 
 
 // sized for the dictionary layout as well (a per-call dictionary is only known at compress())
 size_t ZstdBatchManager::get_compress_temp_size(size_t n) const {
-  size_t nb = std::max<size_t>(1, blocks_of(n, true));
-  size_t const plain = WsLayout::make(nb, 1, nb > 1, pimpl_->config.level >= ZH_DEEP_LEVEL).total;
+  size_t const plain = WsLayout(BatchShape(1, n, pimpl_->config.level, true)).total;
   // long-distance matching: three slots per cell, the table and the sample lists (a dictionary
   // given at compress() switches it off: the plain layout must fit too)
-  return ldm_applies(pimpl_->config, n, false) ? std::max(plain, ldm_layout(pimpl_->config, n).total) : plain;
+  return ldm_applies(pimpl_->config, n, false) ? std::max(plain, WsLayout(BatchShape::ldm_frame(pimpl_->config, n)).total) : plain;
 }
 
 Status ZstdBatchManager::collect_entropy_stats(const void *const *d_ptrs, const size_t *sizes, size_t count, unsigned int *counts,
@@ -851,11 +877,7 @@ Status ZstdBatchManager::collect_entropy_stats(const void *const *d_ptrs, const 
     osz[i] = estimate_compressed_size(sizes[i], pimpl_->config.level);
     off[i + 1] = off[i] + ((osz[i] + 255) & ~(size_t)255);
   }
-  bool const sd = split_dict_of(pimpl_->active() != nullptr, pimpl_->config.level);
-  size_t nb = 0;
-  bool staged = false;
-  for (size_t s : isz) { size_t const k = blocks_of(s, sd); nb += k; staged |= k > 1; }
-  size_t const temp_bytes = WsLayout::make(nb, count, staged, pimpl_->config.level >= ZH_DEEP_LEVEL).total + 256;
+  size_t const temp_bytes = WsLayout(BatchShape(isz.data(), count, pimpl_->config, pimpl_->active() != nullptr)).total;
   u8 *buf = nullptr;
   size_t const stats_off = (off[count] + 255) & ~(size_t)255, temp_off = stats_off + 4096;
   if (hipMalloc(&buf, temp_off + temp_bytes) != hipSuccess) return Status::ERROR_OUT_OF_MEMORY;
@@ -883,11 +905,11 @@ Status ZstdBatchManager::ldm_plan(const void *d_src, size_t size, unsigned int *
   if (!is_device_ptr(d_src)) return Status::ERROR_INVALID_PARAMETER;
   Status s = ensure_kernels();
   if (s != Status::SUCCESS) return s;
-  WsLayout const L = ldm_layout(pimpl_->config, size);
-  size_t const cells = blocks_of(size);
+  WsLayout const L(BatchShape::ldm_frame(pimpl_->config, size));
+  size_t const cells = L.shape.ldm_cells;
   if (temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
   if (capacity < cells) return Status::ERROR_BUFFER_TOO_SMALL;
-  u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
+  u8 *base = aligned_base(temp);
   if (pimpl_->launch_ldm(L, base, d_src, size, cells, 0, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
   if (hipMemcpyAsync(host_records, base + L.ldm_rec, cells * sizeof(ZhLdmRecord), hipMemcpyDeviceToHost, stream) != hipSuccess)
     return Status::ERROR_CUDA_ERROR;
@@ -1027,14 +1049,10 @@ int ZstdBatchManager::get_compression_level() const { return pimpl_->config.leve
 void ZstdBatchManager::reset_stats() { pimpl_->stats = CompressionStats{}; }
 
 size_t ZstdBatchManager::get_batch_compress_temp_size(const std::vector<size_t> &sizes) const {
-  size_t nb = 0;
-  bool staged = false;
   // (for the manager's dictionary as set now -- compress_batch takes no per-call dictionary; a
   // dictionary set later may need more: ZH_FRAME_BLOCK, and the call then fails with
   // ERROR_BUFFER_TOO_SMALL)
-  bool const sd = split_dict_of(pimpl_->active() != nullptr, pimpl_->config.level);
-  for (size_t s : sizes) { size_t k = blocks_of(s, sd); nb += k; staged |= k > 1; }
-  return WsLayout::make(nb, sizes.size(), staged, pimpl_->config.level >= ZH_DEEP_LEVEL).total;
+  return WsLayout(BatchShape(sizes.data(), sizes.size(), pimpl_->config, pimpl_->active() != nullptr)).total;
 }
 size_t ZstdBatchManager::get_batch_decompress_temp_size(const std::vector<size_t> &sizes) const {
   return DecLayout::make(std::max<size_t>(1, sizes.size()), DecLayout::kBlockMax).total;
@@ -1157,96 +1175,27 @@ Status ZstdBatchManager::allocate_inference_workspace(size_t a, size_t b, void *
 Status ZstdBatchManager::free_inference_workspace(void *ptr) { return hipFree(ptr) == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR; }
 
 // (static: no dictionary, levels below ZH_DEEP_LEVEL; get_batch_device_temp_size_for covers the
-// manager's level and dictionary)
-// levels below ZH_DEEP_LEVEL without a dictionary (the deep matcher's scratch slots of levels >=
-// ZH_DEEP_LEVEL, up to ZH_DEEP_SLOTS_MAX x ZH_DEEP_SLOT_BYTES, are in get_batch_device_temp_size_for)
+// manager's level -- the deep matcher's scratch slots from ZH_DEEP_LEVEL on -- and dictionary)
 size_t ZstdBatchManager::get_batch_device_temp_size(size_t count, size_t max_chunk) {
-  size_t const bpi = std::max<size_t>(1, blocks_of(max_chunk));
-  return WsLayout::make(count * bpi, count, bpi > 1).total;
+  return WsLayout(BatchShape(count, max_chunk, 1, false)).total;
 }
 size_t ZstdBatchManager::get_batch_device_temp_size_for(size_t count, size_t max_chunk) const {
-  size_t const bpi = std::max<size_t>(1, blocks_of(max_chunk, split_dict_of(pimpl_->active() != nullptr, pimpl_->config.level)));
-  return WsLayout::make(count * bpi, count, bpi > 1, pimpl_->config.level >= ZH_DEEP_LEVEL).total;
+  return WsLayout(pimpl_->device_shape(count, max_chunk)).total;
 }
 
 Status ZstdBatchManager::compress_batch_device(const void *const *d_in_ptrs, const size_t *d_in_sizes, size_t max_chunk, size_t count,
                                                void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp, size_t temp_size,
                                                hipStream_t stream) {
-  // one manager serialises calls (the dictionary's use events: set_dictionary waits on them)
-  std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
-  Status s = ensure_kernels();
-  if (s != Status::SUCCESS) return s;
-  if (!count) return Status::SUCCESS;
-  if (!d_in_ptrs || !d_in_sizes || !d_out_ptrs || !d_out_sizes || max_chunk == 0) return Status::ERROR_INVALID_PARAMETER;
-  const DevDict *dd = pimpl_->active();
-  // (with a dictionary set, chunks over 32 KiB take two history blocks: a larger workspace
-  // than get_batch_device_temp_size's, from nvcomp_zstd_batch_get_compress_temp_size_v5)
-  size_t const bpi = blocks_of(max_chunk, split_dict_of(dd != nullptr, pimpl_->config.level)), nblocks = count * bpi;
-  WsLayout L = WsLayout::make(nblocks, count, bpi > 1, pimpl_->config.level >= ZH_DEEP_LEVEL);
-  if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
-  u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
-  u64 const cap = estimate_compressed_size(max_chunk, pimpl_->config.level);
-  u64 *item_size = (u64 *)d_out_sizes;
-  u32 *item_status = d_statuses ? (u32 *)d_statuses : (u32 *)(base + L.item_status);
-  bool const ck = pimpl_->config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY;
-  u32 const hist = pimpl_->config.window_log >= ZH_HIST_WINDOW_LOG ? 1u : 0u;
-  const ZhDictEnt *const dent = dd ? dd->dent(pimpl_->config) : nullptr;
-  hipError_t e = zh::launch_plan(d_in_ptrs, d_in_sizes, (u32)count, (u32)bpi, d_out_ptrs, cap, base + L.staging, (ZhBlockDesc *)(base + L.descs),
-                                 (ZhItemDesc *)(base + L.items), item_size, item_status,
-                                 (ck ? ZH_F_CHECKSUM : 0u) | (pimpl_->config.level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u) | (dent ? ZH_F_DICTENT : 0u),
-                                 dd ? dd->content() : nullptr, dd ? (u32)dd->content_n() : 0u, dd ? dd->id : 0u, hist, stream);
-  if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
-  ZhWorkspace ws{base + L.blocks, (u32 *)(base + L.counter), dd && dd->tabs_P ? dd->tabs : nullptr, dd ? dd->tabs_P : 0u};
-  set_deep_dict(ws, dd);
-  ws.deep_slots = L.deep_slots ? base + L.deep : nullptr;
-  ws.deep_nslots = (u32)L.deep_slots;
-  ws.dent = dent;
-  e = zh::launch_compress((const ZhBlockDesc *)(base + L.descs), (u32)nblocks, ws, pimpl_->config.window_log, pimpl_->config.block_size, item_size,
-                          item_status, (u32 *)(base + L.blk_size), (const ZhItemDesc *)(base + L.items), (u32)count, bpi > 1, ck,
-                          pimpl_->config.level, stream);
-  if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
-  return dd ? dd->note_use(stream) : Status::SUCCESS;
+  return pimpl_->run_device({d_in_ptrs, d_in_sizes, d_out_ptrs, nullptr}, false, max_chunk, count, d_out_sizes, d_statuses, temp, temp_size, stream);
 }
 
 size_t ZstdBatchManager::get_batch_device_levels_temp_size(size_t count, size_t max_chunk) {
-  size_t const bpi = std::max<size_t>(1, blocks_of(max_chunk));
-  return LevelsLayout::make(count * bpi, count, bpi > 1).total;
+  return WsLayout(BatchShape::mixed_levels(count, max_chunk)).total;
 }
-
-// compress_batch_device with one level per item, read on the device: the rank kernel sorts the
-// items by parse class, the plan writes the descriptors at their sorted slots, and the matchers run
-// over class ranges they read from the workspace.  The manager's level is not used.
 Status ZstdBatchManager::compress_batch_device_levels(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int *d_levels, size_t max_chunk,
                                                       size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp,
                                                       size_t temp_size, hipStream_t stream) {
-  std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
-  Status s = ensure_kernels();
-  if (s != Status::SUCCESS) return s;
-  if (!count) return Status::SUCCESS;
-  if (!d_in_ptrs || !d_in_sizes || !d_levels || !d_out_ptrs || !d_out_sizes || max_chunk == 0) return Status::ERROR_INVALID_PARAMETER;
-  // a dictionary frame's block split depends on its level (split_dict_of): no one bpi per batch
-  if (pimpl_->active()) return Status::ERROR_INVALID_PARAMETER;
-  size_t const bpi = blocks_of(max_chunk), nblocks = count * bpi;
-  if (count > ZH_RANK_MAX_ITEMS || nblocks > 0xFFFFFFFFull) return Status::ERROR_INVALID_PARAMETER;
-  LevelsLayout const L = LevelsLayout::make(nblocks, count, bpi > 1);
-  if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
-  u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
-  u64 const cap = estimate_compressed_size(max_chunk, pimpl_->config.level);
-  u64 *item_size = (u64 *)d_out_sizes;
-  u32 *item_status = d_statuses ? (u32 *)d_statuses : (u32 *)(base + L.ws.item_status);
-  bool const ck = pimpl_->config.checksum != ChecksumPolicy::NO_COMPUTE_NO_VERIFY;
-  ZhClassRanges *const ranges = (ZhClassRanges *)(base + L.ranges);
-  hipError_t e = zh::launch_plan_levels(d_in_ptrs, d_in_sizes, d_levels, (u32)count, (u32)bpi, d_out_ptrs, cap, base + L.ws.staging,
-                                        (ZhBlockDesc *)(base + L.ws.descs), base + L.blk_level, (u32 *)(base + L.rank), ranges,
-                                        (ZhItemDesc *)(base + L.ws.items), item_size, item_status, ck ? ZH_F_CHECKSUM : 0u, stream);
-  if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
-  ZhWorkspace ws{base + L.ws.blocks, (u32 *)(base + L.ws.counter), nullptr, 0u};
-  ws.deep_slots = base + L.ws.deep;
-  ws.deep_nslots = (u32)L.ws.deep_slots;
-  e = zh::launch_compress_levels((const ZhBlockDesc *)(base + L.ws.descs), (u32)nblocks, ws, pimpl_->config.block_size, item_size, item_status,
-                                 (u32 *)(base + L.ws.blk_size), (const ZhItemDesc *)(base + L.ws.items), (u32)count, bpi > 1, ck, ranges,
-                                 base + L.blk_level, stream);
-  return e == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
+  return pimpl_->run_device({d_in_ptrs, d_in_sizes, d_out_ptrs, d_levels}, true, max_chunk, count, d_out_sizes, d_statuses, temp, temp_size, stream);
 }
 
 size_t ZstdBatchManager::get_batch_device_decompress_temp_size(size_t count, size_t max_out) {
@@ -1264,7 +1213,7 @@ Status ZstdBatchManager::decompress_batch_device(const void *const *d_in_ptrs, c
   if (!d_in_ptrs || !d_in_sizes || !d_out_ptrs || !d_out_sizes || max_out == 0) return Status::ERROR_INVALID_PARAMETER;
   DecLayout L = DecLayout::make(count, max_out);
   if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
-  u8 *base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
+  u8 *base = aligned_base(temp);
   ZhDecArgs a = L.args(base);
   pimpl_->mgr_dict.fill(a);
   a.in_ptrs = d_in_ptrs;
@@ -1980,8 +1929,12 @@ size_t NvcompV5BatchManager::get_decompress_temp_size(const size_t *, size_t n, 
 size_t NvcompV5BatchManager::get_max_compressed_chunk_size(size_t n) const { return pimpl_->mgr.get_max_compressed_size(n); }
 const CompressionStats &NvcompV5BatchManager::get_stats() const { return pimpl_->mgr.get_stats(); }
 
-Status NvcompV5BatchManager::compress_async(const void *const *d_in, const size_t *in_sizes, size_t n, void *const *d_out, size_t *out_sizes,
-                                            void *temp, size_t temp_bytes, hipStream_t stream) {
+// compress_async / decompress_async: the four arrays (host or device) fetched into BatchItems, the
+// batch call, and the sizes written back (0 for a failed item).  cap_of(capacity, input size) = the
+// item's output capacity.
+template <typename Cap, typename Call>
+static Status nvcomp_batch(const void *const *d_in, const size_t *in_sizes, size_t n, void *const *d_out, size_t *out_sizes, hipStream_t stream,
+                           Cap cap_of, Call call) {
   if (!n) return Status::SUCCESS;
   if (!d_in || !in_sizes || !d_out || !out_sizes) return Status::ERROR_INVALID_PARAMETER;
   std::vector<const void *> hin;
@@ -1997,40 +1950,28 @@ Status NvcompV5BatchManager::compress_async(const void *const *d_in, const size_
     items[i].input_ptr = (void *)hin[i];
     items[i].output_ptr = hout[i];
     items[i].input_size = hsz[i];
-    // reference callers pass the compressed-size array uninitialised; treat 0 as "sized with the bound"
-    items[i].output_size = hcap[i] ? hcap[i] : get_max_compressed_chunk_size(hsz[i]);
+    items[i].output_size = cap_of(hcap[i], hsz[i]);
   }
-  Status r = pimpl_->mgr.compress_batch(items, temp, temp_bytes, stream);
+  Status r = call(items);
   for (size_t i = 0; i < n; i++) hcap[i] = items[i].status == Status::SUCCESS ? items[i].output_size : 0;
   Status w = is_device_ptr(out_sizes) ? copy_any(out_sizes, hcap.data(), n * sizeof(size_t), stream) : (memcpy(out_sizes, hcap.data(), n * sizeof(size_t)), Status::SUCCESS);
   return r != Status::SUCCESS ? r : w;
+}
+
+Status NvcompV5BatchManager::compress_async(const void *const *d_in, const size_t *in_sizes, size_t n, void *const *d_out, size_t *out_sizes,
+                                            void *temp, size_t temp_bytes, hipStream_t stream) {
+  // reference callers pass the compressed-size array uninitialised; treat 0 as "sized with the bound"
+  return nvcomp_batch(d_in, in_sizes, n, d_out, out_sizes, stream,
+                      [&](size_t cap, size_t in) { return cap ? cap : get_max_compressed_chunk_size(in); },
+                      [&](std::vector<BatchItem> &items) { return pimpl_->mgr.compress_batch(items, temp, temp_bytes, stream); });
 }
 
 // NvcompV5BatchManager::decompress_async (reference src/cuda_zstd_nvcomp.cpp:540-610): arrays on
 // the host or the device; uncompressed_sizes in = capacity, out = bytes (0 for a failed item).
 Status NvcompV5BatchManager::decompress_async(const void *const *d_in, const size_t *in_sizes, size_t n, void *const *d_out, size_t *out_sizes,
                                               void *temp, size_t temp_bytes, hipStream_t stream) {
-  if (!n) return Status::SUCCESS;
-  if (!d_in || !in_sizes || !d_out || !out_sizes) return Status::ERROR_INVALID_PARAMETER;
-  std::vector<const void *> hin;
-  std::vector<void *> hout;
-  std::vector<size_t> hsz, hcap;
-  Status s = fetch_array(hin, (const void *const *)d_in, n, stream);
-  if (s == Status::SUCCESS) s = fetch_array(hout, (void *const *)d_out, n, stream);
-  if (s == Status::SUCCESS) s = fetch_array(hsz, in_sizes, n, stream);
-  if (s == Status::SUCCESS) s = fetch_array(hcap, (const size_t *)out_sizes, n, stream);
-  if (s != Status::SUCCESS) return s;
-  std::vector<BatchItem> items(n);
-  for (size_t i = 0; i < n; i++) {
-    items[i].input_ptr = (void *)hin[i];
-    items[i].output_ptr = hout[i];
-    items[i].input_size = hsz[i];
-    items[i].output_size = hcap[i];
-  }
-  Status r = pimpl_->mgr.decompress_batch(items, temp, temp_bytes, stream);
-  for (size_t i = 0; i < n; i++) hcap[i] = items[i].status == Status::SUCCESS ? items[i].output_size : 0;
-  Status w = is_device_ptr(out_sizes) ? copy_any(out_sizes, hcap.data(), n * sizeof(size_t), stream) : (memcpy(out_sizes, hcap.data(), n * sizeof(size_t)), Status::SUCCESS);
-  return r != Status::SUCCESS ? r : w;
+  return nvcomp_batch(d_in, in_sizes, n, d_out, out_sizes, stream, [](size_t cap, size_t) { return cap; },
+                      [&](std::vector<BatchItem> &items) { return pimpl_->mgr.decompress_batch(items, temp, temp_bytes, stream); });
 }
 
 // nvcompBatchedZstdGetDecompressSizeAsync: device arrays only, stream-ordered, nvcomp codes
@@ -2985,7 +2926,7 @@ int cuda_zstd_seekable_read(nvcomp_zstd_batch_manager_t *mgr, const void *d_stre
   if (rc) return rc;
   size_t const n = (size_t)f.n, fixed = zh::seek_read_fixed_bytes(n);
   if (!d_temp || temp_bytes < fixed + 256) return 7;  // nothing launched
-  u8 *const base = (u8 *)(((uintptr_t)d_temp + 255) & ~(uintptr_t)255);
+  u8 *const base = aligned_base(d_temp);
   size_t const avail = temp_bytes - (size_t)(base - (u8 *)d_temp);
   if (zh::seek_index_launch(d_stream, size, n, f.entry, offset, length, d_out, base, stream) != hipSuccess) return 4;
   zh::SeekReadCtl ctl;

@@ -3,17 +3,6 @@
 #include "zh_common.h"
 #include "zh_ldm.h"
 
-// Per-item bookkeeping for frames that span several device blocks.
-struct ZhItemDesc {
-  u8 *dst;           // item output
-  u64 cap;           // item output capacity
-  u32 first_block;   // index of the item's first ZhBlockDesc
-  u32 nblocks;       // number of device blocks in the frame
-};
-
-// Staging slot for one block of a multi-block frame: worst case = raw block + frame header.
-#define ZH_STAGE_SLOT ((u32)ZH_BLOCK_MAX + 64u)
-
 // Decoder launch (zh_decode.hip): one workgroup per input buffer; every array is a
 // device array indexed by item.  Item i's workspace slot is ws + i * slot_bytes:
 // block_cap literal bytes (padded to lit_bytes), then seq_cap u64 sequence records.
@@ -39,6 +28,33 @@ struct ZhDecArgs {
 };
 #define ZH_DEC_HANDOFF_BYTES 5376u  // sizeof(DecHandoff), zh_decode.hip
 
+// One batch bound to its workspace (zh_host.cpp bind_batch): where the plan (launch_plan, or the
+// host's upload) writes and the stages (launch_compress) read.
+struct ZhBatch {
+  ZhBlockDesc *descs;  // nblocks block slots
+  ZhItemDesc *items;   // nitems
+  u64 *item_size;      // per item: the frame's bytes
+  u32 *item_status;    // per item: ZH_ST_*
+  u32 *blk_size;       // per block slot: staged bytes of a multi-block frame's block
+  ZhBatchPlan plan;    // the descriptor rule's batch constants (zh_block_plan.h), staging included
+  ZhWorkspace ws;
+  u32 *rank;              // a mixed-level batch (null otherwise): the items' ranks,
+  u8 *blk_level;          // one level byte per block slot,
+  ZhClassRanges *ranges;  // the class ranges with the matchers' counters
+  u32 nblocks, nitems;
+  u32 window_log, block_size;  // the frames' window descriptor (mixed-level: per block, from blk_level) and block size
+  int level;                   // every item's level (not read for a mixed-level batch)
+  bool gather, checksum;       // multi-block frames to concatenate; content checksums to append
+};
+
+// The device arrays launch_plan reads: the items' inputs and outputs
+struct ZhPlanArrays {
+  const void *const *in_ptrs;
+  const size_t *in_sizes;
+  void *const *out_ptrs;
+  const int *levels;  // one level per item (a mixed-level batch), or null
+};
+
 namespace zh {
 u32 dec_lds_bytes();
 // Walker (one pass; from 2,048 items a tables and a rest pass), sequence kernel, execution kernel.
@@ -54,26 +70,17 @@ u32 entropy_lds_bytes();
 // out = 2^15 u16, tmp32 = 2^15 u32 scratch; P = the tail length covered (0: none)
 hipError_t lz_dict_tables(const u8 *content, size_t cn, u16 *out, u32 *tmp32, u32 &P, hipStream_t stream);
 hipError_t lz_deep_dict_tables(const u8 *content, size_t cn, u8 *stg, u32 *dprev, u32 *dhead, u32 &P, u32 &split, hipStream_t stream);
-hipError_t launch_compress(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
-                           u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum, int level,
-                           hipStream_t stream);
+// The stages of one batch: the matchers (ranges null: every block at b.level; else the class ranges
+// the rank kernel left in *b.ranges), entropy, gather, checksum.
+hipError_t launch_compress(const ZhBatch &b, hipStream_t stream);
 void profile_enable(bool on);
 int profile_collect(double *totals);
-hipError_t launch_plan(const void *const *d_in_ptrs, const size_t *d_in_sizes, u32 nitems, u32 bpi, void *const *d_out_ptrs, u64 out_cap,
-                       u8 *staging, ZhBlockDesc *d_descs, ZhItemDesc *d_items, u64 *d_item_size, u32 *d_item_status, u32 extra_flags,
-                       const u8 *dict, u32 dict_n, u32 dict_id, u32 hist, hipStream_t stream);
-// Mixed-level batch (zh_plan.hip): d_levels[i] = item i's level, a device array.  launch_plan_levels
-// ranks the items by parse class (one workgroup, up to ZH_RANK_MAX_ITEMS items) and writes the
-// descriptors at their sorted slots with one level byte per slot; launch_compress_levels runs the
-// matchers over the class ranges left in *d_ranges, then the same entropy / gather / checksum stages.
+// Device plan (zh_plan.hip): descs, items and the invalid items' size and status from the device
+// arrays in `a`; every item takes nblocks / nitems block slots.  a.levels (a mixed-level batch):
+// the items are ranked by parse class (one workgroup, up to ZH_RANK_MAX_ITEMS items) and their
+// descriptors written at the sorted slots with one level byte per slot.
 #define ZH_RANK_MAX_ITEMS (1u << 20)
-hipError_t launch_plan_levels(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int *d_levels, u32 nitems, u32 bpi,
-                              void *const *d_out_ptrs, u64 out_cap, u8 *staging, ZhBlockDesc *d_descs, u8 *d_blk_level, u32 *d_rank,
-                              ZhClassRanges *d_ranges, ZhItemDesc *d_items, u64 *d_item_size, u32 *d_item_status, u32 extra_flags,
-                              hipStream_t stream);
-hipError_t launch_compress_levels(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 cfg_block_size, u64 *d_item_size,
-                                  u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum,
-                                  ZhClassRanges *d_ranges, const u8 *d_blk_level, hipStream_t stream);
+hipError_t launch_plan(const ZhBatch &b, const ZhPlanArrays &a, hipStream_t stream);
 // Long-distance matching (zh_ldm.hip): index + per-cell split of one frame, three descriptor slots per cell
 hipError_t ldm_launch(const u8 *src, u64 size, u32 ncells, u32 table_log, u32 max_dist, u32 flags, u64 *table, u64 *skey, u32 *sslot,
                       u32 *scount, ZhBlockDesc *descs, u8 *staging, u32 *blk_size, ZhLdmRecord *rec, hipStream_t stream);

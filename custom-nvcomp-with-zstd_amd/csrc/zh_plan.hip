@@ -1,9 +1,9 @@
 // zh_plan.hip — batch planning, multi-block frame gather, and launch wrappers.
 //
-// zh_plan_kernel : builds one ZhBlockDesc per (item, 64 KiB sub-block) from device
-//                  pointer/size arrays, for the stream-ordered batched entry point
-//                  (no host round trip, unlike the reference's compress_async,
-//                  src/cuda_zstd_nvcomp.cpp:319-437).
+// zh_plan_kernel : builds one ZhBlockDesc per (item, block slot) from device pointer/size
+//                  arrays with the rule of zh_block_plan.h, for the stream-ordered batched
+//                  entry points (no host round trip, unlike the reference's compress_async,
+//                  src/cuda_zstd_nvcomp.cpp:319-437); zh_plan_levels_kernel: one level per item.
 // zh_gather_kernel: concatenates the staged blocks of multi-block frames (the
 //                  reference assembles them on the host with blocking copies,
 //                  src/cuda_zstd_manager.cu:2765-3027).
@@ -30,54 +30,24 @@ void entropy_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32
                     u32 *d_item_status, u32 *d_blk_size, const u8 *d_blk_level, hipStream_t stream);
 }  // namespace zh
 
-extern "C" __global__ void zh_plan_kernel(const void *const *__restrict__ in_ptrs, const size_t *__restrict__ in_sizes, u32 nitems,
-                                          u32 bpi, void *const *__restrict__ out_ptrs, u64 out_cap, u8 *staging, ZhBlockDesc *descs,
-                                          ZhItemDesc *items, u64 *item_size, u32 *item_status, u32 extra_flags,
-                                          const u8 *dict, u32 dict_n, u32 dict_id, u32 hist) {
-  u32 const b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= nitems * bpi) return;
-  u32 const it = b / bpi, k = b % bpi;
-  u64 const size = in_sizes[it];
-  u64 const bs = ZH_FRAME_BLOCK(size, dict != nullptr && !(extra_flags & ZH_F_DEEP));
-  u64 const nb = (size + bs - 1) / bs;
-  ZhBlockDesc d;
-  d.src = (const u8 *)in_ptrs[it] + (u64)k * bs;
-  d.frame_size = size;
-  d.item = it;
-  d.n = (k < nb) ? (u32)min(bs, size - (u64)k * bs) : 0u;
-  d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) | extra_flags;
-  d.pre = nullptr;
-  d.pre_n = 0;
-  d.dict_id = 0;
-  if (k > 0 && hist) {  // history frame: the previous 32 KiB block is staged in front
-    d.pre = d.src - ZH_HIST_BLOCK;
-    d.pre_n = ZH_HIST_BLOCK;
-  }
-  if (dict) {  // dictionary frame: the first block is compressed behind the content's tail
-    d.flags |= ZH_F_DICT;
-    d.dict_id = dict_id;
-    if (k == 0) {
-      d.pre_n = (extra_flags & ZH_F_DEEP) ? min(dict_n, (u32)ZH_DEEP_PRE) : min(dict_n, (u32)ZH_BLOCK_MAX - d.n);
-      d.pre = dict + dict_n - d.pre_n;
-    }
-  }
-  if (nb == 1) {
-    d.dst = (u8 *)out_ptrs[it];
-    d.dst_cap = (u32)min(out_cap, (u64)0xFFFFFFFFu);
-  } else {
-    d.dst = staging + (size_t)b * ZH_STAGE_SLOT;
-    d.dst_cap = ZH_STAGE_SLOT;
-  }
-  descs[b] = d;
-  if (k == 0) {
-    ZhItemDesc id;
-    id.dst = (u8 *)out_ptrs[it];
-    id.cap = out_cap;
-    id.first_block = b;
-    id.nblocks = (u32)nb;
-    items[it] = id;
-    if (size == 0) { item_size[it] = 0; item_status[it] = ZH_ST_INVALID; }
-  }
+// The device plans: thread t is block k = t % bpi of item i = t / bpi, bpi = nblocks / nitems
+// slots per item, and writes block slot b with the rule of zh_block_plan.h.  valid false: an
+// inactive slot and an invalid item.
+__device__ inline void zh_plan_block(const ZhBatch &B, const ZhPlanArrays &a, u32 i, u32 k, u32 b, int level, bool valid) {
+  ZhPlanItem const it{(const u8 *)a.in_ptrs[i], a.in_sizes[i], i, level, (u8 *)a.out_ptrs[i]};
+  ZhBlockDesc d = zh_block_desc(B.plan, it, k, b);
+  if (!valid) d.n = 0;
+  B.descs[b] = d;
+  if (k != 0) return;
+  bool invalid;
+  B.items[i] = zh_item_desc(B.plan, it, b, &invalid);
+  if (invalid || !valid) { B.item_size[i] = 0; B.item_status[i] = ZH_ST_INVALID; }
+}
+
+// Every item at B.level, slots in item order.
+extern "C" __global__ void zh_plan_kernel(ZhBatch B, ZhPlanArrays a) {
+  u32 const t = blockIdx.x * blockDim.x + threadIdx.x, bpi = B.nblocks / B.nitems;
+  if (t < B.nblocks) zh_plan_block(B, a, t / bpi, t % bpi, t, B.level, true);
 }
 
 // ---- mixed-level batch: one level per item, on the device ----------------------
@@ -136,56 +106,20 @@ extern "C" __global__ __launch_bounds__(ZH_SCAN_THREADS) void zh_rank_kernel(con
   }
 }
 
-// zh_plan_kernel's sibling for a mixed-level batch: item i's bpi descriptors go to block slots
-// rank[i] * bpi .. (sorted by parse class), d.item stays i -- everything downstream of K1 indexes by
-// block and writes results by d.item, so outputs land in input order -- and the item's level is
-// stored per block slot.  A level outside 1..22: size 0, status invalid, inactive slots.  No dictionary.
-extern "C" __global__ void zh_plan_levels_kernel(const void *const *__restrict__ in_ptrs, const size_t *__restrict__ in_sizes,
-                                                 const int *__restrict__ levels, const u32 *__restrict__ rank, u32 nitems, u32 bpi,
-                                                 void *const *__restrict__ out_ptrs, u64 out_cap, u8 *staging, ZhBlockDesc *descs, u8 *blk_level,
-                                                 ZhItemDesc *items, u64 *item_size, u32 *item_status, u32 extra_flags) {
-  u32 const t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nitems * bpi) return;
-  u32 const it = t / bpi, k = t % bpi;
-  u32 const b = rank[it] * bpi + k;
-  int const level = levels[it];
+// zh_plan_kernel for a mixed-level batch: item i's level is a.levels[i], and its bpi descriptors go
+// to block slots rank[i] * bpi .. (sorted by parse class); d.item stays i -- everything downstream
+// of K1 indexes by block and writes results by d.item, so outputs land in input order -- and the
+// item's level is stored per block slot.  A level outside 1..22: size 0, status invalid, inactive slots.
+extern "C" __global__ void zh_plan_levels_kernel(ZhBatch B, ZhPlanArrays a) {
+  u32 const t = blockIdx.x * blockDim.x + threadIdx.x, bpi = B.nblocks / B.nitems;
+  if (t >= B.nblocks) return;
+  u32 const i = t / bpi, k = t % bpi, b = B.rank[i] * bpi + k;
+  int const level = a.levels[i];
   bool const valid = ZH_LEVEL_VALID(level);
-  u64 const size = in_sizes[it];
-  u64 const bs = ZH_FRAME_BLOCK(size, false);
-  u64 const nb = (size + bs - 1) / bs;
-  ZhBlockDesc d;
-  d.src = (const u8 *)in_ptrs[it] + (u64)k * bs;
-  d.frame_size = size;
-  d.item = it;
-  d.n = (valid && k < nb) ? (u32)min(bs, size - (u64)k * bs) : 0u;
-  d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) | extra_flags |
-            (level >= ZH_DEEP_LEVEL ? ZH_F_DEEP : 0u);
-  d.pre = nullptr;
-  d.pre_n = 0;
-  d.dict_id = 0;
-  if (k > 0) {  // history frame: the previous 32 KiB block is staged in front (every level's window reaches it)
-    d.pre = d.src - ZH_HIST_BLOCK;
-    d.pre_n = ZH_HIST_BLOCK;
-  }
-  if (nb == 1) {
-    d.dst = (u8 *)out_ptrs[it];
-    d.dst_cap = (u32)min(out_cap, (u64)0xFFFFFFFFu);
-  } else {
-    d.dst = staging + (size_t)b * ZH_STAGE_SLOT;
-    d.dst_cap = ZH_STAGE_SLOT;
-  }
-  descs[b] = d;
-  blk_level[b] = valid ? (u8)level : (u8)0;
-  if (k == 0) {
-    ZhItemDesc id;
-    id.dst = (u8 *)out_ptrs[it];
-    id.cap = out_cap;
-    id.first_block = b;
-    id.nblocks = (u32)nb;
-    items[it] = id;
-    if (size == 0 || !valid) { item_size[it] = 0; item_status[it] = ZH_ST_INVALID; }
-  }
+  zh_plan_block(B, a, i, k, b, level, valid);
+  B.blk_level[b] = valid ? (u8)level : (u8)0;
 }
+// (a mixed-level batch is bound with plan.hist set whatever the manager's window)
 static_assert(ZH_LEVEL_WINDOW_LOG(1) >= ZH_HIST_WINDOW_LOG, "every level's frames may reach the previous block");
 
 // One workgroup per block: a block of a multi-block frame sums the staged sizes of its
@@ -313,39 +247,36 @@ int profile_collect(double *totals) {
   return n;
 }
 
-// The stages of one batch.  d_ranges null: every block at `level` (launch_compress); else a
-// mixed-level batch (launch_compress_levels): the matchers run over the class ranges the rank kernel
-// left in *d_ranges, counters included, and d_blk_level holds every block slot's level.
-static hipError_t compress_stages(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
-                                  u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum,
-                                  int level, ZhClassRanges *d_ranges, const u8 *d_blk_level, hipStream_t stream) {
-  if (nblocks == 0) return hipSuccess;
+hipError_t launch_compress(const ZhBatch &b, hipStream_t stream) {
+  if (b.nblocks == 0) return hipSuccess;
   std::vector<hipEvent_t> ev;
   {
     std::lock_guard<std::mutex> g(prof().mu);
     if (prof().on) for (int k = 0; k < 4; k++) ev.push_back(prof_event());
   }
   if (!ev.empty()) (void)hipEventRecord(ev[0], stream);
-  if (d_ranges) {
+  if (b.ranges) {
     // four launches whatever the mix (the host cannot see which classes are empty): the three K1
     // parses, then the deep matcher over all its depths
-    lz_launch_ranged(d_descs, nblocks, ws, d_ranges, stream);
-    hipError_t const e = lz_deep_launch_ranged(d_descs, nblocks, ws, d_ranges, d_blk_level, stream);
+    lz_launch_ranged(b.descs, b.nblocks, b.ws, b.ranges, stream);
+    hipError_t const e = lz_deep_launch_ranged(b.descs, b.nblocks, b.ws, b.ranges, b.blk_level, stream);
     if (e != hipSuccess) return e;
-  } else if (level >= ZH_DEEP_LEVEL) {
+  } else if (b.level >= ZH_DEEP_LEVEL) {
     // levels >= ZH_DEEP_LEVEL: the deep chain matcher; below: K1's dual-hash parse
-    (void)hipMemsetAsync(ws.ctr, 0, 4, stream);  // the matcher's block counter
-    hipError_t const e = lz_deep_launch(d_descs, nblocks, ws, level, stream);
+    (void)hipMemsetAsync(b.ws.ctr, 0, 4, stream);  // the matcher's block counter
+    hipError_t const e = lz_deep_launch(b.descs, b.nblocks, b.ws, b.level, stream);
     if (e != hipSuccess) return e;
   } else {
-    (void)hipMemsetAsync(ws.ctr, 0, 4, stream);  // K1's block counter
-    lz_launch(d_descs, nblocks, ws, (u32)ZH_K1_MODE(level), stream);
+    (void)hipMemsetAsync(b.ws.ctr, 0, 4, stream);  // K1's block counter
+    lz_launch(b.descs, b.nblocks, b.ws, (u32)ZH_K1_MODE(b.level), stream);
   }
   if (!ev.empty()) (void)hipEventRecord(ev[1], stream);
-  entropy_launch(d_descs, nblocks, ws, window_log, cfg_block_size, d_item_size, d_item_status, d_blk_size, d_blk_level, stream);
+  entropy_launch(b.descs, b.nblocks, b.ws, b.window_log, b.block_size, b.item_size, b.item_status, b.blk_size, b.blk_level, stream);
   if (!ev.empty()) (void)hipEventRecord(ev[2], stream);
-  if (gather && nitems) hipLaunchKernelGGL(zh_gather_kernel, dim3(nblocks), dim3(256), 0, stream, d_items, d_descs, d_blk_size, d_item_size, d_item_status);
-  if (checksum && nitems) hipLaunchKernelGGL(zh_checksum_kernel, dim3(nitems), dim3(64), 0, stream, d_items, d_descs, d_item_size, d_item_status);
+  if (b.gather && b.nitems)
+    hipLaunchKernelGGL(zh_gather_kernel, dim3(b.nblocks), dim3(256), 0, stream, b.items, b.descs, b.blk_size, b.item_size, b.item_status);
+  if (b.checksum && b.nitems)
+    hipLaunchKernelGGL(zh_checksum_kernel, dim3(b.nitems), dim3(64), 0, stream, b.items, b.descs, b.item_size, b.item_status);
   if (!ev.empty()) {
     (void)hipEventRecord(ev[3], stream);
     std::lock_guard<std::mutex> g(prof().mu);
@@ -354,40 +285,16 @@ static hipError_t compress_stages(const ZhBlockDesc *d_descs, u32 nblocks, ZhWor
   return hipGetLastError();
 }
 
-hipError_t launch_compress(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
-                           u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum, int level,
-                           hipStream_t stream) {
-  return compress_stages(d_descs, nblocks, ws, window_log, cfg_block_size, d_item_size, d_item_status, d_blk_size, d_items, nitems, gather,
-                         checksum, level, nullptr, nullptr, stream);
-}
-
-hipError_t launch_compress_levels(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 cfg_block_size, u64 *d_item_size,
-                                  u32 *d_item_status, u32 *d_blk_size, const ZhItemDesc *d_items, u32 nitems, bool gather, bool checksum,
-                                  ZhClassRanges *d_ranges, const u8 *d_blk_level, hipStream_t stream) {
-  return compress_stages(d_descs, nblocks, ws, 0, cfg_block_size, d_item_size, d_item_status, d_blk_size, d_items, nitems, gather, checksum, 0,
-                         d_ranges, d_blk_level, stream);
-}
-
-hipError_t launch_plan_levels(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int *d_levels, u32 nitems, u32 bpi,
-                              void *const *d_out_ptrs, u64 out_cap, u8 *staging, ZhBlockDesc *d_descs, u8 *d_blk_level, u32 *d_rank,
-                              ZhClassRanges *d_ranges, ZhItemDesc *d_items, u64 *d_item_size, u32 *d_item_status, u32 extra_flags,
-                              hipStream_t stream) {
-  u32 const total = nitems * bpi;
-  if (!total) return hipSuccess;
-  if (nitems > ZH_RANK_MAX_ITEMS) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(zh_rank_kernel, dim3(1), dim3(ZH_SCAN_THREADS), 0, stream, d_levels, nitems, bpi, d_rank, d_ranges);
-  hipLaunchKernelGGL(zh_plan_levels_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, d_in_ptrs, d_in_sizes, d_levels, d_rank, nitems, bpi,
-                     d_out_ptrs, out_cap, staging, d_descs, d_blk_level, d_items, d_item_size, d_item_status, extra_flags);
-  return hipGetLastError();
-}
-
-hipError_t launch_plan(const void *const *d_in_ptrs, const size_t *d_in_sizes, u32 nitems, u32 bpi, void *const *d_out_ptrs, u64 out_cap,
-                       u8 *staging, ZhBlockDesc *d_descs, ZhItemDesc *d_items, u64 *d_item_size, u32 *d_item_status, u32 extra_flags,
-                       const u8 *dict, u32 dict_n, u32 dict_id, u32 hist, hipStream_t stream) {
-  u32 const total = nitems * bpi;
-  if (!total) return hipSuccess;
-  hipLaunchKernelGGL(zh_plan_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, d_in_ptrs, d_in_sizes, nitems, bpi, d_out_ptrs, out_cap,
-                     staging, d_descs, d_items, d_item_size, d_item_status, extra_flags, dict, dict_n, dict_id, hist);
+hipError_t launch_plan(const ZhBatch &b, const ZhPlanArrays &a, hipStream_t stream) {
+  if (!b.nblocks) return hipSuccess;
+  dim3 const grid((b.nblocks + 255) / 256);
+  if (a.levels) {
+    if (b.nitems > ZH_RANK_MAX_ITEMS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zh_rank_kernel, dim3(1), dim3(ZH_SCAN_THREADS), 0, stream, a.levels, b.nitems, b.nblocks / b.nitems, b.rank, b.ranges);
+    hipLaunchKernelGGL(zh_plan_levels_kernel, grid, dim3(256), 0, stream, b, a);
+  } else {
+    hipLaunchKernelGGL(zh_plan_kernel, grid, dim3(256), 0, stream, b, a);
+  }
   return hipGetLastError();
 }
 
