@@ -1,7 +1,7 @@
 // zh_block_plan.h — the block descriptors of a frame: the one rule behind the host plan
 // (ZstdBatchManager::Impl::run, zh_host.cpp) and the two device plans (zh_plan_kernel,
 // zh_plan_levels_kernel, zh_plan.hip).  Plain C++, no HIP types: tests/cpp/block_plan_check.cpp
-// walks the rule on the host.
+// and tests/cpp/prefix_plan_check.cpp (the per-item prefix) walk the rule on the host.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -73,13 +73,18 @@ struct ZhBatchPlan {
   u64 out_cap;     // output capacity: one for the batch (device plans), set per item by the host plan
 };
 
-// One item of the batch.
+// One item of the batch.  pre / pre_n: the item's own prefix (pre_n 0: none), the bytes that
+// precede the chunk as a raw-content dictionary without a Dictionary_ID; the item then gets the
+// descriptors of a batch whose dictionary is that prefix, an item without one those of a
+// dictionary-less frame.  Not together with ZhBatchPlan::dict.
 struct ZhPlanItem {
   const u8 *src;
   u64 size;
   u32 index;
   int level;
   u8 *out;
+  const u8 *pre = nullptr;
+  u64 pre_n = 0;
 };
 
 // A dictionary frame below ZH_DEEP_LEVEL is cut into 32 KiB blocks from 32 KiB on (ZH_FRAME_BLOCK)
@@ -91,15 +96,21 @@ ZH_BP_HD u64 zh_frame_blocks(u64 size, bool split_dict) {
 
 // Block k of item `it`, written to block slot `slot` (k at or past the frame's block count: an
 // inactive padding slot, n = 0).
+// The item's prefix source: the batch's dictionary, or the item's own prefix
+ZH_BP_HD bool zh_item_has_dict(const ZhBatchPlan &p, const ZhPlanItem &it) { return p.dict != nullptr || it.pre_n != 0; }
+// An item that names a prefix length without a pointer has no frame
+ZH_BP_HD bool zh_item_bad_prefix(const ZhBatchPlan &p, const ZhPlanItem &it) { return !p.dict && it.pre_n != 0 && it.pre == nullptr; }
+
 ZH_BP_HD ZhBlockDesc zh_block_desc(const ZhBatchPlan &p, const ZhPlanItem &it, u32 k, u32 slot) {
-  bool const deep = it.level >= ZH_DEEP_LEVEL, split = zh_split_dict(it.level, p.dict != nullptr);
+  bool const has_dict = zh_item_has_dict(p, it);
+  bool const deep = it.level >= ZH_DEEP_LEVEL, split = zh_split_dict(it.level, has_dict);
   u64 const bs = ZH_FRAME_BLOCK(it.size, split), nb = zh_frame_blocks(it.size, split);
   ZhBlockDesc d;
   d.src = it.src + (u64)k * bs;
   d.frame_size = it.size;
   d.item = it.index;
   d.n = 0;
-  if (k < nb) d.n = (u32)(it.size - (u64)k * bs < bs ? it.size - (u64)k * bs : bs);
+  if (k < nb && !zh_item_bad_prefix(p, it)) d.n = (u32)(it.size - (u64)k * bs < bs ? it.size - (u64)k * bs : bs);
   d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) | p.flags | (deep ? ZH_F_DEEP : 0u);
   d.pre = nullptr;
   d.pre_n = 0;
@@ -108,15 +119,17 @@ ZH_BP_HD ZhBlockDesc zh_block_desc(const ZhBatchPlan &p, const ZhPlanItem &it, u
     d.pre = d.src - ZH_HIST_BLOCK;
     d.pre_n = ZH_HIST_BLOCK;
   }
-  if (p.dict) {  // dictionary frame: the first block is compressed behind the content's tail
+  if (has_dict) {  // dictionary frame: the first block is compressed behind the content's tail
+    const u8 *const dict = p.dict ? p.dict : it.pre;
+    u64 const dict_n = p.dict ? (u64)p.dict_n : it.pre_n;
     d.flags |= ZH_F_DICT;
-    d.dict_id = p.dict_id;
+    d.dict_id = p.dict ? p.dict_id : 0u;
     if (k == 0) {
       // what fits in front of the block in K1's 64 KiB of LDS; the deep matcher keeps its staged
       // bytes in global memory and takes up to ZH_DEEP_PRE
       u32 const room = deep ? (u32)ZH_DEEP_PRE : (u32)ZH_BLOCK_MAX - d.n;
-      d.pre_n = p.dict_n < room ? p.dict_n : room;
-      d.pre = p.dict + p.dict_n - d.pre_n;
+      d.pre_n = dict_n < room ? (u32)dict_n : room;
+      d.pre = dict ? dict + dict_n - d.pre_n : nullptr;
     }
   }
   if (nb == 1) {
@@ -130,13 +143,14 @@ ZH_BP_HD ZhBlockDesc zh_block_desc(const ZhBatchPlan &p, const ZhPlanItem &it, u
 }
 
 // The item's descriptor, its blocks starting at block slot first_slot; *invalid: the item has no
-// frame (size 0: item size 0, status ZH_ST_INVALID).
+// frame (size 0, or a prefix length without a pointer: item size 0, status ZH_ST_INVALID, every
+// slot inactive).
 ZH_BP_HD ZhItemDesc zh_item_desc(const ZhBatchPlan &p, const ZhPlanItem &it, u32 first_slot, bool *invalid) {
   ZhItemDesc id;
   id.dst = it.out;
   id.cap = p.out_cap;
   id.first_block = first_slot;
-  id.nblocks = (u32)zh_frame_blocks(it.size, zh_split_dict(it.level, p.dict != nullptr));
-  *invalid = it.size == 0;
+  id.nblocks = (u32)zh_frame_blocks(it.size, zh_split_dict(it.level, zh_item_has_dict(p, it)));
+  *invalid = it.size == 0 || zh_item_bad_prefix(p, it);
   return id;
 }

@@ -1293,6 +1293,12 @@ __device__ __forceinline__ Item item_view(const ZhDecArgs &a, u32 idx) {
   it.ho = handoff(a, idx);
   it.dend = a.dict ? a.dict + a.dict_n : nullptr;
   it.dlen = a.dict ? (s64)(a.dict_n - a.dict_off) : 0;
+  if (a.pre_sizes) {  // the item's own prefix: raw content, the whole of it in front of the frame
+    const u8 *const pre = (const u8 *)a.pre_ptrs[idx];
+    u64 const pn = pre ? (u64)a.pre_sizes[idx] : 0ull;
+    it.dend = pn ? pre + pn : nullptr;
+    it.dlen = (s64)pn;
+  }
   return it;
 }
 // The Size pass's item: the input alone.  Its capacity is unbounded and its sequence count limit

@@ -38,6 +38,7 @@
 #include "zh_dict_train.h"
 #include "zh_launch.h"
 #include "zh_seek.h"
+#include "zh_stream_window.h"
 
 namespace cuda_zstd {
 
@@ -665,6 +666,9 @@ class ZstdBatchManager::Impl {
     return BatchShape(count, max_chunk, config.level, zh_split_dict(config.level, active() != nullptr));
   }
 
+  // compress_batch_device_prefix's shape: that of a manager with a dictionary at this level
+  BatchShape prefix_shape(size_t count, size_t max_chunk) const { return BatchShape(count, max_chunk, config.level, zh_split_dict(config.level, true)); }
+
   // The long-distance finder over one frame (layout L of BatchShape::ldm_frame): descriptors, one-sequence
   // blocks, staged sizes and records of all its cells
   hipError_t launch_ldm(const WsLayout &L, u8 *base, const void *src, size_t n, size_t cells, u32 flags, hipStream_t stream) {
@@ -679,6 +683,10 @@ class ZstdBatchManager::Impl {
   // max_chunk.  levels: one level per item in a.levels, read on the device -- the rank kernel sorts
   // the items by parse class, the plan writes the descriptors at their sorted slots, and the matchers
   // run over class ranges they read from the workspace; the manager's level is not used.
+  // a.prefix_sizes: one prefix per item, read on the device by the plan -- an item with one gets a
+  // dictionary frame's descriptors, the others plain ones, in a batch shaped like a dictionary
+  // handle's (prefix_shape); ws.dtab and ws.dd_* stay null as for a view, so every first block
+  // hashes its own prefix.
   Status run_device(const ZhPlanArrays &a, bool levels, size_t max_chunk, size_t count, size_t *d_out_sizes, int *d_statuses, void *temp,
                     size_t temp_size, hipStream_t stream) {
     // one manager serialises calls (the dictionary's use events: set_dictionary waits on them)
@@ -692,7 +700,10 @@ class ZstdBatchManager::Impl {
     const DevDict *dd = active();
     // a dictionary frame's block split depends on its level (zh_split_dict): no one bpi per mixed-level batch
     if (levels && (!a.levels || dd)) return Status::ERROR_INVALID_PARAMETER;
-    BatchShape const shape = levels ? BatchShape::mixed_levels(count, max_chunk) : device_shape(count, max_chunk);
+    // one prefix source per item: not a batch dictionary too, and one level per batch
+    bool const prefix = a.prefix_ptrs || a.prefix_sizes;
+    if (prefix && (!a.prefix_ptrs || !a.prefix_sizes || dd || levels)) return Status::ERROR_INVALID_PARAMETER;
+    BatchShape const shape = levels ? BatchShape::mixed_levels(count, max_chunk) : prefix ? prefix_shape(count, max_chunk) : device_shape(count, max_chunk);
     if (levels && (count > ZH_RANK_MAX_ITEMS || shape.nblocks > 0xFFFFFFFFull)) return Status::ERROR_INVALID_PARAMETER;
     WsLayout const L(shape);
     if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
@@ -1186,7 +1197,7 @@ size_t ZstdBatchManager::get_batch_device_temp_size_for(size_t count, size_t max
 Status ZstdBatchManager::compress_batch_device(const void *const *d_in_ptrs, const size_t *d_in_sizes, size_t max_chunk, size_t count,
                                                void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp, size_t temp_size,
                                                hipStream_t stream) {
-  return pimpl_->run_device({d_in_ptrs, d_in_sizes, d_out_ptrs, nullptr}, false, max_chunk, count, d_out_sizes, d_statuses, temp, temp_size, stream);
+  return pimpl_->run_device({d_in_ptrs, d_in_sizes, d_out_ptrs, nullptr, nullptr, nullptr}, false, max_chunk, count, d_out_sizes, d_statuses, temp, temp_size, stream);
 }
 
 size_t ZstdBatchManager::get_batch_device_levels_temp_size(size_t count, size_t max_chunk) {
@@ -1195,7 +1206,18 @@ size_t ZstdBatchManager::get_batch_device_levels_temp_size(size_t count, size_t 
 Status ZstdBatchManager::compress_batch_device_levels(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int *d_levels, size_t max_chunk,
                                                       size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp,
                                                       size_t temp_size, hipStream_t stream) {
-  return pimpl_->run_device({d_in_ptrs, d_in_sizes, d_out_ptrs, d_levels}, true, max_chunk, count, d_out_sizes, d_statuses, temp, temp_size, stream);
+  return pimpl_->run_device({d_in_ptrs, d_in_sizes, d_out_ptrs, d_levels, nullptr, nullptr}, true, max_chunk, count, d_out_sizes, d_statuses, temp, temp_size, stream);
+}
+
+size_t ZstdBatchManager::get_batch_device_prefix_temp_size(size_t count, size_t max_chunk) const {
+  return WsLayout(pimpl_->prefix_shape(count, max_chunk)).total;
+}
+Status ZstdBatchManager::compress_batch_device_prefix(const void *const *d_in_ptrs, const size_t *d_in_sizes, const void *const *d_prefix_ptrs,
+                                                      const size_t *d_prefix_sizes, size_t max_chunk, size_t count, void *const *d_out_ptrs,
+                                                      size_t *d_out_sizes, int *d_statuses, void *temp, size_t temp_size, hipStream_t stream) {
+  if (count && (!d_prefix_ptrs || !d_prefix_sizes)) return Status::ERROR_INVALID_PARAMETER;
+  return pimpl_->run_device({d_in_ptrs, d_in_sizes, d_out_ptrs, nullptr, d_prefix_ptrs, d_prefix_sizes}, false, max_chunk, count, d_out_sizes,
+                            d_statuses, temp, temp_size, stream);
 }
 
 size_t ZstdBatchManager::get_batch_device_decompress_temp_size(size_t count, size_t max_out) {
@@ -1205,17 +1227,29 @@ size_t ZstdBatchManager::get_batch_device_decompress_temp_size(size_t count, siz
 Status ZstdBatchManager::decompress_batch_device(const void *const *d_in_ptrs, const size_t *d_in_sizes, const size_t *d_out_caps, size_t max_out,
                                                  size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp,
                                                  size_t temp_size, hipStream_t stream) {
+  return decompress_batch_device_prefix(d_in_ptrs, d_in_sizes, nullptr, nullptr, d_out_caps, max_out, count, d_out_ptrs, d_out_sizes, d_statuses, temp,
+                                        temp_size, stream);
+}
+// (d_prefix_sizes null: the plain entry, with the manager's dictionary if one is set)
+Status ZstdBatchManager::decompress_batch_device_prefix(const void *const *d_in_ptrs, const size_t *d_in_sizes, const void *const *d_prefix_ptrs,
+                                                        const size_t *d_prefix_sizes, const size_t *d_out_caps, size_t max_out, size_t count,
+                                                        void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp,
+                                                        size_t temp_size, hipStream_t stream) {
   // one manager serialises calls (the dictionary's use events: set_dictionary waits on them)
   std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
   Status s = ensure_kernels();
   if (s != Status::SUCCESS) return s;
   if (!count) return Status::SUCCESS;
   if (!d_in_ptrs || !d_in_sizes || !d_out_ptrs || !d_out_sizes || max_out == 0) return Status::ERROR_INVALID_PARAMETER;
+  bool const prefix = d_prefix_ptrs || d_prefix_sizes;
+  if (prefix && (!d_prefix_ptrs || !d_prefix_sizes || pimpl_->mgr_dict.n)) return Status::ERROR_INVALID_PARAMETER;
   DecLayout L = DecLayout::make(count, max_out);
   if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
   u8 *base = aligned_base(temp);
   ZhDecArgs a = L.args(base);
   pimpl_->mgr_dict.fill(a);
+  a.pre_ptrs = d_prefix_ptrs;
+  a.pre_sizes = d_prefix_sizes;
   a.in_ptrs = d_in_ptrs;
   a.in_sizes = d_in_sizes;
   a.out_ptrs = d_out_ptrs;
@@ -1981,6 +2015,24 @@ Status NvcompV5BatchManager::get_decompress_sizes_async(const void *const *d_com
                                                   true);
 }
 
+Status NvcompV5BatchManager::compress_prefix_async(const void *const *d_uncompressed_ptrs, const size_t *d_uncompressed_sizes,
+                                                   const void *const *d_prefix_ptrs, const size_t *d_prefix_sizes, size_t max_chunk,
+                                                   size_t num_chunks, void *const *d_compressed_ptrs, size_t *d_compressed_sizes, int *d_statuses,
+                                                   void *d_temp_storage, size_t temp_storage_bytes, hipStream_t stream) {
+  return pimpl_->mgr.compress_batch_device_prefix(d_uncompressed_ptrs, d_uncompressed_sizes, d_prefix_ptrs, d_prefix_sizes, max_chunk, num_chunks,
+                                                  d_compressed_ptrs, d_compressed_sizes, d_statuses, d_temp_storage, temp_storage_bytes, stream);
+}
+Status NvcompV5BatchManager::decompress_prefix_async(const void *const *d_compressed_ptrs, const size_t *d_compressed_sizes,
+                                                     const void *const *d_prefix_ptrs, const size_t *d_prefix_sizes,
+                                                     const size_t *d_uncompressed_caps, size_t max_chunk, size_t num_chunks,
+                                                     void *const *d_uncompressed_ptrs, size_t *d_actual_sizes, int *d_statuses,
+                                                     void *d_temp_storage, size_t temp_storage_bytes, hipStream_t stream) {
+  if (num_chunks && (!d_prefix_ptrs || !d_prefix_sizes)) return Status::ERROR_INVALID_PARAMETER;
+  return pimpl_->mgr.decompress_batch_device_prefix(d_compressed_ptrs, d_compressed_sizes, d_prefix_ptrs, d_prefix_sizes, d_uncompressed_caps,
+                                                    max_chunk, num_chunks, d_uncompressed_ptrs, d_actual_sizes, d_statuses, d_temp_storage,
+                                                    temp_storage_bytes, stream);
+}
+
 Status get_metadata_async(const void *d, size_t n, NvcompV5Metadata *m, hipStream_t) {
   if (!m) return Status::ERROR_INVALID_PARAMETER;
   size_t s;
@@ -2647,6 +2699,25 @@ int nvcomp_zstd_batched_compress_levels_async_v5(nvcomp_zstd_batch_manager_t *m,
   return c_err(
       m->mgr->batch_manager().compress_batch_device_levels(d_in, d_in_sizes, d_levels, max_chunk, n, d_out, d_out_sizes, d_statuses, t, tb, s));
 }
+size_t nvcomp_zstd_batch_get_batched_prefix_temp_size_v5(nvcomp_zstd_batch_manager_t *m, size_t n, size_t max_chunk) {
+  return (m && m->mgr) ? m->mgr->batch_manager().get_batch_device_prefix_temp_size(n, max_chunk) : 0;
+}
+int nvcomp_zstd_batched_compress_prefix_async_v5(nvcomp_zstd_batch_manager_t *m, const void *const *d_in, const size_t *d_in_sizes,
+                                                 const void *const *d_pre, const size_t *d_pre_sizes, size_t max_chunk, size_t n,
+                                                 void *const *d_out, size_t *d_out_sizes, int *d_statuses, void *t, size_t tb, hipStream_t s) {
+  if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
+  return c_err(m->mgr->batch_manager().compress_batch_device_prefix(d_in, d_in_sizes, d_pre, d_pre_sizes, max_chunk, n, d_out, d_out_sizes,
+                                                                     d_statuses, t, tb, s));
+}
+int nvcomp_zstd_batched_decompress_prefix_async_v5(nvcomp_zstd_batch_manager_t *m, const void *const *d_in, const size_t *d_in_sizes,
+                                                   const void *const *d_pre, const size_t *d_pre_sizes, const size_t *d_out_caps, size_t max_out,
+                                                   size_t n, void *const *d_out, size_t *d_out_sizes, int *d_statuses, void *t, size_t tb,
+                                                   hipStream_t s) {
+  if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
+  if (n && (!d_pre || !d_pre_sizes)) return c_err(Status::ERROR_INVALID_PARAMETER);
+  return c_err(m->mgr->batch_manager().decompress_batch_device_prefix(d_in, d_in_sizes, d_pre, d_pre_sizes, d_out_caps, max_out, n, d_out,
+                                                                       d_out_sizes, d_statuses, t, tb, s));
+}
 size_t nvcomp_zstd_batch_get_decompress_temp_size_v5(nvcomp_zstd_batch_manager_t *m, const size_t *sizes, size_t n) {
   return (m && m->mgr) ? m->mgr->get_decompress_temp_size(sizes, n) : 0;
 }
@@ -2786,6 +2857,12 @@ void cuda_zstd_hip_ldm_profile(int on, double *ms) {
   double const t = zh::ldm_profile(on != 0);
   if (ms) *ms = t;
 }
+// HIP events around zh_window_update_kernel: on = 1 starts recording; on = 0 stops and stores the
+// summed milliseconds of the launches since then
+void cuda_zstd_hip_window_profile(int on, double *ms) {
+  double const t = zh::window_profile(on != 0);
+  if (ms) *ms = t;
+}
 void cuda_zstd_hip_profile_enable(int on) { zh::profile_enable(on != 0); }
 int cuda_zstd_hip_profile_collect(double *ms3) { return zh::profile_collect(ms3); }
 
@@ -2822,6 +2899,102 @@ int cuda_zstd_stream_decompress_chunk(cuda_zstd_stream_t *s, const void *src, si
   return c_err(st);
 }
 int cuda_zstd_stream_reset(cuda_zstd_stream_t *s) { return s && s->m ? c_err(s->m->reset()) : 2; }
+
+// ---- many streams in one call (zh_stream.hip) -------------------------------------------------
+// One device allocation made at create: the compress and the decode workspace, the window pairs of
+// both directions (as ZstdStreamingManager keeps chist and dhist), per direction the current-half
+// words and the prefix pointer / size arrays the prefix entries are called with, and a status array
+// for callers that pass none.  A call is the prefix entry plus one window launch.
+struct cuda_zstd_stream_batch_t {
+  struct Dir {
+    u8 *windows = nullptr;
+    u32 *which = nullptr;
+    const void **pre_ptrs = nullptr;
+    size_t *pre_sizes = nullptr;
+  };
+  ZstdBatchManager mgr;
+  size_t n = 0, max_chunk = 0, cws_bytes = 0, dws_bytes = 0;
+  u8 *mem = nullptr, *cws = nullptr, *dws = nullptr;
+  int *statuses = nullptr;
+  Dir c, d;
+  explicit cuda_zstd_stream_batch_t(int level) : mgr(CompressionConfig::from_level(level)) {}
+  ~cuda_zstd_stream_batch_t() { if (mem) (void)hipFree(mem); }
+  bool allocate() {
+    cws_bytes = mgr.get_batch_device_prefix_temp_size(n, max_chunk);
+    dws_bytes = ZstdBatchManager::get_batch_device_decompress_temp_size(n, max_chunk);
+    size_t o = 0;
+    auto take = [&o](size_t bytes) { size_t const at = o; o = align256(o + bytes); return at; };
+    size_t const o_cws = take(cws_bytes), o_dws = take(dws_bytes), o_st = take(n * 4);
+    size_t o_win[2], o_which[2], o_pp[2], o_ps[2];
+    for (int k = 0; k < 2; k++) {
+      o_win[k] = take(n * 2 * (size_t)ZH_STREAM_WINDOW);
+      o_which[k] = take(n * 4);
+      o_pp[k] = take(n * 8);
+      o_ps[k] = take(n * 8);
+    }
+    if (hipMalloc(&mem, o) != hipSuccess) { mem = nullptr; return false; }
+    cws = mem + o_cws;
+    dws = mem + o_dws;
+    statuses = (int *)(mem + o_st);
+    Dir *dirs[2] = {&c, &d};
+    for (int k = 0; k < 2; k++) {
+      dirs[k]->windows = mem + o_win[k];
+      dirs[k]->which = (u32 *)(mem + o_which[k]);
+      dirs[k]->pre_ptrs = (const void **)(mem + o_pp[k]);
+      dirs[k]->pre_sizes = (size_t *)(mem + o_ps[k]);
+    }
+    return true;
+  }
+  Status reset(hipStream_t stream) {
+    for (Dir *x : {&c, &d})
+      if (zh::window_reset_launch(x->windows, x->which, x->pre_ptrs, x->pre_sizes, (u32)n, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+    return Status::SUCCESS;
+  }
+  Status advance(Dir &x, const void *const *chunk_ptrs, const size_t *chunk_sizes, const int *st, hipStream_t stream) {
+    return zh::window_update_launch(x.windows, x.which, x.pre_ptrs, x.pre_sizes, chunk_ptrs, chunk_sizes, (const u32 *)st, (u32)n, stream) == hipSuccess
+               ? Status::SUCCESS
+               : Status::ERROR_CUDA_ERROR;
+  }
+};
+cuda_zstd_stream_batch_t *cuda_zstd_stream_batch_create(int level, size_t num_streams, size_t max_chunk_bytes) {
+  if (!is_valid_compression_level(level) || !num_streams || !max_chunk_bytes || num_streams > 0xFFFFFFFFull) return nullptr;
+  try {
+    std::unique_ptr<cuda_zstd_stream_batch_t> sb(new cuda_zstd_stream_batch_t(level));
+    sb->n = num_streams;
+    sb->max_chunk = max_chunk_bytes;
+    if (ensure_kernels() != Status::SUCCESS || !sb->allocate()) return nullptr;
+    if (sb->reset(nullptr) != Status::SUCCESS || hipStreamSynchronize(nullptr) != hipSuccess) return nullptr;
+    return sb.release();
+  } catch (...) {
+    return nullptr;
+  }
+}
+void cuda_zstd_stream_batch_destroy(cuda_zstd_stream_batch_t *sb) { delete sb; }
+size_t cuda_zstd_stream_batch_max_compressed_chunk_size(cuda_zstd_stream_batch_t *sb) {
+  return sb ? sb->mgr.get_max_compressed_size(sb->max_chunk) : 0;
+}
+int cuda_zstd_stream_batch_compress_async(cuda_zstd_stream_batch_t *sb, const void *const *d_in_ptrs, const size_t *d_in_sizes,
+                                          void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, hipStream_t stream) {
+  if (!sb || !d_in_ptrs || !d_in_sizes || !d_out_ptrs || !d_out_sizes) return c_err(Status::ERROR_INVALID_PARAMETER);
+  int *const st = d_statuses ? d_statuses : sb->statuses;
+  Status s = sb->mgr.compress_batch_device_prefix(d_in_ptrs, d_in_sizes, sb->c.pre_ptrs, sb->c.pre_sizes, sb->max_chunk, sb->n, d_out_ptrs,
+                                                  d_out_sizes, st, sb->cws, sb->cws_bytes, stream);
+  if (s == Status::SUCCESS) s = sb->advance(sb->c, d_in_ptrs, d_in_sizes, st, stream);
+  return c_err(s);
+}
+int cuda_zstd_stream_batch_decompress_async(cuda_zstd_stream_batch_t *sb, const void *const *d_in_ptrs, const size_t *d_in_sizes,
+                                            const size_t *d_out_caps, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses,
+                                            hipStream_t stream) {
+  if (!sb || !d_in_ptrs || !d_in_sizes || !d_out_ptrs || !d_out_sizes) return c_err(Status::ERROR_INVALID_PARAMETER);
+  int *const st = d_statuses ? d_statuses : sb->statuses;
+  Status s = sb->mgr.decompress_batch_device_prefix(d_in_ptrs, d_in_sizes, sb->d.pre_ptrs, sb->d.pre_sizes, d_out_caps, sb->max_chunk, sb->n,
+                                                    d_out_ptrs, d_out_sizes, st, sb->dws, sb->dws_bytes, stream);
+  if (s == Status::SUCCESS) s = sb->advance(sb->d, d_out_ptrs, d_out_sizes, st, stream);
+  return c_err(s);
+}
+int cuda_zstd_stream_batch_reset(cuda_zstd_stream_batch_t *sb, hipStream_t stream) {
+  return sb ? c_err(sb->reset(stream)) : c_err(Status::ERROR_INVALID_PARAMETER);
+}
 
 int cuda_zstd_write_metadata_frame(void *dst, size_t capacity, int level, size_t *written, hipStream_t stream) {
   return c_err(write_metadata_frame(dst, capacity, level, written, stream));

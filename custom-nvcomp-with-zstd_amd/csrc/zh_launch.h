@@ -25,6 +25,10 @@ struct ZhDecArgs {
   u64 dict_n;      // its size
   u32 dict_off;    // content offset (formatted dictionary: after tables + repcodes; raw: 0)
   u32 dict_id;     // Dictionary_ID (formatted), 0 for raw content
+  // one prefix per item (device arrays, or null: none): raw content in front of item i's frames,
+  // all of it addressable; not together with dict.  A zero size or a null pointer: no prefix
+  const void *const *pre_ptrs;
+  const size_t *pre_sizes;
 };
 #define ZH_DEC_HANDOFF_BYTES 5376u  // sizeof(DecHandoff), zh_decode.hip
 
@@ -53,6 +57,9 @@ struct ZhPlanArrays {
   const size_t *in_sizes;
   void *const *out_ptrs;
   const int *levels;  // one level per item (a mixed-level batch), or null
+  // one prefix per item (ZhPlanItem::pre / pre_n), or both null; prefix_sizes[i] == 0: item i has none
+  const void *const *prefix_ptrs;
+  const size_t *prefix_sizes;
 };
 
 namespace zh {
@@ -78,11 +85,20 @@ int profile_collect(double *totals);
 // Device plan (zh_plan.hip): descs, items and the invalid items' size and status from the device
 // arrays in `a`; every item takes nblocks / nitems block slots.  a.levels (a mixed-level batch):
 // the items are ranked by parse class (one workgroup, up to ZH_RANK_MAX_ITEMS items) and their
-// descriptors written at the sorted slots with one level byte per slot.
+// descriptors written at the sorted slots with one level byte per slot.  a.prefix_sizes: item i is
+// planned behind its own prefix (a.prefix_ptrs[i], a.prefix_sizes[i] bytes; 0: none).
 #define ZH_RANK_MAX_ITEMS (1u << 20)
 hipError_t launch_plan(const ZhBatch &b, const ZhPlanArrays &a, hipStream_t stream);
 // Long-distance matching (zh_ldm.hip): index + per-cell split of one frame, three descriptor slots per cell
 hipError_t ldm_launch(const u8 *src, u64 size, u32 ncells, u32 table_log, u32 max_dist, u32 flags, u64 *table, u64 *skey, u32 *sslot,
                       u32 *scount, ZhBlockDesc *descs, u8 *staging, u32 *blk_size, ZhLdmRecord *rec, hipStream_t stream);
 double ldm_profile(bool on);
+// Many streams (zh_stream.hip): stream i's window pair is windows + i * 2 * ZH_STREAM_WINDOW, which[i]
+// its current half, pre_ptrs[i] / pre_sizes[i] the current window as the batch entries' prefix.
+// window_update_launch: one workgroup per stream appends chunk i (chunk_sizes[i] bytes; statuses[i]
+// non-zero or no bytes: the window stays) and writes the stream's next prefix pointer and size.
+hipError_t window_update_launch(u8 *windows, u32 *which, const void **pre_ptrs, size_t *pre_sizes, const void *const *chunk_ptrs,
+                                const size_t *chunk_sizes, const u32 *statuses, u32 nstreams, hipStream_t stream);
+double window_profile(bool on);
+hipError_t window_reset_launch(u8 *windows, u32 *which, const void **pre_ptrs, size_t *pre_sizes, u32 nstreams, hipStream_t stream);
 }  // namespace zh

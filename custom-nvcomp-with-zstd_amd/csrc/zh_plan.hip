@@ -4,6 +4,8 @@
 //                  arrays with the rule of zh_block_plan.h, for the stream-ordered batched
 //                  entry points (no host round trip, unlike the reference's compress_async,
 //                  src/cuda_zstd_nvcomp.cpp:319-437); zh_plan_levels_kernel: one level per item.
+//                  With ZhPlanArrays::prefix_ptrs / prefix_sizes every item brings its own prefix
+//                  (the bytes in front of it, a raw-content dictionary): ZhPlanItem::pre / pre_n.
 // zh_gather_kernel: concatenates the staged blocks of multi-block frames (the
 //                  reference assembles them on the host with blocking copies,
 //                  src/cuda_zstd_manager.cu:2765-3027).
@@ -34,7 +36,8 @@ void entropy_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32
 // slots per item, and writes block slot b with the rule of zh_block_plan.h.  valid false: an
 // inactive slot and an invalid item.
 __device__ inline void zh_plan_block(const ZhBatch &B, const ZhPlanArrays &a, u32 i, u32 k, u32 b, int level, bool valid) {
-  ZhPlanItem const it{(const u8 *)a.in_ptrs[i], a.in_sizes[i], i, level, (u8 *)a.out_ptrs[i]};
+  ZhPlanItem it{(const u8 *)a.in_ptrs[i], a.in_sizes[i], i, level, (u8 *)a.out_ptrs[i]};
+  if (a.prefix_sizes) { it.pre = (const u8 *)a.prefix_ptrs[i]; it.pre_n = a.prefix_sizes[i]; }  // the item's own prefix
   ZhBlockDesc d = zh_block_desc(B.plan, it, k, b);
   if (!valid) d.n = 0;
   B.descs[b] = d;

@@ -87,6 +87,15 @@ def lib() -> ctypes.CDLL:
             "nvcomp_zstd_batched_compress_async_v5": (i, [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
             "nvcomp_zstd_batched_compress_levels_get_temp_size_v5": (sz, [sz, sz]),
             "nvcomp_zstd_batched_compress_levels_async_v5": (i, [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
+            "nvcomp_zstd_batch_get_batched_prefix_temp_size_v5": (sz, [vp, sz, sz]),
+            "nvcomp_zstd_batched_compress_prefix_async_v5": (i, [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
+            "nvcomp_zstd_batched_decompress_prefix_async_v5": (i, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
+            "cuda_zstd_stream_batch_create": (vp, [i, sz, sz]),
+            "cuda_zstd_stream_batch_destroy": (None, [vp]),
+            "cuda_zstd_stream_batch_max_compressed_chunk_size": (sz, [vp]),
+            "cuda_zstd_stream_batch_compress_async": (i, [vp, vp, vp, vp, vp, vp, vp]),
+            "cuda_zstd_stream_batch_decompress_async": (i, [vp, vp, vp, vp, vp, vp, vp, vp]),
+            "cuda_zstd_stream_batch_reset": (i, [vp, vp]),
             "cuda_zstd_get_batch_decompress_workspace_size": (sz, [vp, psz, sz]),
             "cuda_zstd_decompress_batch": (i, [vp, pvp, psz, sz, pvp, psz, pi, vp, sz, vp]),
             "nvcomp_zstd_batch_get_decompress_temp_size_v5": (sz, [vp, psz, sz]),
@@ -126,6 +135,7 @@ def lib() -> ctypes.CDLL:
             "nvcomp_zstd_batch_set_dict_entropy_v5": (i, [vp, i]),
             "cuda_zstd_hip_ldm_plan": (ctypes.c_longlong, [vp, vp, sz, vp, sz, vp, sz, vp]),
             "cuda_zstd_hip_ldm_profile": (None, [i, ctypes.POINTER(ctypes.c_double)]),
+            "cuda_zstd_hip_window_profile": (None, [i, ctypes.POINTER(ctypes.c_double)]),
             "cuda_zstd_adaptive_get_temp_size": (sz, [sz]),
             "cuda_zstd_adaptive_analyze_batch_async": (i, [vp, vp, sz, sz, i, vp, vp, vp, sz, vp]),
             "cuda_zstd_adaptive_select_level": (i, [vp, sz, sz, i, vp, vp]),
@@ -595,6 +605,20 @@ class BatchedDecompressor:
         if rc:
             raise ZstdError(rc, "nvcomp_zstd_batched_decompress_async_v5")
 
+    def decompress_prefix_async(self, d_in_ptrs, d_in_sizes, d_prefix_ptrs, d_prefix_sizes, d_out_caps, max_out, d_out_ptrs, d_out_sizes,
+                                d_status, temp, stream=None):
+        """decompress_async with one prefix per buffer (nvcomp_zstd_batched_decompress_prefix_async_v5):
+        d_prefix_ptrs / d_prefix_sizes are int64 device tensors, size 0 = no prefix; the whole prefix
+        is addressable in front of the frame.  Same workspace as decompress_async."""
+        n = d_in_ptrs.numel()
+        rc = lib().nvcomp_zstd_batched_decompress_prefix_async_v5(
+            self._h, d_in_ptrs.data_ptr(), d_in_sizes.data_ptr(), d_prefix_ptrs.data_ptr() if d_prefix_ptrs is not None else None,
+            d_prefix_sizes.data_ptr() if d_prefix_sizes is not None else None, d_out_caps.data_ptr() if d_out_caps is not None else None,
+            max_out, n, d_out_ptrs.data_ptr(), d_out_sizes.data_ptr(), d_status.data_ptr() if d_status is not None else None,
+            temp.data_ptr(), temp.numel(), _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batched_decompress_prefix_async_v5")
+
     def get_sizes_async(self, d_in_ptrs, d_in_sizes, d_out_sizes, d_status, stream=None):
         """The decompressed size of every buffer, on the device
         (nvcomp_zstd_batched_get_decompress_size_async_v5): int64 device tensors of pointers and
@@ -675,6 +699,24 @@ class BatchedCompressor:
             temp.numel(), _stream_ptr(stream))
         if rc:
             raise ZstdError(rc, "nvcomp_zstd_batched_compress_levels_async_v5")
+
+    def temp_size_prefix(self, num_chunks: int, max_chunk: int) -> int:
+        """Workspace of compress_prefix_async (nvcomp_zstd_batch_get_batched_prefix_temp_size_v5)."""
+        return lib().nvcomp_zstd_batch_get_batched_prefix_temp_size_v5(self._h, num_chunks, max_chunk)
+
+    def compress_prefix_async(self, d_in_ptrs, d_in_sizes, d_prefix_ptrs, d_prefix_sizes, max_chunk, d_out_ptrs, d_out_sizes, d_status, temp,
+                              stream=None):
+        """compress_async with one prefix per chunk (nvcomp_zstd_batched_compress_prefix_async_v5):
+        d_prefix_ptrs / d_prefix_sizes are int64 device tensors; chunk i is compressed behind the
+        bytes at d_prefix_ptrs[i] as a raw-content dictionary (size 0: a plain frame).  No handle
+        dictionary, no per-chunk levels."""
+        n = d_in_ptrs.numel()
+        rc = lib().nvcomp_zstd_batched_compress_prefix_async_v5(
+            self._h, d_in_ptrs.data_ptr(), d_in_sizes.data_ptr(), d_prefix_ptrs.data_ptr() if d_prefix_ptrs is not None else None,
+            d_prefix_sizes.data_ptr() if d_prefix_sizes is not None else None, max_chunk, n, d_out_ptrs.data_ptr(), d_out_sizes.data_ptr(),
+            d_status.data_ptr() if d_status is not None else None, temp.data_ptr(), temp.numel(), _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batched_compress_prefix_async_v5")
 
     @staticmethod
     def seekable_max_size(num_frames: int, max_compressed_chunk: int, checksums: bool = False) -> int:
@@ -760,6 +802,88 @@ class StreamingManager:
         rc = lib().cuda_zstd_stream_reset(self._h)
         if rc:
             raise ZstdError(rc, "cuda_zstd_stream_reset")
+
+
+class StreamBatch:
+    """Many streams in one call (cuda_zstd_stream_batch_*): num_streams streams whose 64 KiB
+    windows stay on the device.  compress_chunks / decompress_chunks take one chunk per stream
+    (uint8 device tensors; None or an empty tensor: the stream is idle this round) and return one
+    tensor per stream (None for an idle or failed stream) plus the statuses.  Frame i is what a
+    StreamingManager of stream i writes with history."""
+
+    def __init__(self, level: int, num_streams: int, max_chunk: int):
+        self._h = lib().cuda_zstd_stream_batch_create(level, num_streams, max_chunk)
+        if not self._h:
+            raise ZstdError(INVALID, "cuda_zstd_stream_batch_create")
+        self.num_streams, self.max_chunk = num_streams, max_chunk
+        self.max_out = lib().cuda_zstd_stream_batch_max_compressed_chunk_size(self._h)
+
+    def close(self):
+        if self._h:
+            lib().cuda_zstd_stream_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def compress_async(self, d_in_ptrs, d_in_sizes, d_out_ptrs, d_out_sizes, d_status, stream=None):
+        """The raw call over int64 device tensors (cuda_zstd_stream_batch_compress_async)."""
+        rc = lib().cuda_zstd_stream_batch_compress_async(self._h, d_in_ptrs.data_ptr(), d_in_sizes.data_ptr(), d_out_ptrs.data_ptr(),
+                                                         d_out_sizes.data_ptr(), d_status.data_ptr() if d_status is not None else None,
+                                                         _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_stream_batch_compress_async")
+
+    def decompress_async(self, d_in_ptrs, d_in_sizes, d_out_caps, d_out_ptrs, d_out_sizes, d_status, stream=None):
+        rc = lib().cuda_zstd_stream_batch_decompress_async(self._h, d_in_ptrs.data_ptr(), d_in_sizes.data_ptr(),
+                                                           d_out_caps.data_ptr() if d_out_caps is not None else None, d_out_ptrs.data_ptr(),
+                                                           d_out_sizes.data_ptr(), d_status.data_ptr() if d_status is not None else None,
+                                                           _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_stream_batch_decompress_async")
+
+    def _round(self, items, slot, decode, stream):
+        torch = _torch()
+        n = self.num_streams
+        if len(items) != n:
+            raise ZstdError(INVALID, "StreamBatch: one chunk (or None) per stream")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        ins = [None if c is None else c.contiguous().view(torch.uint8) for c in items]
+        sizes = [0 if t is None else t.numel() for t in ins]
+        with torch.cuda.stream(s):
+            out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
+            table = torch.tensor([[0 if t is None or not t.numel() else t.data_ptr() for t in ins], sizes,
+                                  [out.data_ptr() + k * slot for k in range(n)]], dtype=torch.int64)
+            d_table = table.pin_memory().to("cuda", non_blocking=True)
+            if s != torch.cuda.current_stream():
+                for t in ins:
+                    if t is not None:
+                        t.record_stream(s)
+            d_sizes = torch.zeros(n, dtype=torch.int64, device="cuda")
+            d_status = torch.zeros(n, dtype=torch.int32, device="cuda")
+            if decode:
+                self.decompress_async(d_table[0], d_table[1], None, d_table[2], d_sizes, d_status, s)
+            else:
+                self.compress_async(d_table[0], d_table[1], d_table[2], d_sizes, d_status, s)
+            got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
+        res = [out[k * slot : k * slot + got_sizes[k]] if got_status[k] == OK else None for k in range(n)]
+        return res, got_status
+
+    def compress_chunks(self, chunks: Sequence, stream=None):
+        """-> (frames, statuses): frame i of stream i's chunk behind its window; every window advances."""
+        return self._round(chunks, ((self.max_out + 255) // 256) * 256, False, stream)
+
+    def decompress_chunks(self, frames: Sequence, stream=None):
+        """-> (chunks, statuses): the frames of one round, decoded behind the decoded windows."""
+        return self._round(frames, ((self.max_chunk + 255) // 256) * 256, True, stream)
+
+    def reset(self, stream=None):
+        rc = lib().cuda_zstd_stream_batch_reset(self._h, _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_stream_batch_reset")
 
 
 # HybridEngine (reference PyHybridEngine, python/src/binding.cpp:331-545, over
@@ -1111,6 +1235,95 @@ def compress_batch_levels(chunks: Sequence, levels, checksum: bool = False, stre
         if got_status[k] != OK:
             raise ZstdError(got_status[k], f"compress_batch_levels item {k}")
         res.append(out[k * slot : k * slot + got_sizes[k]])
+    return res
+
+
+def _prefix_table(items, prefixes, torch):
+    """Device tensors of the items and their prefixes (hosts are uploaded; None: no prefix)."""
+    ins = [(_to_device(c) if _is_host(c) else c).contiguous().view(torch.uint8) for c in items]
+    if len(prefixes) != len(ins):
+        raise ZstdError(INVALID, "one prefix (or None) per item")
+    pre = [None if p is None else (_to_device(p) if _is_host(p) else p).contiguous().view(torch.uint8) for p in prefixes]
+    return ins, pre
+
+
+def compress_batch_prefix(chunks: Sequence, prefixes: Sequence, level: int = 3, checksum: bool = False, stream=None) -> List:
+    """Compress chunk i behind prefixes[i] (the bytes that precede it: a raw-content dictionary;
+    None = no prefix) in one stream-ordered call (nvcomp_zstd_batched_compress_prefix_async_v5) ->
+    the frames in input order.  Hosts (bytes, numpy) or CUDA tensors in; device tensors in ->
+    device tensors out, hosts in -> bytes out.  Waits once, for the frames' sizes."""
+    torch = _torch()
+    n = len(chunks)
+    if n == 0:
+        return []
+    host = _is_host(chunks[0])
+    s = stream if stream is not None else torch.cuda.current_stream()
+    ins, pre = _prefix_table(chunks, prefixes, torch)
+    sizes = [t.numel() for t in ins]
+    max_chunk = max(max(sizes), 1)
+    bc = BatchedCompressor(level, checksum=checksum)
+    slot = ((bc.max_out(max_chunk) + 255) // 256) * 256
+    with torch.cuda.stream(s):
+        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
+        table = torch.tensor([[t.data_ptr() if t.numel() else 0 for t in ins], sizes, [out.data_ptr() + k * slot for k in range(n)],
+                              [0 if p is None or not p.numel() else p.data_ptr() for p in pre],
+                              [0 if p is None else p.numel() for p in pre]], dtype=torch.int64)
+        d_table = table.pin_memory().to("cuda", non_blocking=True)
+        if s != torch.cuda.current_stream():
+            for t in ins + [p for p in pre if p is not None]:
+                t.record_stream(s)
+        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
+        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
+        temp = torch.empty(bc.temp_size_prefix(n, max_chunk), dtype=torch.uint8, device="cuda")
+        bc.compress_prefix_async(d_table[0], d_table[1], d_table[3], d_table[4], max_chunk, d_table[2], d_sizes, d_status, temp, s)
+        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
+    bc.close()
+    res = []
+    for k in range(n):
+        if got_status[k] != OK:
+            raise ZstdError(got_status[k], f"compress_batch_prefix item {k}")
+        f = out[k * slot : k * slot + got_sizes[k]]
+        res.append(_host_bytes(f) if host else f)
+    return res
+
+
+def decompress_batch_prefix(frames: Sequence, prefixes: Sequence, capacities=None, stream=None) -> List:
+    """Decode frame i behind prefixes[i] (None = no prefix) in one stream-ordered call
+    (nvcomp_zstd_batched_decompress_prefix_async_v5).  capacities: one output capacity per frame
+    (default: the frame header's content size).  Hosts in -> bytes out, CUDA tensors in -> tensors."""
+    torch = _torch()
+    n = len(frames)
+    if n == 0:
+        return []
+    host = _is_host(frames[0])
+    s = stream if stream is not None else torch.cuda.current_stream()
+    ins, pre = _prefix_table(frames, prefixes, torch)
+    caps = [int(c) for c in capacities] if capacities is not None else [_frame_size(t) for t in ins]
+    max_out = max(max(caps), 1)
+    slot = ((max_out + 255) // 256) * 256
+    bd = BatchedDecompressor()
+    with torch.cuda.stream(s):
+        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
+        table = torch.tensor([[t.data_ptr() if t.numel() else 0 for t in ins], [t.numel() for t in ins],
+                              [out.data_ptr() + k * slot for k in range(n)], caps,
+                              [0 if p is None or not p.numel() else p.data_ptr() for p in pre],
+                              [0 if p is None else p.numel() for p in pre]], dtype=torch.int64)
+        d_table = table.pin_memory().to("cuda", non_blocking=True)
+        if s != torch.cuda.current_stream():
+            for t in ins + [p for p in pre if p is not None]:
+                t.record_stream(s)
+        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
+        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
+        temp = torch.empty(bd.temp_size(n, max_out), dtype=torch.uint8, device="cuda")
+        bd.decompress_prefix_async(d_table[0], d_table[1], d_table[4], d_table[5], d_table[3], max_out, d_table[2], d_sizes, d_status, temp, s)
+        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
+    bd.close()
+    res = []
+    for k in range(n):
+        if got_status[k] != OK:
+            raise ZstdError(got_status[k], f"decompress_batch_prefix item {k}")
+        f = out[k * slot : k * slot + got_sizes[k]]
+        res.append(_host_bytes(f) if host else f)
     return res
 
 

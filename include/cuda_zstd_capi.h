@@ -165,6 +165,39 @@ int nvcomp_zstd_batched_compress_levels_async_v5(nvcomp_zstd_batch_manager_t *mg
                                                  size_t *d_compressed_sizes, int *d_statuses, void *d_temp_storage,
                                                  size_t temp_storage_bytes, hipStream_t stream);
 
+/* The batched call with one prefix per chunk: d_prefix_ptrs[i] / d_prefix_sizes[i] (DEVICE arrays)
+ * are the bytes that precede chunk i -- earlier data of its stream, the previous version of a shard
+ * (zstd --patch-from per chunk), a per-tenant sample -- used as a raw-content dictionary.  Stream-
+ * ordered like nvcomp_zstd_batched_compress_async_v5: every array is a device array, nothing is
+ * allocated, synchronised or copied to the host.
+ * Frame i is byte-identical to what ZstdBatchManager::compress_with_history(chunk i, prefix i) writes
+ * at the handle's configuration; with d_prefix_sizes[i] == 0 it is the frame
+ * nvcomp_zstd_batched_compress_async_v5 writes for chunk i.  The frames carry no Dictionary_ID and
+ * decode with nvcomp_zstd_batched_decompress_prefix_async_v5 or libzstd's ZSTD_decompress_usingDict.
+ * Only the tail of a prefix that the matcher stages is read.  Levels 1-4: the last 64 KiB - block
+ * bytes; a chunk over 32 KiB is cut into 32 KiB blocks, the first sees the last 32 KiB of the prefix,
+ * later blocks see the frame's previous 32 KiB.  Levels >= 5: the last 64 KiB.
+ * A non-zero prefix size with a null pointer gives that chunk size 0 and status 2 and leaves its
+ * output untouched; a chunk of size 0 behaves as in the plain entry; neighbours are unaffected.
+ * Returns 2 for a null required array (d_statuses is optional), max_uncompressed_chunk_bytes == 0 or
+ * a handle with a dictionary set; 7 for a workspace below
+ * nvcomp_zstd_batch_get_batched_prefix_temp_size_v5 (nothing is launched); num_chunks == 0 succeeds
+ * and launches nothing.  The handle's checksum setting applies; dict_entropy and enable_ldm have no
+ * effect here.
+ * Out of scope: a prefix together with a handle dictionary; with per-chunk levels; with dict_entropy
+ * or long-distance matching; staging the aligned region of a reference for blocks after the first --
+ * at levels 1-4 a 64 KiB chunk's second block sees the frame's own first half, not the reference's
+ * second half, so delta users below level 5 should use chunks of <= 32 KiB (lifting that needs an
+ * offset bias through the matcher and the sequence stage).
+ * The workspace is that of a handle with a dictionary at its level. */
+size_t nvcomp_zstd_batch_get_batched_prefix_temp_size_v5(nvcomp_zstd_batch_manager_t *mgr, size_t num_chunks,
+                                                         size_t max_uncompressed_chunk_bytes);
+int nvcomp_zstd_batched_compress_prefix_async_v5(nvcomp_zstd_batch_manager_t *mgr, const void *const *d_uncompressed_ptrs,
+                                                 const size_t *d_uncompressed_sizes, const void *const *d_prefix_ptrs,
+                                                 const size_t *d_prefix_sizes, size_t max_uncompressed_chunk_bytes, size_t num_chunks,
+                                                 void *const *d_compressed_ptrs, size_t *d_compressed_sizes, int *d_statuses,
+                                                 void *d_temp_storage, size_t temp_storage_bytes, hipStream_t stream);
+
 /* NvcompV5BatchManager::decompress_async as a C handle call (reference include/cuda_zstd_nvcomp.h:97-99,
  * 119-125): host or device arrays, uncompressed_sizes[i] capacity in, bytes out; blocking on return. */
 size_t nvcomp_zstd_batch_get_decompress_temp_size_v5(nvcomp_zstd_batch_manager_t *mgr, const size_t *compressed_sizes, size_t num_chunks);
@@ -184,6 +217,46 @@ int nvcomp_zstd_batched_decompress_async_v5(nvcomp_zstd_batch_manager_t *mgr, co
                                             size_t max_uncompressed_chunk_bytes, size_t num_chunks, void *const *d_uncompressed_ptrs,
                                             size_t *d_actual_sizes, int *d_statuses, void *d_temp_storage, size_t temp_storage_bytes,
                                             hipStream_t stream);
+
+/* The same call with one prefix per buffer (DEVICE arrays; size 0 or a null pointer: none): the
+ * whole prefix is addressable in front of buffer i's frames, as with libzstd's
+ * ZSTD_decompress_usingDict on raw content.  A frame that names a Dictionary_ID gets the
+ * dictionary-wrong code (there is no formatted dictionary on this route).  The workspace is
+ * nvcomp_zstd_batched_decompress_get_temp_size_v5; a handle with a dictionary set returns 2.
+ * Out of scope: a prefix together with a handle dictionary. */
+int nvcomp_zstd_batched_decompress_prefix_async_v5(nvcomp_zstd_batch_manager_t *mgr, const void *const *d_compressed_ptrs,
+                                                   const size_t *d_compressed_sizes, const void *const *d_prefix_ptrs,
+                                                   const size_t *d_prefix_sizes, const size_t *d_uncompressed_caps,
+                                                   size_t max_uncompressed_chunk_bytes, size_t num_chunks, void *const *d_uncompressed_ptrs,
+                                                   size_t *d_actual_sizes, int *d_statuses, void *d_temp_storage,
+                                                   size_t temp_storage_bytes, hipStream_t stream);
+
+/* Many streams in one call: num_streams streams, each with a device-resident window of its last
+ * 64 KiB, compressed or decoded one chunk per stream per call.  create allocates everything the
+ * object owns (the compress and decode workspaces, one pair of 64 KiB window buffers per stream and
+ * direction, the prefix pointer and size arrays); a call allocates nothing and synchronises nothing.
+ * All arrays are DEVICE arrays of num_streams entries.
+ * compress_async: chunk i of stream i goes through nvcomp_zstd_batched_compress_prefix_async_v5
+ * behind window i, then one launch (zh_window_update_kernel, one workgroup per stream) advances every
+ * window.  Frame i is what ZstdStreamingManager::compress_chunk_with_history writes for that stream.
+ * Every output buffer holds cuda_zstd_stream_batch_max_compressed_chunk_size bytes.
+ * decompress_async: the same with nvcomp_zstd_batched_decompress_prefix_async_v5 and the decoded
+ * output (d_out_caps null: max_chunk_bytes for every stream).  Frames decode in stream order.
+ * A stream whose item did not succeed keeps its window; an idle stream (d_in_sizes[i] == 0) reports
+ * size 0 and status 2 like any empty item and keeps its window.  d_statuses is optional.
+ * reset: every window of both directions empty again (stream-ordered).
+ * Returns 2 for a null handle or required array, otherwise as the batched entries.
+ * Out of scope: dictionaries, per-chunk levels, dict_entropy, long-distance matching. */
+typedef struct cuda_zstd_stream_batch_t cuda_zstd_stream_batch_t;
+cuda_zstd_stream_batch_t *cuda_zstd_stream_batch_create(int level, size_t num_streams, size_t max_chunk_bytes);
+void cuda_zstd_stream_batch_destroy(cuda_zstd_stream_batch_t *sb);
+size_t cuda_zstd_stream_batch_max_compressed_chunk_size(cuda_zstd_stream_batch_t *sb);
+int cuda_zstd_stream_batch_compress_async(cuda_zstd_stream_batch_t *sb, const void *const *d_in_ptrs, const size_t *d_in_sizes,
+                                          void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, hipStream_t stream);
+int cuda_zstd_stream_batch_decompress_async(cuda_zstd_stream_batch_t *sb, const void *const *d_in_ptrs, const size_t *d_in_sizes,
+                                            const size_t *d_out_caps, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses,
+                                            hipStream_t stream);
+int cuda_zstd_stream_batch_reset(cuda_zstd_stream_batch_t *sb, hipStream_t stream);
 
 /* Batched decompressed-size query on the device (nvCOMP nvcompBatchedZstdGetDecompressSizeAsync
  * shape).  All arrays are DEVICE arrays; one launch; nothing is synchronised or allocated and no
@@ -359,6 +432,8 @@ long long cuda_zstd_hip_ldm_plan(cuda_zstd_manager_t *manager, const void *d_src
 /* HIP events around the finder's two kernels: on != 0 starts recording; on == 0 stops and stores the
  * summed milliseconds of the launches since then in *ms (optional). */
 void cuda_zstd_hip_ldm_profile(int on, double *ms);
+/* The same around zh_window_update_kernel (cuda_zstd_stream_batch_*). */
+void cuda_zstd_hip_window_profile(int on, double *ms);
 
 /* ---------------- library info ---------------- */
 const char *cuda_zstd_hip_version(void);

@@ -116,6 +116,30 @@ class ZstdBatchManager : public ZstdManager {
   // its workspace: get_batch_device_temp_size_for of a level >= 5 plus the items' ranks, one level
   // byte per block and the class ranges; at least what any dictionary-less manager's call needs
   static size_t get_batch_device_levels_temp_size(size_t count, size_t max_chunk_bytes);
+  // compress_batch_device with one prefix per chunk: d_prefix_ptrs[i] / d_prefix_sizes[i] (device
+  // arrays) are the bytes that precede chunk i, used as a raw-content dictionary without a
+  // Dictionary_ID.  Frame i is byte-identical to what compress_with_history(chunk i, prefix i) writes
+  // at this manager's configuration; with d_prefix_sizes[i] == 0 it is compress_batch_device's frame.
+  // Stream-ordered like it: no allocation, no synchronisation, no copy to the host.  Only the tail
+  // the matcher stages is read: below level 5 the last 64 KiB - block bytes (a chunk over 32 KiB is
+  // cut into 32 KiB blocks, the first behind the prefix's last 32 KiB, later ones behind the frame's
+  // previous 32 KiB), from level 5 on the last 64 KiB.  A non-zero prefix size with a null pointer
+  // gives that chunk size 0 and status ERROR_INVALID_PARAMETER and leaves its output untouched.
+  // ERROR_INVALID_PARAMETER for a null array, max_chunk_bytes == 0 or a manager with a dictionary
+  // set; ERROR_BUFFER_TOO_SMALL for a workspace below get_batch_device_prefix_temp_size (nothing is
+  // launched); count == 0 succeeds.  The checksum setting applies; dict_entropy and enable_ldm have
+  // no effect here.
+  // Not covered: a prefix together with a manager dictionary, with per-chunk levels, or with
+  // dict_entropy / long-distance matching; staging the aligned region of a reference for blocks
+  // after the first (below level 5 a 64 KiB chunk's second block sees the frame's own first half,
+  // not the reference's second half: delta users there should keep chunks <= 32 KiB; lifting that
+  // needs an offset bias through the matcher and the sequence stage).
+  Status compress_batch_device_prefix(const void *const *d_in_ptrs, const size_t *d_in_sizes, const void *const *d_prefix_ptrs,
+                                      const size_t *d_prefix_sizes, size_t max_chunk_bytes, size_t count, void *const *d_out_ptrs,
+                                      size_t *d_out_sizes, int *d_statuses, void *temp_workspace, size_t temp_size, hipStream_t stream);
+  // its workspace: that of a manager with a dictionary at this level (the 32 KiB split with staging
+  // and gather above 32 KiB below level 5, the deep matcher's slots from level 5 on)
+  size_t get_batch_device_prefix_temp_size(size_t count, size_t max_chunk_bytes) const;
 
   // Stream-ordered batched decompression over device arrays (no host sync; GPU decoder,
   // any RFC 8878 frames); used by nvcomp_zstd_batched_decompress_async_v5.
@@ -126,6 +150,15 @@ class ZstdBatchManager : public ZstdManager {
                                  size_t max_uncompressed_chunk_bytes, size_t count, void *const *d_out_ptrs, size_t *d_out_sizes,
                                  int *d_statuses, void *temp_workspace, size_t temp_size, hipStream_t stream);
   static size_t get_batch_device_decompress_temp_size(size_t count, size_t max_uncompressed_chunk_bytes);
+  // decompress_batch_device with one prefix per buffer (device arrays; size 0 or a null pointer:
+  // none): the whole prefix is addressable in front of the frame, as with libzstd's
+  // ZSTD_decompress_usingDict on raw content.  A frame that names a Dictionary_ID is answered with
+  // the dictionary-wrong code (there is no formatted dictionary on this route).  Same workspace;
+  // ERROR_INVALID_PARAMETER for a manager with a dictionary set.
+  Status decompress_batch_device_prefix(const void *const *d_in_ptrs, const size_t *d_in_sizes, const void *const *d_prefix_ptrs,
+                                        const size_t *d_prefix_sizes, const size_t *d_out_caps, size_t max_uncompressed_chunk_bytes,
+                                        size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp_workspace,
+                                        size_t temp_size, hipStream_t stream);
   // The decompressed size of every buffer, computed on the device (nvCOMP's
   // nvcompBatchedZstdGetDecompressSizeAsync): all arrays are device arrays, one launch, no
   // workspace, no allocation, no synchronisation.  d_out_sizes[i] = the bytes all frames of buffer i

@@ -49,6 +49,18 @@ class NvcompV5BatchManager {
   // (ZstdBatchManager::get_decompressed_sizes_async)
   Status get_decompress_sizes_async(const void *const *d_compressed_ptrs, const size_t *d_compressed_bytes, size_t *d_uncompressed_bytes,
                                     int *d_statuses, size_t num_chunks, hipStream_t stream = 0);
+  // One prefix per chunk (ZstdBatchManager::compress_batch_device_prefix / decompress_batch_device_prefix):
+  // device arrays only, stream-ordered, nothing is synchronised or allocated; workspaces of
+  // batch_manager().get_batch_device_prefix_temp_size and get_batch_device_decompress_temp_size.
+  // Not together with a dictionary, per-chunk levels, dict_entropy or long-distance matching.
+  Status compress_prefix_async(const void *const *d_uncompressed_ptrs, const size_t *d_uncompressed_sizes, const void *const *d_prefix_ptrs,
+                               const size_t *d_prefix_sizes, size_t max_uncompressed_chunk_bytes, size_t num_chunks,
+                               void *const *d_compressed_ptrs, size_t *d_compressed_sizes, int *d_statuses, void *d_temp_storage,
+                               size_t temp_storage_bytes, hipStream_t stream = 0);
+  Status decompress_prefix_async(const void *const *d_compressed_ptrs, const size_t *d_compressed_sizes, const void *const *d_prefix_ptrs,
+                                 const size_t *d_prefix_sizes, const size_t *d_uncompressed_caps, size_t max_uncompressed_chunk_bytes,
+                                 size_t num_chunks, void *const *d_uncompressed_ptrs, size_t *d_actual_sizes, int *d_statuses,
+                                 void *d_temp_storage, size_t temp_storage_bytes, hipStream_t stream = 0);
   const CompressionStats &get_stats() const;
   ZstdBatchManager &batch_manager();
 
