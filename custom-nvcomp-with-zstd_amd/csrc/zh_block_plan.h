@@ -1,7 +1,8 @@
 // zh_block_plan.h — the block descriptors of a frame: the one rule behind the host plan
 // (ZstdBatchManager::Impl::run, zh_host.cpp) and the two device plans (zh_plan_kernel,
 // zh_plan_levels_kernel, zh_plan.hip).  Plain C++, no HIP types: tests/cpp/block_plan_check.cpp
-// and tests/cpp/prefix_plan_check.cpp (the per-item prefix) walk the rule on the host.
+// and tests/cpp/prefix_plan_check.cpp (the per-item prefix) walk the rule on the host, as does
+// tests/cpp/dictset_check.cpp for an item of a dictionary-set batch (zh_dictset.h).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -76,7 +77,9 @@ struct ZhBatchPlan {
 // One item of the batch.  pre / pre_n: the item's own prefix (pre_n 0: none), the bytes that
 // precede the chunk as a raw-content dictionary without a Dictionary_ID; the item then gets the
 // descriptors of a batch whose dictionary is that prefix, an item without one those of a
-// dictionary-less frame.  Not together with ZhBatchPlan::dict.
+// dictionary-less frame.  Not together with ZhBatchPlan::dict.  dict_id / flags: an item of a
+// dictionary-set batch (zh_dictset.h) is planned behind its entry's content, and its frames carry
+// that entry's Dictionary_ID and frame flags (ZH_F_DICTENT).
 struct ZhPlanItem {
   const u8 *src;
   u64 size;
@@ -85,6 +88,8 @@ struct ZhPlanItem {
   u8 *out;
   const u8 *pre = nullptr;
   u64 pre_n = 0;
+  u32 dict_id = 0;
+  u32 flags = 0;
 };
 
 // A dictionary frame below ZH_DEEP_LEVEL is cut into 32 KiB blocks from 32 KiB on (ZH_FRAME_BLOCK)
@@ -111,7 +116,7 @@ ZH_BP_HD ZhBlockDesc zh_block_desc(const ZhBatchPlan &p, const ZhPlanItem &it, u
   d.item = it.index;
   d.n = 0;
   if (k < nb && !zh_item_bad_prefix(p, it)) d.n = (u32)(it.size - (u64)k * bs < bs ? it.size - (u64)k * bs : bs);
-  d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) | p.flags | (deep ? ZH_F_DEEP : 0u);
+  d.flags = (k == 0 ? ZH_F_FIRST : 0u) | (k + 1 == nb ? ZH_F_LAST : 0u) | (nb == 1 ? ZH_F_DIRECT : 0u) | p.flags | it.flags | (deep ? ZH_F_DEEP : 0u);
   d.pre = nullptr;
   d.pre_n = 0;
   d.dict_id = 0;
@@ -123,7 +128,7 @@ ZH_BP_HD ZhBlockDesc zh_block_desc(const ZhBatchPlan &p, const ZhPlanItem &it, u
     const u8 *const dict = p.dict ? p.dict : it.pre;
     u64 const dict_n = p.dict ? (u64)p.dict_n : it.pre_n;
     d.flags |= ZH_F_DICT;
-    d.dict_id = p.dict ? p.dict_id : 0u;
+    d.dict_id = p.dict ? p.dict_id : it.dict_id;
     if (k == 0) {
       // what fits in front of the block in K1's 64 KiB of LDS; the deep matcher keeps its staged
       // bytes in global memory and takes up to ZH_DEEP_PRE

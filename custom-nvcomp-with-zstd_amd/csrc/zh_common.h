@@ -5,6 +5,7 @@
 #include "zstd_hip_params.h"
 #include "zh_dict_ent.h"
 #include "zh_block_plan.h"  // ZhBlockDesc, ZhItemDesc, ZH_F_*, ZH_ST_*, u8 .. u64
+#include "zh_dictset.h"
 
 typedef int16_t s16;
 typedef int32_t s32;
@@ -104,6 +105,12 @@ struct ZhWorkspace {
   const ZhDictEnt *dent;
   // The statistics pass's four global histograms (ZH_F_STATS; null: none)
   u32 *stats;
+  // A dictionary-set batch (zh_dictset.h; null: none): the set's entry table and every item's entry
+  // index.  A ZH_F_DICT block's precomputed tables and entropy blob are then its item's entry's
+  // (such a block's index is in range: the plan leaves any other item without active slots), and
+  // dtab, dd_* and dent above stay null.
+  const ZhDictSetEntry *set;
+  const s32 *item_ent;
   __device__ u64 *seq(u32 b) const { return (u64 *)(base + (size_t)b * ZH_WS_BLOCK_BYTES); }
   __device__ u8 *lits(u32 b) const { return base + (size_t)b * ZH_WS_BLOCK_BYTES + ZH_SEQ_BYTES; }
   __device__ u32 *meta(u32 b) const { return (u32 *)(base + (size_t)b * ZH_WS_BLOCK_BYTES + ZH_SEQ_BYTES + ZH_LIT_BYTES); }
@@ -113,6 +120,18 @@ struct ZhWorkspace {
 };
 
 #define ZH_DTAB_MARGIN 256u  // tail positions a block inserts itself (>= one inserter batch)
+
+// One dictionary of a batched table build (zh_lz.hip zh_dict_hash_batch_kernel / zh_dict_pack_batch_kernel,
+// zh_lz_deep.hip zh_deep_dict_batch_kernel): what the single builders take as arguments.
+struct ZhDictBuildJob {
+  const u8 *tail;  // K1: the last P content bytes; B = P - ZH_DTAB_MARGIN positions hashed (0: no tables)
+  u16 *dtab;       // 2^15 u16 out
+  const u8 *dtail; // deep matcher: the last dP content bytes (0: no chains)
+  u32 *dprev;      // >= split u32 out, 16-byte aligned
+  u32 *dhead;      // 2^ZH_HASH_LOG_SHORT u32 out
+  u32 B, dP;
+};
+#define ZH_DEEP_DICT_STG ((u32)ZH_DEEP_PRE + 256u)  // staging bytes of one dictionary's chain build
 
 // Mixed-level batch (zh_plan.hip zh_rank_kernel): the class partition the device leaves in the
 // workspace.  Blocks are laid out sorted by parse class (ZH_LEVEL_CLASS), so class c owns block

@@ -1260,6 +1260,7 @@ struct DecHandoff {
   u64 sumLL, sumML;
   u32 sbad;
   u32 rep[3];      // repcodes at the block start
+  s32 dent;        // with a dictionary set: the entry the deferred frame resolved to (-1: none)
 };
 static_assert(sizeof(DecHandoff) <= ZH_DEC_HANDOFF_BYTES, "hand-off record");
 
@@ -1410,7 +1411,44 @@ __device__ __forceinline__ u32 frame_header(const ZhDecArgs &a, const u8 *p, u64
   else if (fcsn == 2) h.fcs = rd16(q) + 256ull;
   else if (fcsn == 4) h.fcs = rd32(q);
   else if (fcsn == 8) h.fcs = (u64)rd32(q) | (u64)rd32(q + 4) << 32;
-  if (h.did != 0 && (!a.dict || h.did != a.dict_id)) return ST_DICT;  // libzstd: dictionary_wrong
+  // libzstd: dictionary_wrong (with a dictionary set the frame's entry is looked up by frame_dict)
+  if (!a.set && h.did != 0 && (!a.dict || h.did != a.dict_id)) return ST_DICT;
+  return ST_OK;
+}
+
+// ---- the dictionary of one frame.  Without a dictionary set: the launch's (a.dict) or the item's
+// prefix, as item_view left them in `it`.  With one (a.set): resolved per frame -- item idx's entry
+// index if it names one (a.dict_index[idx] >= 0; an entry with another Dictionary_ID than the
+// frame's is ST_DICT, an index outside the set ST_INVALID), else the entry with the frame's
+// Dictionary_ID (none: ST_DICT), else, for a frame without an ID, no dictionary.
+struct FrameDict {
+  const u8 *dict;  // the whole buffer (null: none) and its content offset: a formatted dictionary's
+  u32 off;         // tables and repcodes seed the frame (load_dict_entropy)
+  const u8 *dend;  // match sources before the frame start: dlen content bytes ending at dend
+  s64 dlen;
+  s32 entry;       // the set's entry (-1: none)
+};
+__device__ __forceinline__ u32 frame_dict(const ZhDecArgs &a, const Item &it, u32 did, FrameDict &fd) {
+  fd.dict = a.dict;
+  fd.off = a.dict_off;
+  fd.dend = it.dend;
+  fd.dlen = it.dlen;
+  fd.entry = -1;
+  if (!a.set) return ST_OK;
+  s32 e = a.dict_index ? a.dict_index[it.idx] : -1;
+  if (e < -1 || e >= (s32)a.set_count) return ST_INVALID;
+  if (e < 0) {
+    if (did == 0) return ST_OK;
+    e = zh_dictset_find(a.set_ids, a.set_nids, did);
+    if (e < 0) return ST_DICT;
+  }
+  ZhDictSetEntry const ent = a.set[e];
+  if (did != 0 && ent.id != did) return ST_DICT;
+  fd.dict = ent.buf;
+  fd.off = ent.off;
+  fd.dend = ent.buf + ent.n;
+  fd.dlen = (s64)(ent.n - ent.off);
+  fd.entry = e;
   return ST_OK;
 }
 
@@ -1664,22 +1702,28 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
     if (st != ST_OK) break;
     ip += fh.size;
     if (fh.skip) continue;
+    FrameDict fd;  // this frame's dictionary (every pass: a first block may repeat its tables)
+    st = frame_dict(a, it, fh.did, fd);
+    if (st != ST_OK) break;
+    if constexpr (P != Pass::Rest && !SZ) {
+      if (a.set && lane == 0) it.ho->dent = fd.entry;  // for zh_dec_exec_kernel, should the buffer be deferred
+    }
     // (Size: cap is 2^64 - 1, so this is the sum of the frames' sizes overflowing)
     if (fh.fcs != ~0ull && fh.fcs > cap - produced) { st = ST_FULL; break; }
     u64 const fstart = produced;
     bool const stated = SZ && fh.fcs != ~0ull;  // Size: the frame's size is its Frame_Content_Size
     // frame state: repcodes, table kinds
     u32 rep0 = 1, rep1 = 4, rep2 = 8;
-    bool const fdict = a.dict && a.dict_off && !stated;  // formatted dictionary: its tables and repcodes
+    bool const fdict = fd.dict && fd.off && !stated;  // formatted dictionary: its tables and repcodes
     if (lane == 0) {
       L.tkind[0] = L.tkind[1] = L.tkind[2] = TAB_NONE;
       L.hvalid = 0;
-      L.err = (fdict && !load_dict_entropy(L, a.dict, a.dict_off)) ? 1u : 0u;
+      L.err = (fdict && !load_dict_entropy(L, fd.dict, fd.off)) ? 1u : 0u;
     }
     __syncthreads();
     if (fdict) {
       if (uni(L.err)) { st = ST_DICT; break; }
-      const u8 *const rp = a.dict + a.dict_off - 12;
+      const u8 *const rp = fd.dict + fd.off - 12;
       rep0 = rd32(rp);
       rep1 = rd32(rp + 4);
       rep2 = rd32(rp + 8);
@@ -1787,7 +1831,7 @@ __device__ __forceinline__ void decode_body(PassLds<P> &L, const ZhDecArgs &a) {
             __syncthreads();
             u32 const tl = lits.n - (u32)sumLL;
             s64 const fpos = (s64)(produced - fstart);  // frame bytes before this block
-            bad = !execute_block(L, it.sl, ob, fpos, lits, nseq, tl, it.dend, it.dlen);
+            bad = !execute_block(L, it.sl, ob, fpos, lits, nseq, tl, fd.dend, fd.dlen);
             DSTAMP(4);
           }
           if (bad) { st = ST_CORRUPT; break; }
@@ -1857,11 +1901,19 @@ struct ExecLds {
 extern "C" __global__ __launch_bounds__(DEC_THREADS) void zh_dec_exec_kernel(ZhDecArgs a) {
   __shared__ ExecLds L;
   u32 const lane = lane_id();
-  Item const it = item_view(a, blockIdx.x);
+  Item it = item_view(a, blockIdx.x);
   if (lane < 4) L.wvs[64 + lane] = 0x7FFFFFFF;
   __syncthreads();
   DecHandoff *const ho = it.ho;
   if (uni(ho->flag) != 1) return;
+  if (a.set) {  // the entry the walker resolved for the deferred frame (frame_dict)
+    s32 const e = (s32)uni((u32)ho->dent);
+    if (e >= 0 && e < (s32)a.set_count) {
+      ZhDictSetEntry const ent = a.set[e];
+      it.dend = ent.buf + ent.n;
+      it.dlen = (s64)(ent.n - ent.off);
+    }
+  }
   LitSrc lits;
   lits.g = (const u8 *)uni64(ho->litg);
   lits.rle = uni(ho->litrle);

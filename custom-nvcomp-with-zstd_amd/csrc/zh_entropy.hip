@@ -982,10 +982,12 @@ __device__ __noinline__ bool dict_literals(const ZhDictEnt *dent, const u32 *his
   return true;
 }
 
-extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const ZhBlockDesc *__restrict__ blocks, ZhWorkspace ws, u32 window_log,
-                                                                             u32 cfg_block_size, u64 *__restrict__ item_size,
-                                                                             u32 *__restrict__ item_status, u32 *__restrict__ blk_size,
-                                                                             const u8 *__restrict__ blk_level) {
+// The entropy kernel's body.  SET: the kernel of a dictionary-set batch (ws.set; zh_dictset.h) -- its
+// own instantiation, so that every other batch runs the code it ran before.
+template <bool SET>
+__device__ __forceinline__ void entropy_block(const ZhBlockDesc *__restrict__ blocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size,
+                                              u64 *__restrict__ item_size, u32 *__restrict__ item_status, u32 *__restrict__ blk_size,
+                                              const u8 *__restrict__ blk_level) {
   extern __shared__ __attribute__((aligned(16))) u8 smem_all[];
   // Two waves per block, each with its own copy of the LDS layout: wave 0 builds the literals
   // section, wave 1 (concurrently) the sequences section's merge / repcodes / codes / FSE
@@ -1017,7 +1019,8 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
   Out const o{d.dst, d.dst_cap};
   // the dictionary's entropy section (CompressionConfig::dict_entropy): first block of a frame only
   constexpr u32 DENT_FLAGS = ZH_F_FIRST | ZH_F_DICT | ZH_F_DICTENT;
-  const ZhDictEnt *const dent = (d.flags & DENT_FLAGS) == DENT_FLAGS ? ws.dent : nullptr;
+  // (a dictionary-set batch: the blob of the block's own entry, zh_dictset.h)
+  const ZhDictEnt *const dent = (d.flags & DENT_FLAGS) == DENT_FLAGS ? (SET ? ws.set[ws.item_ent[d.item]].dent : ws.dent) : nullptr;
   // fewest literals worth an entropy-coded section: with the dictionary's Huffman table (no tree
   // description to pay for) libzstd's 6, else its 64
   // statistics pass of dictionary finalisation (ZH_F_STATS): every block's literal histogram and
@@ -1623,6 +1626,18 @@ extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const
 #endif
   if (wave == 1 && !handoff) write_status(d, b, total, item_size, item_status, blk_size);
 }
+extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_kernel(const ZhBlockDesc *__restrict__ blocks, ZhWorkspace ws, u32 window_log,
+                                                                             u32 cfg_block_size, u64 *__restrict__ item_size,
+                                                                             u32 *__restrict__ item_status, u32 *__restrict__ blk_size,
+                                                                             const u8 *__restrict__ blk_level) {
+  entropy_block<false>(blocks, ws, window_log, cfg_block_size, item_size, item_status, blk_size, blk_level);
+}
+extern "C" __global__ __launch_bounds__(K2_THREADS) void zh_entropy_set_kernel(const ZhBlockDesc *__restrict__ blocks, ZhWorkspace ws, u32 window_log,
+                                                                                 u32 cfg_block_size, u64 *__restrict__ item_size,
+                                                                                 u32 *__restrict__ item_status, u32 *__restrict__ blk_size,
+                                                                                 const u8 *__restrict__ blk_level) {
+  entropy_block<true>(blocks, ws, window_log, cfg_block_size, item_size, item_status, blk_size, blk_level);
+}
 
 // ======================= FSE state chains (K3) =======================
 // One wave per block (K3_WAVES per workgroup).  Lane t * K3_SEGS + g runs segment g of table
@@ -1925,13 +1940,14 @@ extern "C" void zh_hst_host(u32 *out6) {
 namespace zh {
 hipError_t entropy_init() {
   hipError_t e = hipFuncSetAttribute((const void *)zh_entropy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K2_LDS);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_entropy_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K2_LDS);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_fse_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K3_LDS);
   return e;
 }
 void entropy_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 window_log, u32 cfg_block_size, u64 *d_item_size,
                     u32 *d_item_status, u32 *d_blk_size, const u8 *d_blk_level, hipStream_t stream) {
-  hipLaunchKernelGGL(zh_entropy_kernel, dim3(nblocks), dim3(K2_THREADS), K2_LDS, stream, d_descs, ws, window_log, cfg_block_size, d_item_size,
-                     d_item_status, d_blk_size, d_blk_level);
+  hipLaunchKernelGGL(ws.set ? zh_entropy_set_kernel : zh_entropy_kernel, dim3(nblocks), dim3(K2_THREADS), K2_LDS, stream, d_descs, ws, window_log,
+                     cfg_block_size, d_item_size, d_item_status, d_blk_size, d_blk_level);
   // (persistent K3 / K4 waves taking blocks from a counter measured slower: entropy stage
   // 3.04 -> 3.22 ms at 16,384 blocks, 0.75 -> 0.80 ms at 2,048)
   u32 const g3 = (nblocks + K3_BPW - 1) / K3_BPW, g4 = (nblocks + K4_WAVES - 1) / K4_WAVES;

@@ -574,6 +574,152 @@ struct DevDict {
   }
 };
 
+// A set of dictionaries on the device (zh_dictset.h): one allocation holding, per entry, what
+// DevDict::load builds for one dictionary, indexed by an entry table, with the non-zero IDs sorted
+// next to it.  Immutable once built.  The tables come from the batched builders (the dictionary is
+// a grid dimension), ZH_DICTSET_GROUP dictionaries at a time so that the build's scratch is bounded:
+// four stream operations per group, whatever the set's size.
+#define ZH_DICTSET_GROUP 64u
+struct DictSetDev {
+  u8 *mem = nullptr;
+  size_t mem_bytes = 0;
+  std::vector<ZhDictSetEntry> ents;  // (device pointers)
+  std::vector<ZhDictSetId> ids;      // the non-zero IDs, sorted
+  const ZhDictSetEntry *d_ents = nullptr;
+  const ZhDictSetId *d_ids = nullptr;
+  // stream-ordered launches that may still read the set: one event per stream (as DevDict::uses)
+  std::mutex mu;
+  std::vector<std::pair<hipStream_t, hipEvent_t>> uses;
+  DictSetDev() = default;
+  DictSetDev(const DictSetDev &) = delete;
+  DictSetDev &operator=(const DictSetDev &) = delete;
+  ~DictSetDev() {
+    (void)wait_uses();
+    for (auto &u : uses) (void)hipEventDestroy(u.second);
+    if (mem) (void)hipFree(mem);
+  }
+  u32 count() const { return (u32)ents.size(); }
+  int find(u32 id) const { return zh_dictset_find(ids.data(), (u32)ids.size(), id); }
+  // the decoder's view; dict_index: one entry index per item (device array) or null
+  void fill(ZhDecArgs &a, const int32_t *dict_index) const {
+    a.set = d_ents;
+    a.set_ids = d_ids;
+    a.set_count = count();
+    a.set_nids = (u32)ids.size();
+    a.dict_index = dict_index;
+  }
+  Status note_use(hipStream_t stream) {
+    std::lock_guard<std::mutex> g(mu);
+    for (auto &u : uses)
+      if (u.first == stream) return hipEventRecord(u.second, stream) == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
+    hipEvent_t e;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+    uses.emplace_back(stream, e);
+    return hipEventRecord(e, stream) == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
+  }
+  Status wait_uses() {
+    std::lock_guard<std::mutex> g(mu);
+    Status s = Status::SUCCESS;
+    for (auto &u : uses)
+      if (hipEventSynchronize(u.second) != hipSuccess) s = Status::ERROR_CUDA_ERROR;
+    return s;
+  }
+  // bufs[i] / sizes[i]: host bytes of dictionary i, raw content or formatted
+  Status build(const u8 *const *bufs, const size_t *sizes, size_t n, hipStream_t stream) {
+    if (!bufs || !sizes || n < 1 || n > ZH_DICTSET_MAX) return Status::ERROR_INVALID_PARAMETER;
+    Status s = ensure_kernels();
+    if (s != Status::SUCCESS) return s;
+    std::vector<u32> raw_ids(n);
+    std::vector<size_t> offs(n);
+    for (size_t i = 0; i < n; i++) {
+      if (!bufs[i] || sizes[i] < dictionary::MIN_DICT_SIZE || sizes[i] > zh::kDictMaxBytes) return Status::ERROR_INVALID_PARAMETER;
+      if (!zh::dict_layout(bufs[i], sizes[i], raw_ids[i], offs[i])) return Status::ERROR_DICTIONARY_FAILED;
+    }
+    ids.resize(n);
+    u32 nids = 0;
+    if (!zh_dictset_sort_ids(raw_ids.data(), n, ids.data(), &nids)) return Status::ERROR_INVALID_PARAMETER;  // a shared non-zero ID
+    ids.resize(nids);
+    // layout: the uploaded part (entry table, IDs, build jobs, buffers, entropy blobs), then the tables
+    size_t o = 0;
+    auto take = [&o](size_t bytes) { size_t const at = o; o = align256(o + bytes); return at; };
+    size_t const o_ents = take(n * sizeof(ZhDictSetEntry)), o_ids = take(n * sizeof(ZhDictSetId)), o_jobs = take(n * sizeof(ZhDictBuildJob));
+    std::vector<size_t> o_buf(n), o_dent(n, 0), o_dtab(n, 0), o_prev(n, 0), o_head(n, 0);
+    std::vector<ZhDictEnt> blobs(n);
+    std::vector<u8> has_ent(n, 0);
+    for (size_t i = 0; i < n; i++) {
+      o_buf[i] = take(sizes[i]);
+      size_t co2 = 0;
+      if (offs[i] && zh::dent::parse(bufs[i], sizes[i], &blobs[i], &co2) && co2 == offs[i]) {
+        has_ent[i] = 1;
+        o_dent[i] = take(sizeof(ZhDictEnt));
+      }
+    }
+    size_t const upload = o;
+    size_t const tab_entries = (size_t(1) << ZH_HASH_LOG_LONG) + (size_t(1) << ZH_HASH_LOG_SHORT);
+    ents.assign(n, ZhDictSetEntry{});
+    std::vector<ZhDictBuildJob> jobs(n);
+    for (size_t i = 0; i < n; i++) {
+      size_t const cn = sizes[i] - offs[i];
+      ZhDictSetEntry &e = ents[i];
+      e.n = (u32)sizes[i];
+      e.off = (u32)offs[i];
+      e.id = raw_ids[i];
+      e.dtab_P = zh::lz_dict_tables_P(cn);
+      zh::lz_deep_dict_shape(cn, e.dd_pre, e.dd_split);
+      if (e.dtab_P) o_dtab[i] = take(tab_entries * 2);
+      if (e.dd_pre) {
+        o_prev[i] = take((size_t)e.dd_split * 4);
+        o_head[i] = take(size_t(4) << ZH_HASH_LOG_SHORT);
+      }
+    }
+    mem_bytes = o;
+    if (hipMalloc(&mem, mem_bytes) != hipSuccess) { mem = nullptr; return Status::ERROR_OUT_OF_MEMORY; }
+    for (size_t i = 0; i < n; i++) {
+      ZhDictSetEntry &e = ents[i];
+      size_t const cn = sizes[i] - offs[i];
+      e.buf = mem + o_buf[i];
+      e.dtab = e.dtab_P ? (const u16 *)(mem + o_dtab[i]) : nullptr;
+      e.dd_prev = e.dd_pre ? (const u32 *)(mem + o_prev[i]) : nullptr;
+      e.dd_head = e.dd_pre ? (const u32 *)(mem + o_head[i]) : nullptr;
+      e.dent = has_ent[i] ? (const ZhDictEnt *)(mem + o_dent[i]) : nullptr;
+      ZhDictBuildJob &j = jobs[i];
+      j.tail = e.buf + e.off + cn - e.dtab_P;
+      j.dtab = (u16 *)e.dtab;
+      j.B = e.dtab_P ? e.dtab_P - ZH_DTAB_MARGIN : 0u;
+      j.dtail = e.buf + e.off + cn - e.dd_pre;
+      j.dprev = (u32 *)e.dd_prev;
+      j.dhead = (u32 *)e.dd_head;
+      j.dP = e.dd_pre;
+    }
+    std::vector<u8> h(upload);
+    memcpy(h.data() + o_ents, ents.data(), n * sizeof(ZhDictSetEntry));
+    if (nids) memcpy(h.data() + o_ids, ids.data(), nids * sizeof(ZhDictSetId));
+    memcpy(h.data() + o_jobs, jobs.data(), n * sizeof(ZhDictBuildJob));
+    for (size_t i = 0; i < n; i++) {
+      memcpy(h.data() + o_buf[i], bufs[i], sizes[i]);
+      if (has_ent[i]) memcpy(h.data() + o_dent[i], &blobs[i], sizeof(ZhDictEnt));
+    }
+    if (hipMemcpy(mem, h.data(), upload, hipMemcpyHostToDevice) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+    d_ents = (const ZhDictSetEntry *)(mem + o_ents);
+    d_ids = (const ZhDictSetId *)(mem + o_ids);
+    // the tables, a group at a time
+    u32 const group = (u32)std::min<size_t>(n, ZH_DICTSET_GROUP);
+    size_t const tmp_bytes = align256((size_t)group * tab_entries * 4);
+    u8 *scratch = nullptr;
+    if (hipMalloc(&scratch, tmp_bytes + (size_t)group * ZH_DEEP_DICT_STG) != hipSuccess) return Status::ERROR_OUT_OF_MEMORY;
+    const ZhDictBuildJob *const d_jobs = (const ZhDictBuildJob *)(mem + o_jobs);
+    hipError_t e = hipSuccess;
+    for (size_t g0 = 0; g0 < n && e == hipSuccess; g0 += group) {
+      u32 const cnt = (u32)std::min<size_t>(group, n - g0);
+      e = zh::lz_dict_tables_batch(d_jobs + g0, cnt, (u32 *)scratch, stream);
+      if (e == hipSuccess) e = zh::lz_deep_dict_tables_batch(d_jobs + g0, cnt, scratch + tmp_bytes, stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    (void)hipFree(scratch);
+    return e == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
+  }
+};
+
 // The batch of layout L bound to its (aligned) workspace: every pointer the plan and the stages
 // take, the descriptor rule's batch constants (plan.out_cap is the caller's: one per batch on the
 // device routes, one per item on the host route) and the filled ZhWorkspace.  dd: the batch's
@@ -646,6 +792,7 @@ class ZstdBatchManager::Impl {
   DevDict mgr_dict, call_dict;  // set_dictionary()'s / compress()'s per-call dictionary
   u32 *stats_dev = nullptr;     // collect_entropy_stats: run() asks the entropy kernel for its histograms (ZH_F_STATS)
   const DevDict *active() const { return mgr_dict.n ? &mgr_dict : nullptr; }
+  std::shared_ptr<DictSetDev> set;  // set_dictionary_set()'s dictionary set (never together with mgr_dict)
 
   explicit Impl(const CompressionConfig &c) : config(c) {}
   ~Impl() { if (pinned) (void)hipHostFree(pinned); }
@@ -687,6 +834,10 @@ class ZstdBatchManager::Impl {
   // dictionary frame's descriptors, the others plain ones, in a batch shaped like a dictionary
   // handle's (prefix_shape); ws.dtab and ws.dd_* stay null as for a view, so every first block
   // hashes its own prefix.
+  // a.dict_index: one entry of the bound dictionary set per item, read on the device by the plan --
+  // the entry's content is the item's prefix, its ID the frames' Dictionary_ID (zh_dictset_plan_item),
+  // in the same shape; the stages take each first block's precomputed tables and entropy blob from
+  // its item's entry (ws.set / ws.item_ent).
   Status run_device(const ZhPlanArrays &a, bool levels, size_t max_chunk, size_t count, size_t *d_out_sizes, int *d_statuses, void *temp,
                     size_t temp_size, hipStream_t stream) {
     // one manager serialises calls (the dictionary's use events: set_dictionary waits on them)
@@ -703,7 +854,10 @@ class ZstdBatchManager::Impl {
     // one prefix source per item: not a batch dictionary too, and one level per batch
     bool const prefix = a.prefix_ptrs || a.prefix_sizes;
     if (prefix && (!a.prefix_ptrs || !a.prefix_sizes || dd || levels)) return Status::ERROR_INVALID_PARAMETER;
-    BatchShape const shape = levels ? BatchShape::mixed_levels(count, max_chunk) : prefix ? prefix_shape(count, max_chunk) : device_shape(count, max_chunk);
+    // one entry of the bound set per item: one level per batch, no prefix, no long-distance matching
+    std::shared_ptr<DictSetDev> const ds = a.dict_index ? set : nullptr;
+    if (a.dict_index && (!ds || dd || levels || prefix || config.enable_ldm)) return Status::ERROR_INVALID_PARAMETER;
+    BatchShape const shape = levels ? BatchShape::mixed_levels(count, max_chunk) : (prefix || ds) ? prefix_shape(count, max_chunk) : device_shape(count, max_chunk);
     if (levels && (count > ZH_RANK_MAX_ITEMS || shape.nblocks > 0xFFFFFFFFull)) return Status::ERROR_INVALID_PARAMETER;
     WsLayout const L(shape);
     if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
@@ -711,11 +865,25 @@ class ZstdBatchManager::Impl {
     b.plan.out_cap = estimate_compressed_size(max_chunk, config.level);
     b.item_size = (u64 *)d_out_sizes;
     if (d_statuses) b.item_status = (u32 *)d_statuses;
-    hipError_t e = zh::launch_plan(b, a, stream);
+    ZhPlanArrays pa = a;
+    if (ds) {
+      pa.set = b.ws.set = ds->d_ents;
+      pa.set_count = ds->count();
+      pa.set_entropy = config.dict_entropy ? 1u : 0u;
+      b.ws.item_ent = a.dict_index;
+    }
+    hipError_t e = zh::launch_plan(b, pa, stream);
     if (e == hipSuccess) e = zh::launch_compress(b, stream);
     if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
+    if (ds) return ds->note_use(stream);
     return dd ? dd->note_use(stream) : Status::SUCCESS;
   }
+
+  // The device-array decoding entries (defined with them below): prefixes, or the bound dictionary
+  // set with an optional entry index per buffer
+  Status run_device_decompress(const void *const *d_in_ptrs, const size_t *d_in_sizes, const void *const *d_prefix_ptrs,
+                               const size_t *d_prefix_sizes, const int32_t *d_dict_index, const size_t *d_out_caps, size_t max_out, size_t count,
+                               void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp, size_t temp_size, hipStream_t stream);
 
   // Run the device pipeline over a list of frames given as host arrays.
   // out_sizes: in = capacity, out = bytes; statuses out.
@@ -1020,6 +1188,7 @@ Status ZstdBatchManager::set_dictionary(const dictionary::Dictionary &d) {
   std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
   if (!d.raw_content || d.raw_size == 0) return Status::ERROR_INVALID_PARAMETER;
   if (d.raw_size < dictionary::MIN_DICT_SIZE || d.raw_size > dictionary::MAX_DICT_SIZE) return Status::ERROR_INVALID_PARAMETER;
+  if (pimpl_->set) return Status::ERROR_INVALID_PARAMETER;  // a dictionary set is bound: one or the other
   Status s = pimpl_->mgr_dict.load(d.raw_content, d.raw_size, 0);
   if (s != Status::SUCCESS) return s;
   pimpl_->dict_hdr = d.header;
@@ -1220,6 +1389,56 @@ Status ZstdBatchManager::compress_batch_device_prefix(const void *const *d_in_pt
                             d_statuses, temp, temp_size, stream);
 }
 
+// ---- dictionary sets (zh_dictset.h) ----
+class DictionarySet::Impl {
+ public:
+  std::shared_ptr<DictSetDev> dev = std::make_shared<DictSetDev>();
+};
+DictionarySet::DictionarySet() : pimpl_(new Impl) {}
+DictionarySet::~DictionarySet() { (void)pimpl_->dev->wait_uses(); }  // (a manager it is still bound to keeps the memory)
+size_t DictionarySet::count() const { return pimpl_->dev->count(); }
+int DictionarySet::find(u32 dictionary_id) const { return pimpl_->dev->find(dictionary_id); }
+Status DictionarySet::create(const dictionary::Dictionary *const *dicts, size_t count, hipStream_t stream, std::unique_ptr<DictionarySet> &out) {
+  out.reset();
+  if (!dicts || count < 1 || count > ZH_DICTSET_MAX) return Status::ERROR_INVALID_PARAMETER;
+  std::vector<std::vector<u8>> host(count);
+  std::vector<const u8 *> bufs(count);
+  std::vector<size_t> sizes(count);
+  for (size_t i = 0; i < count; i++) {
+    const dictionary::Dictionary *const d = dicts[i];
+    if (!d || !d->raw_content || d->raw_size < dictionary::MIN_DICT_SIZE || d->raw_size > dictionary::MAX_DICT_SIZE)
+      return Status::ERROR_INVALID_PARAMETER;
+    host[i].resize(d->raw_size);
+    Status const s = copy_any(host[i].data(), d->raw_content, d->raw_size, stream);
+    if (s != Status::SUCCESS) return s;
+    bufs[i] = host[i].data();
+    sizes[i] = d->raw_size;
+  }
+  std::unique_ptr<DictionarySet> set(new DictionarySet);
+  Status const s = set->pimpl_->dev->build(bufs.data(), sizes.data(), count, stream);
+  if (s != Status::SUCCESS) return s;
+  out = std::move(set);
+  return Status::SUCCESS;
+}
+
+Status ZstdBatchManager::set_dictionary_set(const DictionarySet *set) {
+  std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
+  if (set && pimpl_->mgr_dict.n) return Status::ERROR_INVALID_PARAMETER;  // a dictionary is set: one or the other
+  pimpl_->set = set ? set->impl().dev : nullptr;
+  return Status::SUCCESS;
+}
+size_t ZstdBatchManager::get_batch_device_dicts_temp_size(size_t count, size_t max_chunk) const {
+  return WsLayout(pimpl_->prefix_shape(count, max_chunk)).total;
+}
+Status ZstdBatchManager::compress_batch_device_dicts(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int32_t *d_dict_index,
+                                                     size_t max_chunk, size_t count, void *const *d_out_ptrs, size_t *d_out_sizes,
+                                                     int *d_statuses, void *temp, size_t temp_size, hipStream_t stream) {
+  if (!d_dict_index) return Status::ERROR_INVALID_PARAMETER;
+  ZhPlanArrays a{d_in_ptrs, d_in_sizes, d_out_ptrs, nullptr, nullptr, nullptr};
+  a.dict_index = d_dict_index;
+  return pimpl_->run_device(a, false, max_chunk, count, d_out_sizes, d_statuses, temp, temp_size, stream);
+}
+
 size_t ZstdBatchManager::get_batch_device_decompress_temp_size(size_t count, size_t max_out) {
   return DecLayout::make(std::max<size_t>(1, count), max_out).total;
 }
@@ -1235,6 +1454,23 @@ Status ZstdBatchManager::decompress_batch_device_prefix(const void *const *d_in_
                                                         const size_t *d_prefix_sizes, const size_t *d_out_caps, size_t max_out, size_t count,
                                                         void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp,
                                                         size_t temp_size, hipStream_t stream) {
+  return pimpl_->run_device_decompress(d_in_ptrs, d_in_sizes, d_prefix_ptrs, d_prefix_sizes, nullptr, d_out_caps, max_out, count, d_out_ptrs,
+                                       d_out_sizes, d_statuses, temp, temp_size, stream);
+}
+// With a dictionary set bound every frame's dictionary is resolved on the device from its
+// Dictionary_ID; d_dict_index (optional) names entries outright.
+Status ZstdBatchManager::decompress_batch_device_dicts(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int32_t *d_dict_index,
+                                                       const size_t *d_out_caps, size_t max_out, size_t count, void *const *d_out_ptrs,
+                                                       size_t *d_out_sizes, int *d_statuses, void *temp, size_t temp_size, hipStream_t stream) {
+  if (!pimpl_->set) return Status::ERROR_INVALID_PARAMETER;
+  return pimpl_->run_device_decompress(d_in_ptrs, d_in_sizes, nullptr, nullptr, d_dict_index, d_out_caps, max_out, count, d_out_ptrs, d_out_sizes,
+                                       d_statuses, temp, temp_size, stream);
+}
+Status ZstdBatchManager::Impl::run_device_decompress(const void *const *d_in_ptrs, const size_t *d_in_sizes, const void *const *d_prefix_ptrs,
+                                                     const size_t *d_prefix_sizes, const int32_t *d_dict_index, const size_t *d_out_caps,
+                                                     size_t max_out, size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses,
+                                                     void *temp, size_t temp_size, hipStream_t stream) {
+  Impl *const pimpl_ = this;
   // one manager serialises calls (the dictionary's use events: set_dictionary waits on them)
   std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
   Status s = ensure_kernels();
@@ -1242,12 +1478,15 @@ Status ZstdBatchManager::decompress_batch_device_prefix(const void *const *d_in_
   if (!count) return Status::SUCCESS;
   if (!d_in_ptrs || !d_in_sizes || !d_out_ptrs || !d_out_sizes || max_out == 0) return Status::ERROR_INVALID_PARAMETER;
   bool const prefix = d_prefix_ptrs || d_prefix_sizes;
-  if (prefix && (!d_prefix_ptrs || !d_prefix_sizes || pimpl_->mgr_dict.n)) return Status::ERROR_INVALID_PARAMETER;
+  if (prefix && (!d_prefix_ptrs || !d_prefix_sizes || pimpl_->mgr_dict.n || pimpl_->set)) return Status::ERROR_INVALID_PARAMETER;
+  if (d_dict_index && !pimpl_->set) return Status::ERROR_INVALID_PARAMETER;
   DecLayout L = DecLayout::make(count, max_out);
   if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
   u8 *base = aligned_base(temp);
   ZhDecArgs a = L.args(base);
   pimpl_->mgr_dict.fill(a);
+  std::shared_ptr<DictSetDev> const ds = pimpl_->set;
+  if (ds) ds->fill(a, d_dict_index);
   a.pre_ptrs = d_prefix_ptrs;
   a.pre_sizes = d_prefix_sizes;
   a.in_ptrs = d_in_ptrs;
@@ -1259,6 +1498,7 @@ Status ZstdBatchManager::decompress_batch_device_prefix(const void *const *d_in_
   a.statuses = d_statuses ? (u32 *)d_statuses : (u32 *)(base + L.statuses);
   a.nvcomp_codes = 1;
   if (zh::launch_decompress(a, (u32)count, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+  if (ds) return ds->note_use(stream);
   return pimpl_->mgr_dict.n ? pimpl_->mgr_dict.note_use(stream) : Status::SUCCESS;
 }
 
@@ -1274,12 +1514,15 @@ Status ZstdBatchManager::get_decompressed_sizes_async(const void *const *d_ptrs,
   if (!d_ptrs || !d_sizes || !d_out_sizes || count > 0xFFFFFFFFull) return Status::ERROR_INVALID_PARAMETER;
   ZhDecArgs a{};
   pimpl_->mgr_dict.fill(a);
+  std::shared_ptr<DictSetDev> const ds = pimpl_->set;  // a bound dictionary set: every frame's dictionary by its ID
+  if (ds) ds->fill(a, nullptr);
   a.in_ptrs = d_ptrs;
   a.in_sizes = d_sizes;
   a.out_sizes = d_out_sizes;
   a.statuses = (u32 *)d_statuses;
   a.nvcomp_codes = nvcomp_codes ? 1u : 0u;
   if (zh::launch_decompress_sizes(a, (u32)count, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
+  if (ds) return ds->note_use(stream);
   return pimpl_->mgr_dict.n ? pimpl_->mgr_dict.note_use(stream) : Status::SUCCESS;
 }
 
@@ -2032,6 +2275,21 @@ Status NvcompV5BatchManager::decompress_prefix_async(const void *const *d_compre
                                                     max_chunk, num_chunks, d_uncompressed_ptrs, d_actual_sizes, d_statuses, d_temp_storage,
                                                     temp_storage_bytes, stream);
 }
+Status NvcompV5BatchManager::compress_dicts_async(const void *const *d_uncompressed_ptrs, const size_t *d_uncompressed_sizes,
+                                                  const int32_t *d_dict_index, size_t max_chunk, size_t num_chunks,
+                                                  void *const *d_compressed_ptrs, size_t *d_compressed_sizes, int *d_statuses,
+                                                  void *d_temp_storage, size_t temp_storage_bytes, hipStream_t stream) {
+  return pimpl_->mgr.compress_batch_device_dicts(d_uncompressed_ptrs, d_uncompressed_sizes, d_dict_index, max_chunk, num_chunks,
+                                                 d_compressed_ptrs, d_compressed_sizes, d_statuses, d_temp_storage, temp_storage_bytes, stream);
+}
+Status NvcompV5BatchManager::decompress_dicts_async(const void *const *d_compressed_ptrs, const size_t *d_compressed_sizes,
+                                                    const int32_t *d_dict_index, const size_t *d_uncompressed_caps, size_t max_chunk,
+                                                    size_t num_chunks, void *const *d_uncompressed_ptrs, size_t *d_actual_sizes,
+                                                    int *d_statuses, void *d_temp_storage, size_t temp_storage_bytes, hipStream_t stream) {
+  return pimpl_->mgr.decompress_batch_device_dicts(d_compressed_ptrs, d_compressed_sizes, d_dict_index, d_uncompressed_caps, max_chunk,
+                                                   num_chunks, d_uncompressed_ptrs, d_actual_sizes, d_statuses, d_temp_storage,
+                                                   temp_storage_bytes, stream);
+}
 
 Status get_metadata_async(const void *d, size_t n, NvcompV5Metadata *m, hipStream_t) {
   if (!m) return Status::ERROR_INVALID_PARAMETER;
@@ -2433,6 +2691,7 @@ struct cuda_zstd_dict_t {
     dict->header.raw_content_size = (u32)bytes.size();
   }
 };
+struct cuda_zstd_dict_set_t { std::unique_ptr<DictionarySet> set; };
 struct nvcomp_zstd_batch_manager_t { std::unique_ptr<nvcomp_v5::NvcompV5BatchManager> mgr; };
 struct cuda_zstd_hybrid_engine_t { std::unique_ptr<HybridEngine> engine; };
 
@@ -2717,6 +2976,77 @@ int nvcomp_zstd_batched_decompress_prefix_async_v5(nvcomp_zstd_batch_manager_t *
   if (n && (!d_pre || !d_pre_sizes)) return c_err(Status::ERROR_INVALID_PARAMETER);
   return c_err(m->mgr->batch_manager().decompress_batch_device_prefix(d_in, d_in_sizes, d_pre, d_pre_sizes, d_out_caps, max_out, n, d_out,
                                                                        d_out_sizes, d_statuses, t, tb, s));
+}
+// ---- dictionary sets (DESIGN.md §2 "A batch against a set of dictionaries") ----
+int cuda_zstd_dict_set_create(const cuda_zstd_dict_t *const *dicts, size_t n, hipStream_t stream, cuda_zstd_dict_set_t **out) {
+  if (out) *out = nullptr;
+  if (!dicts || !out || n < 1 || n > ZH_DICTSET_MAX) return c_err(Status::ERROR_INVALID_PARAMETER);
+  try {
+    std::vector<const dictionary::Dictionary *> v(n);
+    for (size_t i = 0; i < n; i++) {
+      if (!dicts[i] || !dicts[i]->dict) return c_err(Status::ERROR_INVALID_PARAMETER);
+      v[i] = dicts[i]->dict.get();
+    }
+    std::unique_ptr<DictionarySet> set;
+    Status const s = DictionarySet::create(v.data(), n, stream, set);
+    if (s != Status::SUCCESS) return c_err(s);
+    auto *h = new cuda_zstd_dict_set_t;
+    h->set = std::move(set);
+    *out = h;
+    return 0;
+  } catch (...) {
+    return c_err(Status::ERROR_OUT_OF_MEMORY);
+  }
+}
+void cuda_zstd_dict_set_destroy(cuda_zstd_dict_set_t *set) { delete set; }
+size_t cuda_zstd_dict_set_count(const cuda_zstd_dict_set_t *set) { return (set && set->set) ? set->set->count() : 0; }
+int cuda_zstd_dict_set_find(const cuda_zstd_dict_set_t *set, unsigned int dict_id) { return (set && set->set) ? set->set->find(dict_id) : -1; }
+// Test hooks (tests/test_gpu_dictset.py, not product entry points): the precomputed tables of one
+// dictionary copied back -- entry `index` of a set (the batched builders), and a host buffer loaded
+// as set_dictionary loads it (the single builders, DevDict::load).  dtab: 2^15 u16, K1's packed
+// tables (written when *P != 0); prev: ZH_DEEP_PRE u32, the deep matcher's links, [0, *split)
+// written; head: 2^ZH_HASH_LOG_SHORT u32 (written when *dP != 0).  Returns 0, 1 (HIP error) or 2.
+static int copy_dict_tables(const u16 *tabs, u32 tP, const u32 *dprev, const u32 *dhead, u32 dP, u32 dsplit, u16 *dtab, u32 *P, u32 *prev, u32 *head,
+                            u32 *pdP, u32 *split) {
+  *P = tP;
+  *pdP = dP;
+  *split = dsplit;
+  size_t const tab_bytes = ((size_t(1) << ZH_HASH_LOG_LONG) + (size_t(1) << ZH_HASH_LOG_SHORT)) * 2;
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (tP && hipMemcpy(dtab, tabs, tab_bytes, hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  if (dP && dsplit && hipMemcpy(prev, dprev, (size_t)dsplit * 4, hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  if (dP && hipMemcpy(head, dhead, size_t(4) << ZH_HASH_LOG_SHORT, hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  return 0;
+}
+int zh_test_dictset_tables(const cuda_zstd_dict_set_t *set, size_t index, u16 *dtab, u32 *P, u32 *prev, u32 *head, u32 *dP, u32 *split) {
+  if (!set || !set->set || index >= set->set->count()) return 2;
+  ZhDictSetEntry const &e = set->set->impl().dev->ents[index];
+  return copy_dict_tables(e.dtab, e.dtab_P, e.dd_prev, e.dd_head, e.dd_pre, e.dd_split, dtab, P, prev, head, dP, split);
+}
+int zh_test_dict_tables(const void *buf, size_t n, u16 *dtab, u32 *P, u32 *prev, u32 *head, u32 *dP, u32 *split) {
+  if (ensure_kernels() != Status::SUCCESS) return 1;
+  DevDict d;
+  if (d.load(buf, n, 0) != Status::SUCCESS) return 2;
+  return copy_dict_tables(d.tabs, d.tabs_P, d.deep_prev, d.deep_head, d.deep_P, d.deep_split, dtab, P, prev, head, dP, split);
+}
+int nvcomp_zstd_batch_set_dictionary_set_v5(nvcomp_zstd_batch_manager_t *m, cuda_zstd_dict_set_t *set) {
+  if (!m || !m->mgr || (set && !set->set)) return c_err(Status::ERROR_INVALID_PARAMETER);
+  return c_err(m->mgr->batch_manager().set_dictionary_set(set ? set->set.get() : nullptr));
+}
+size_t nvcomp_zstd_batch_get_batched_dicts_temp_size_v5(nvcomp_zstd_batch_manager_t *m, size_t n, size_t max_chunk) {
+  return (m && m->mgr) ? m->mgr->batch_manager().get_batch_device_dicts_temp_size(n, max_chunk) : 0;
+}
+int nvcomp_zstd_batched_compress_dicts_async_v5(nvcomp_zstd_batch_manager_t *m, const void *const *d_in, const size_t *d_in_sizes,
+                                                const int32_t *d_dict_index, size_t max_chunk, size_t n, void *const *d_out,
+                                                size_t *d_out_sizes, int *d_statuses, void *t, size_t tb, hipStream_t s) {
+  if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
+  return c_err(m->mgr->compress_dicts_async(d_in, d_in_sizes, d_dict_index, max_chunk, n, d_out, d_out_sizes, d_statuses, t, tb, s));
+}
+int nvcomp_zstd_batched_decompress_dicts_async_v5(nvcomp_zstd_batch_manager_t *m, const void *const *d_in, const size_t *d_in_sizes,
+                                                  const int32_t *d_dict_index, const size_t *d_out_caps, size_t max_out, size_t n,
+                                                  void *const *d_out, size_t *d_out_sizes, int *d_statuses, void *t, size_t tb, hipStream_t s) {
+  if (!m || !m->mgr) return c_err(Status::ERROR_INVALID_PARAMETER);
+  return c_err(m->mgr->decompress_dicts_async(d_in, d_in_sizes, d_dict_index, d_out_caps, max_out, n, d_out, d_out_sizes, d_statuses, t, tb, s));
 }
 size_t nvcomp_zstd_batch_get_decompress_temp_size_v5(nvcomp_zstd_batch_manager_t *m, const size_t *sizes, size_t n) {
   return (m && m->mgr) ? m->mgr->get_decompress_temp_size(sizes, n) : 0;

@@ -29,6 +29,13 @@ struct ZhDecArgs {
   // all of it addressable; not together with dict.  A zero size or a null pointer: no prefix
   const void *const *pre_ptrs;
   const size_t *pre_sizes;
+  // a dictionary set (zh_dictset.h; null: none; not together with dict or prefixes): every frame's
+  // dictionary is resolved on the device, from its Dictionary_ID over set_ids[0, set_nids) or, where
+  // dict_index (optional, per item) is >= 0, that entry of set[0, set_count)
+  const ZhDictSetEntry *set;
+  const ZhDictSetId *set_ids;
+  const int32_t *dict_index;
+  u32 set_count, set_nids;
 };
 #define ZH_DEC_HANDOFF_BYTES 5376u  // sizeof(DecHandoff), zh_decode.hip
 
@@ -60,6 +67,11 @@ struct ZhPlanArrays {
   // one prefix per item (ZhPlanItem::pre / pre_n), or both null; prefix_sizes[i] == 0: item i has none
   const void *const *prefix_ptrs;
   const size_t *prefix_sizes;
+  // one entry of a dictionary set per item (zh_dictset.h), or null: dict_index[i] names an entry of
+  // set[0, set_count), -1 none; set_entropy: the handle's dict_entropy setting
+  const int32_t *dict_index;
+  const ZhDictSetEntry *set;
+  u32 set_count, set_entropy;
 };
 
 namespace zh {
@@ -77,6 +89,15 @@ u32 entropy_lds_bytes();
 // out = 2^15 u16, tmp32 = 2^15 u32 scratch; P = the tail length covered (0: none)
 hipError_t lz_dict_tables(const u8 *content, size_t cn, u16 *out, u32 *tmp32, u32 &P, hipStream_t stream);
 hipError_t lz_deep_dict_tables(const u8 *content, size_t cn, u8 *stg, u32 *dprev, u32 *dhead, u32 &P, u32 &split, hipStream_t stream);
+// The two builders with the dictionary as a grid dimension (a dictionary set's creation): the
+// tables of d_jobs[0, count) in one memset and three launches whatever count is, byte for byte
+// what the single builders give each dictionary.  tmp32: count x 2^15 u32, stg: count x
+// ZH_DEEP_DICT_STG bytes of scratch.  lz_dict_tables_P / lz_deep_dict_shape: the P (and split) the
+// single builders take for cn content bytes.
+u32 lz_dict_tables_P(size_t cn);
+void lz_deep_dict_shape(size_t cn, u32 &P, u32 &split);
+hipError_t lz_dict_tables_batch(const ZhDictBuildJob *d_jobs, u32 count, u32 *tmp32, hipStream_t stream);
+hipError_t lz_deep_dict_tables_batch(const ZhDictBuildJob *d_jobs, u32 count, u8 *stg, hipStream_t stream);
 // The stages of one batch: the matchers (ranges null: every block at b.level; else the class ranges
 // the rank kernel left in *b.ranges), entropy, gather, checksum.
 hipError_t launch_compress(const ZhBatch &b, hipStream_t stream);

@@ -1366,7 +1366,9 @@ __device__ __forceinline__ bool repeat_scan(const u32 *in32, u32 *E, u32 *hw, u3
   return total >= max(span >> ZH_SCAN_SHIFT, (u32)ZH_SCAN_MIN);
 }
 
-template <u32 MODE>
+// SET: the kernels of a dictionary-set batch (ws.set; zh_dictset.h) -- their own instantiations, so
+// that every other batch runs the code it ran before
+template <u32 MODE, bool SET>
 __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, ZhWorkspace ws, u32 b, u32 nblocks, u32 *s_take, Prefetch &pf, u32 wv, bool redo) {
   u8 *const smem = k1_lds();
   u8 *in = smem + OFF_IN;
@@ -1452,8 +1454,18 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
   // batch of tiles holding `pre` are inserted by the inserter waves (insert_span), and the
   // window loop starts at the window holding `pre` -- the same tables, candidates and parse as
   // inserting every history position (the oracle's order), without the history windows.
-  bool const use_dt = ws.dtab && (d.flags & ZH_F_DICT) && (d.flags & ZH_F_FIRST) && pre >= 2 * ZH_DTAB_MARGIN && d.n >= 16 &&
-                      ws.dtab_P >= pre;
+  // (a dictionary-set batch: the tables of the block's own entry, zh_dictset.h)
+  const u16 *dtab = ws.dtab;
+  u32 dtab_P = ws.dtab_P;
+  if constexpr (SET) {
+    if ((d.flags & ZH_F_DICT) && (d.flags & ZH_F_FIRST)) {
+      const ZhDictSetEntry *const e = ws.set + ws.item_ent[d.item];
+      dtab_P = e->dtab_P;
+      dtab = dtab_P ? e->dtab : nullptr;
+    }
+  }
+  bool const use_dt = dtab && (d.flags & ZH_F_DICT) && (d.flags & ZH_F_FIRST) && pre >= 2 * ZH_DTAB_MARGIN && d.n >= 16 &&
+                      dtab_P >= pre;
   // History without precomputed tables (a frame's later blocks, stream history, dictionary
   // views): only the final table over positions [0, pmin) -- the latest position per slot --
   // matters, so every wave inserts them at once (below) instead of the inserter waves walking
@@ -1473,8 +1485,8 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
   u32 const kprobe0 = a0 + ZH_PROBE_WINDOWS + 1 <= nwl && e0p <= ZH_PROBE_MAX_E0 ? a0 + ZH_PROBE_WINDOWS + 1 - wstart / ZH_WINDOW : ~0u;
   u32 next_b = 0;
   if (use_dt) {
-    u32 const delta = ws.dtab_P - pre;
-    const u32 *dt32 = (const u32 *)ws.dtab;
+    u32 const delta = dtab_P - pre;
+    const u32 *dt32 = (const u32 *)dtab;
     auto clip = [&](u32 e) { return e > delta ? e - delta : 0u; };
     for (u32 i = tid; i < (HL_SIZE + HS_SIZE) / 2; i += K1_THREADS) {
       u32 const w = dt32[i];
@@ -1869,7 +1881,7 @@ __device__ __forceinline__ u32 lz_block(const ZhBlockDesc *__restrict__ blocks, 
 // Persistent workgroups (grid = one per CU, the LDS footprint allows no second): workgroup g
 // takes blocks g, g + grid, ... and stages each block from registers loaded while the previous
 // one was processed, so the HBM latency of staging and the per-block launch gap overlap work.
-template <u32 MODE>
+template <u32 MODE, bool SET = false>
 __device__ __forceinline__ void lz_blocks(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws) {
   extern __shared__ __attribute__((aligned(16))) u8 smem_dyn[];
   u8 *const smem = k1_lds();
@@ -1889,7 +1901,7 @@ __device__ __forceinline__ void lz_blocks(const ZhBlockDesc *__restrict__ blocks
     // the next block taken, or K1_REDO (the same in every wave; readfirstlane keeps it -- and the
     // block index and descriptor fields derived from it -- in SGPRs: the function's return paths
     // join under the inserter / worker split, which the compiler takes for divergence)
-    u32 const r = (u32)__builtin_amdgcn_readfirstlane(lz_block<MODE>(blocks, ws, b, nblocks, &s_take, pf, wv, redo));
+    u32 const r = (u32)__builtin_amdgcn_readfirstlane(lz_block<MODE, SET>(blocks, ws, b, nblocks, &s_take, pf, wv, redo));
     k1_barrier();  // every wave is done with this block's LDS before the next is staged
     redo = r == K1_REDO;
     b = redo ? b : r;
@@ -1904,6 +1916,16 @@ extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_short_kernel(cons
 }
 extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_greedy_kernel(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws) {
   lz_blocks<2>(blocks, nblocks, ws);
+}
+// ... and per parse mode for a dictionary-set batch
+extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_set_kernel(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws) {
+  lz_blocks<0, true>(blocks, nblocks, ws);
+}
+extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_short_set_kernel(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws) {
+  lz_blocks<1, true>(blocks, nblocks, ws);
+}
+extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_greedy_set_kernel(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws) {
+  lz_blocks<2, true>(blocks, nblocks, ws);
 }
 // Ranged launches of a mixed-level batch: the parse's blocks are class `cls`'s slots
 // [begin, end) of the sorted layout, known only on the device (ZhClassRanges).  The block loop is
@@ -1944,11 +1966,31 @@ extern "C" __global__ void zh_dict_pack_kernel(const u32 *__restrict__ t32, u16 
   u32 const i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < HL_SIZE + HS_SIZE) out[i] = (u16)t32[i];
 }
+// The same for a group of dictionaries (a dictionary set, zh_dictset.h): blockIdx.y is the
+// dictionary, jobs[y] its tail, positions and output, t32 + y * (HL_SIZE + HS_SIZE) its scratch
+// table (zeroed by the caller).  A job with B = 0 has no tables.
+extern "C" __global__ void zh_dict_hash_batch_kernel(const ZhDictBuildJob *__restrict__ jobs, u32 *__restrict__ t32) {
+  ZhDictBuildJob const job = jobs[blockIdx.y];
+  const u8 *const tail = job.tail;
+  u32 *const t = t32 + (size_t)blockIdx.y * (HL_SIZE + HS_SIZE);
+  for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < job.B; j += gridDim.x * blockDim.x) {
+    u32 const lo = (u32)tail[j] | ((u32)tail[j + 1] << 8) | ((u32)tail[j + 2] << 16) | ((u32)tail[j + 3] << 24);
+    u32 const hi = (u32)tail[j + 4] | ((u32)tail[j + 5] << 8) | ((u32)tail[j + 6] << 16) | ((u32)tail[j + 7] << 24);
+    atomicMax(&t[hash_of<true>(lo, hi)], j + 1);
+    atomicMax(&t[HL_SIZE + hash_of<false>(lo, hi)], j + 1);
+  }
+}
+extern "C" __global__ void zh_dict_pack_batch_kernel(const ZhDictBuildJob *__restrict__ jobs, const u32 *__restrict__ t32) {
+  ZhDictBuildJob const job = jobs[blockIdx.y];
+  u32 const i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (job.B && i < HL_SIZE + HS_SIZE) job.dtab[i] = (u16)t32[(size_t)blockIdx.y * (HL_SIZE + HS_SIZE) + i];
+}
 
 namespace zh {
 hipError_t lz_init() {
   for (const void *f : {(const void *)zh_lz_kernel, (const void *)zh_lz_short_kernel, (const void *)zh_lz_greedy_kernel,
-                        (const void *)zh_lz_ranged_kernel, (const void *)zh_lz_short_ranged_kernel, (const void *)zh_lz_greedy_ranged_kernel}) {
+                        (const void *)zh_lz_ranged_kernel, (const void *)zh_lz_short_ranged_kernel, (const void *)zh_lz_greedy_ranged_kernel,
+                        (const void *)zh_lz_set_kernel, (const void *)zh_lz_short_set_kernel, (const void *)zh_lz_greedy_set_kernel}) {
     hipError_t const e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K1_LDS);
     if (e != hipSuccess) return e;
   }
@@ -1966,6 +2008,21 @@ hipError_t lz_dict_tables(const u8 *content, size_t cn, u16 *out, u32 *tmp32, u3
   hipLaunchKernelGGL(zh_dict_pack_kernel, dim3((HL_SIZE + HS_SIZE + 255) / 256), dim3(256), 0, stream, tmp32, out);
   return hipGetLastError();
 }
+// the tail length lz_dict_tables covers for cn content bytes (0: no tables)
+u32 lz_dict_tables_P(size_t cn) {
+  u32 const P = (u32)std::min(cn, (size_t)65535);
+  return P < 2 * ZH_DTAB_MARGIN ? 0u : P;
+}
+// lz_dict_tables for the `count` dictionaries of d_jobs (tail = content + cn - P, B = P -
+// ZH_DTAB_MARGIN, or B = 0) in one memset and two launches: tmp32 = count x 2^15 u32 scratch
+hipError_t lz_dict_tables_batch(const ZhDictBuildJob *d_jobs, u32 count, u32 *tmp32, hipStream_t stream) {
+  if (!count) return hipSuccess;
+  hipError_t e = hipMemsetAsync(tmp32, 0, (size_t)count * 4 * (HL_SIZE + HS_SIZE), stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(zh_dict_hash_batch_kernel, dim3((65535 - ZH_DTAB_MARGIN + 255) / 256, count), dim3(256), 0, stream, d_jobs, tmp32);
+  hipLaunchKernelGGL(zh_dict_pack_batch_kernel, dim3((HL_SIZE + HS_SIZE + 255) / 256, count), dim3(256), 0, stream, d_jobs, (const u32 *)tmp32);
+  return hipGetLastError();
+}
 // mode = ZH_K1_MODE(level)
 void lz_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 mode, hipStream_t stream) {
   // one persistent workgroup per CU of the stream's device
@@ -1974,7 +2031,8 @@ void lz_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32 mode
   else (void)hipGetDevice(&dev);
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   u32 const grid = std::min(nblocks, (u32)cus);
-  auto *const k = mode == 2 ? zh_lz_greedy_kernel : mode == 1 ? zh_lz_short_kernel : zh_lz_kernel;
+  auto *const k = ws.set ? (mode == 2 ? zh_lz_greedy_set_kernel : mode == 1 ? zh_lz_short_set_kernel : zh_lz_set_kernel)
+                         : (mode == 2 ? zh_lz_greedy_kernel : mode == 1 ? zh_lz_short_kernel : zh_lz_kernel);
   hipLaunchKernelGGL(k, dim3(grid), dim3(K1_THREADS), K1_LDS, stream, d_descs, nblocks, ws);
 }
 // The three parses of a mixed-level batch over their class ranges (ZhClassRanges, device only):

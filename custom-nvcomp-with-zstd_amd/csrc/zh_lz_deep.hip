@@ -620,6 +620,9 @@ __device__ void deep_parse_demand(const u32 *D32, const u16 *P16, const u32 *dpr
 #else
 #define DSTAMP(k) do { } while (0)
 #endif
+// SET: the kernel of a dictionary-set batch (ws.set; zh_dictset.h) -- its own instantiation, so that
+// every other batch runs the code it ran before
+template <bool SET = false>
 __device__ void deep_block(const ZhBlockDesc &d, ZhWorkspace ws, u32 b, u8 *slot, u32 depth, u32 tid) {
 #ifdef ZH_STAMPS
   u64 const dst0 = __builtin_amdgcn_s_memtime();
@@ -678,10 +681,22 @@ __device__ void deep_block(const ZhBlockDesc &d, ZhWorkspace ws, u32 b, u8 *slot
   // A dictionary frame's first block starts from the dictionary's precomputed chains (built once
   // per dictionary, zh_deep_dict_kernel): the head table after its positions [0, dd_split), whose
   // links stay in ws.dd_prev; the block links only [dd_split, lim) -- the same chains.
-  bool const use_dd = ws.dd_head && (d.flags & ZH_F_DICT) && (d.flags & ZH_F_FIRST) && pre == ws.dd_pre;
-  u32 const s0 = use_dd ? ws.dd_split : 0u;
-  const u32 *const dprev = ws.dd_prev;
-  for (u32 i = tid; i < HSIZE + 4; i += DT) head[i] = use_dd && i < HSIZE ? ws.dd_head[i] : 0u;
+  // (a dictionary-set batch: the chains of the block's own entry, zh_dictset.h)
+  const u32 *dd_head = ws.dd_head, *dd_prev = ws.dd_prev;
+  u32 dd_pre = ws.dd_pre, dd_split = ws.dd_split;
+  if constexpr (SET) {
+    if ((d.flags & ZH_F_DICT) && (d.flags & ZH_F_FIRST)) {
+      const ZhDictSetEntry *const e = ws.set + ws.item_ent[d.item];
+      dd_pre = e->dd_pre;
+      dd_split = e->dd_split;
+      dd_prev = e->dd_prev;
+      dd_head = dd_pre ? e->dd_head : nullptr;
+    }
+  }
+  bool const use_dd = dd_head && (d.flags & ZH_F_DICT) && (d.flags & ZH_F_FIRST) && pre == dd_pre;
+  u32 const s0 = use_dd ? dd_split : 0u;
+  const u32 *const dprev = dd_prev;
+  for (u32 i = tid; i < HSIZE + 4; i += DT) head[i] = use_dd && i < HSIZE ? dd_head[i] : 0u;
   if (wg_any(!same, &misc[0], tid) == false && nb >= 2) {
     if (tid == 0) { meta[0] = 0; meta[1] = 0; meta[2] = 1; }
     return;
@@ -820,6 +835,25 @@ extern "C" __global__ __launch_bounds__(DT) void zh_lz_deep_kernel(const ZhBlock
     __syncthreads();  // the slot and LDS are free for the next block
   }
 }
+// The same over a dictionary-set batch: every first block's chains are its own entry's
+extern "C" __global__ __launch_bounds__(DT) void zh_lz_deep_set_kernel(const ZhBlockDesc *__restrict__ blocks, u32 nblocks, ZhWorkspace ws,
+                                                                      u8 *scratch, u32 depth) {
+  extern __shared__ __attribute__((aligned(16))) u8 smem[];
+  u32 *misc = (u32 *)(smem + L_MISC);
+  u32 const tid = threadIdx.x;
+  u8 *const slot = scratch + (size_t)blockIdx.x * SLOT_BYTES;
+  if (tid == 0) misc[0] = 0;
+  for (;;) {
+    if (tid == 0) misc[1] = atomicAdd(ws.ctr, 1u);
+    __syncthreads();
+    u32 const b = misc[1];
+    __syncthreads();
+    if (b >= nblocks) break;
+    ZhBlockDesc const d = blocks[b];
+    if (d.n) deep_block<true>(d, ws, b, slot, depth, tid);
+    __syncthreads();  // the slot and LDS are free for the next block
+  }
+}
 
 // The deep classes of a mixed-level batch (zh_plan.hip zh_rank_kernel): block slots [begin of class
 // ZH_CLASS_DEEP0, end of the last deep class) of the sorted layout, the deepest search first, taken
@@ -874,6 +908,24 @@ extern "C" __global__ __launch_bounds__(DT) void zh_deep_dict_kernel(const u8 *_
   deep_chains((const u32 *)stg, dprev, head, (u16 *)(smem + L_TM), 0, split, tid);
   for (u32 i = tid; i < HSIZE; i += DT) dhead[i] = head[i];
 }
+// The same for a group of dictionaries (a dictionary set, zh_dictset.h): workgroup g builds
+// jobs[g]'s chains in its own staging area stg + g * stride.  A job with dP = 0 has none.
+extern "C" __global__ __launch_bounds__(DT) void zh_deep_dict_batch_kernel(const ZhDictBuildJob *__restrict__ jobs, u8 *stg_all, u32 stride) {
+  extern __shared__ __attribute__((aligned(16))) u8 smem[];
+  ZhDictBuildJob const job = jobs[blockIdx.x];
+  u32 const P = job.dP;
+  if (!P) return;
+  const u8 *const tail = job.dtail;
+  u8 *const stg = stg_all + (size_t)blockIdx.x * stride;
+  u32 *head = (u32 *)(smem + L_HEAD);
+  u32 const tid = threadIdx.x;
+  for (u32 i = tid; i < P + 64; i += DT) stg[i] = i < P ? tail[i] : (u8)0;
+  for (u32 i = tid; i < HSIZE + 4; i += DT) head[i] = 0;
+  __syncthreads();
+  u32 const split = (P > ZH_HASH_READ ? P - ZH_HASH_READ : 0u) & ~3u;
+  deep_chains((const u32 *)stg, job.dprev, head, (u16 *)(smem + L_TM), 0, split, tid);
+  for (u32 i = tid; i < HSIZE; i += DT) job.dhead[i] = head[i];
+}
 
 namespace zh {
 // chains of a dictionary's last min(cn, ZH_DEEP_PRE) content bytes: dprev u32[ZH_DEEP_PRE],
@@ -890,8 +942,20 @@ hipError_t lz_deep_dict_tables(const u8 *content, size_t cn, u8 *stg, u32 *dprev
   return hipGetLastError();
 }
 
+// the staged bytes and split lz_deep_dict_tables takes for cn content bytes (0, 0: no chains)
+void lz_deep_dict_shape(size_t cn, u32 &P, u32 &split) { deep_dict_split(cn, P, split); }
+// lz_deep_dict_tables for the `count` dictionaries of d_jobs (dtail = content + cn - dP, or dP = 0)
+// in one launch: stg = count x ZH_DEEP_DICT_STG bytes of staging
+hipError_t lz_deep_dict_tables_batch(const ZhDictBuildJob *d_jobs, u32 count, u8 *stg, hipStream_t stream) {
+  if (!count) return hipSuccess;
+  hipLaunchKernelGGL(zh_deep_dict_batch_kernel, dim3(count), dim3(DT), DEEP_LDS, stream, d_jobs, stg, (u32)ZH_DEEP_DICT_STG);
+  return hipGetLastError();
+}
+
 hipError_t lz_deep_init() {
   hipError_t e = hipFuncSetAttribute((const void *)zh_lz_deep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_lz_deep_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_deep_dict_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_deep_dict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_lz_deep_ranged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   return e;
@@ -919,7 +983,8 @@ static hipError_t deep_launch_depth(const ZhBlockDesc *d_descs, u32 nblocks, ZhW
   // one persistent workgroup per CU, at most one per scratch slot of the caller's workspace
   if (!ws.deep_slots || !ws.deep_nslots) return hipErrorInvalidValue;
   u32 const grid = std::min(std::min(nblocks, (u32)cus), ws.deep_nslots);
-  hipLaunchKernelGGL(zh_lz_deep_kernel, dim3(grid), dim3(DT), DEEP_LDS, stream, d_descs, nblocks, ws, ws.deep_slots, depth);
+  hipLaunchKernelGGL(ws.set ? zh_lz_deep_set_kernel : zh_lz_deep_kernel, dim3(grid), dim3(DT), DEEP_LDS, stream, d_descs, nblocks, ws, ws.deep_slots,
+                     depth);
   return hipGetLastError();
 }
 

@@ -6,6 +6,8 @@
 //                  src/cuda_zstd_nvcomp.cpp:319-437); zh_plan_levels_kernel: one level per item.
 //                  With ZhPlanArrays::prefix_ptrs / prefix_sizes every item brings its own prefix
 //                  (the bytes in front of it, a raw-content dictionary): ZhPlanItem::pre / pre_n.
+//                  With ZhPlanArrays::dict_index every item names an entry of a dictionary set
+//                  (zh_dictset.h): that entry's content, Dictionary_ID and frame flags.
 // zh_gather_kernel: concatenates the staged blocks of multi-block frames (the
 //                  reference assembles them on the host with blocking copies,
 //                  src/cuda_zstd_manager.cu:2765-3027).
@@ -38,6 +40,7 @@ void entropy_launch(const ZhBlockDesc *d_descs, u32 nblocks, ZhWorkspace ws, u32
 __device__ inline void zh_plan_block(const ZhBatch &B, const ZhPlanArrays &a, u32 i, u32 k, u32 b, int level, bool valid) {
   ZhPlanItem it{(const u8 *)a.in_ptrs[i], a.in_sizes[i], i, level, (u8 *)a.out_ptrs[i]};
   if (a.prefix_sizes) { it.pre = (const u8 *)a.prefix_ptrs[i]; it.pre_n = a.prefix_sizes[i]; }  // the item's own prefix
+  if (a.dict_index) zh_dictset_plan_item(it, a.set, a.set_count, a.dict_index[i], a.set_entropy != 0);  // its entry of the set
   ZhBlockDesc d = zh_block_desc(B.plan, it, k, b);
   if (!valid) d.n = 0;
   B.descs[b] = d;

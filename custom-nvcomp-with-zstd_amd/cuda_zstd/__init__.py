@@ -90,6 +90,14 @@ def lib() -> ctypes.CDLL:
             "nvcomp_zstd_batch_get_batched_prefix_temp_size_v5": (sz, [vp, sz, sz]),
             "nvcomp_zstd_batched_compress_prefix_async_v5": (i, [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
             "nvcomp_zstd_batched_decompress_prefix_async_v5": (i, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
+            "cuda_zstd_dict_set_create": (i, [pvp, sz, vp, pvp]),
+            "cuda_zstd_dict_set_destroy": (None, [vp]),
+            "cuda_zstd_dict_set_count": (sz, [vp]),
+            "cuda_zstd_dict_set_find": (i, [vp, ctypes.c_uint]),
+            "nvcomp_zstd_batch_set_dictionary_set_v5": (i, [vp, vp]),
+            "nvcomp_zstd_batch_get_batched_dicts_temp_size_v5": (sz, [vp, sz, sz]),
+            "nvcomp_zstd_batched_compress_dicts_async_v5": (i, [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
+            "nvcomp_zstd_batched_decompress_dicts_async_v5": (i, [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
             "cuda_zstd_stream_batch_create": (vp, [i, sz, sz]),
             "cuda_zstd_stream_batch_destroy": (None, [vp]),
             "cuda_zstd_stream_batch_max_compressed_chunk_size": (sz, [vp]),
@@ -572,6 +580,45 @@ class Dictionary:
             pass
 
 
+class DictionarySet:
+    """A set of dictionaries on the device (cuda_zstd_dict_set_create): 1 .. 4,096 Dictionary
+    handles, raw content or formatted, for batches whose chunks use different dictionaries.  The
+    bytes are copied (the handles may be closed afterwards) and the set is immutable.  Two
+    dictionaries with the same non-zero Dictionary_ID raise; raw-content entries (ID 0) are
+    reachable by index only.  Bind it with BatchedCompressor / BatchedDecompressor
+    .set_dictionary_set, or use compress_batch_dicts / decompress_batch_dicts."""
+
+    def __init__(self, dictionaries: Sequence["Dictionary"], stream=None):
+        ds = list(dictionaries)
+        n = len(ds)
+        self._h = None
+        h = ctypes.c_void_p()
+        rc = lib().cuda_zstd_dict_set_create((ctypes.c_void_p * max(n, 1))(*[d._h for d in ds]), n, _stream_ptr(stream), ctypes.byref(h))
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_dict_set_create")
+        self._h = h.value
+
+    def __len__(self) -> int:
+        return lib().cuda_zstd_dict_set_count(self._h)
+
+    def find(self, dict_id: int) -> int:
+        """Entry index of a non-zero Dictionary_ID, or -1."""
+        return lib().cuda_zstd_dict_set_find(self._h, dict_id)
+
+    def close(self):
+        """Waits for the stream-ordered calls that read the set, then frees it (a handle it is still
+        bound to keeps the device memory)."""
+        if self._h:
+            lib().cuda_zstd_dict_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+
 class BatchedDecompressor:
     """Stream-ordered batched GPU decompression over device arrays
     (nvcomp_zstd_batched_decompress_async_v5).  Used by bench.py --decompress."""
@@ -618,6 +665,33 @@ class BatchedDecompressor:
             temp.data_ptr(), temp.numel(), _stream_ptr(stream))
         if rc:
             raise ZstdError(rc, "nvcomp_zstd_batched_decompress_prefix_async_v5")
+
+    def set_dictionary(self, d: "Dictionary"):
+        rc = lib().nvcomp_zstd_batch_set_dictionary_v5(self._h, d._h)
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batch_set_dictionary_v5")
+
+    def set_dictionary_set(self, s: "DictionarySet"):
+        """Bind a dictionary set (None clears): decompress_async and get_sizes_async then resolve every
+        frame's dictionary from its Dictionary_ID on the device; decompress_dicts_async also takes
+        entry indices.  Not together with set_dictionary."""
+        rc = lib().nvcomp_zstd_batch_set_dictionary_set_v5(self._h, s._h if s is not None else None)
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batch_set_dictionary_set_v5")
+
+    def decompress_dicts_async(self, d_in_ptrs, d_in_sizes, d_dict_index, d_out_caps, max_out, d_out_ptrs, d_out_sizes, d_status, temp,
+                               stream=None):
+        """decompress_async against the bound set (nvcomp_zstd_batched_decompress_dicts_async_v5):
+        d_dict_index is an int32 device tensor or None; -1 (or None) resolves a frame by its
+        Dictionary_ID, an index >= 0 names the entry (a raw-content entry's frames carry no ID).
+        Same workspace as decompress_async."""
+        n = d_in_ptrs.numel()
+        rc = lib().nvcomp_zstd_batched_decompress_dicts_async_v5(
+            self._h, d_in_ptrs.data_ptr(), d_in_sizes.data_ptr(), d_dict_index.data_ptr() if d_dict_index is not None else None,
+            d_out_caps.data_ptr() if d_out_caps is not None else None, max_out, n, d_out_ptrs.data_ptr(), d_out_sizes.data_ptr(),
+            d_status.data_ptr() if d_status is not None else None, temp.data_ptr(), temp.numel(), _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batched_decompress_dicts_async_v5")
 
     def get_sizes_async(self, d_in_ptrs, d_in_sizes, d_out_sizes, d_status, stream=None):
         """The decompressed size of every buffer, on the device
@@ -717,6 +791,30 @@ class BatchedCompressor:
             d_status.data_ptr() if d_status is not None else None, temp.data_ptr(), temp.numel(), _stream_ptr(stream))
         if rc:
             raise ZstdError(rc, "nvcomp_zstd_batched_compress_prefix_async_v5")
+
+    def set_dictionary_set(self, s: "DictionarySet"):
+        """Bind a dictionary set for compress_dicts_async (None clears).  Not together with
+        set_dictionary."""
+        rc = lib().nvcomp_zstd_batch_set_dictionary_set_v5(self._h, s._h if s is not None else None)
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batch_set_dictionary_set_v5")
+
+    def temp_size_dicts(self, num_chunks: int, max_chunk: int) -> int:
+        """Workspace of compress_dicts_async (nvcomp_zstd_batch_get_batched_dicts_temp_size_v5)."""
+        return lib().nvcomp_zstd_batch_get_batched_dicts_temp_size_v5(self._h, num_chunks, max_chunk)
+
+    def compress_dicts_async(self, d_in_ptrs, d_in_sizes, d_dict_index, max_chunk, d_out_ptrs, d_out_sizes, d_status, temp, stream=None):
+        """compress_async with one entry of the bound set per chunk
+        (nvcomp_zstd_batched_compress_dicts_async_v5): d_dict_index is an int32 device tensor, read
+        on the device; -1 = no dictionary.  Frame i is what a handle with that one dictionary set
+        writes for chunk i."""
+        n = d_in_ptrs.numel()
+        rc = lib().nvcomp_zstd_batched_compress_dicts_async_v5(
+            self._h, d_in_ptrs.data_ptr(), d_in_sizes.data_ptr(), d_dict_index.data_ptr() if d_dict_index is not None else None, max_chunk, n,
+            d_out_ptrs.data_ptr(), d_out_sizes.data_ptr(), d_status.data_ptr() if d_status is not None else None, temp.data_ptr(),
+            temp.numel(), _stream_ptr(stream))
+        if rc:
+            raise ZstdError(rc, "nvcomp_zstd_batched_compress_dicts_async_v5")
 
     @staticmethod
     def seekable_max_size(num_frames: int, max_compressed_chunk: int, checksums: bool = False) -> int:
@@ -1322,6 +1420,94 @@ def decompress_batch_prefix(frames: Sequence, prefixes: Sequence, capacities=Non
     for k in range(n):
         if got_status[k] != OK:
             raise ZstdError(got_status[k], f"decompress_batch_prefix item {k}")
+        f = out[k * slot : k * slot + got_sizes[k]]
+        res.append(_host_bytes(f) if host else f)
+    return res
+
+
+def compress_batch_dicts(chunks: Sequence, dict_set: "DictionarySet", indices: Sequence[int], level: int = 3, checksum: bool = False,
+                         dict_entropy: bool = False, stream=None) -> List:
+    """Compress chunk i against entry indices[i] of dict_set (-1: no dictionary) in one
+    stream-ordered call (nvcomp_zstd_batched_compress_dicts_async_v5) -> the frames in input order,
+    each what a handle with that one dictionary set writes.  Hosts (bytes, numpy) or CUDA tensors
+    in; device tensors in -> device tensors out, hosts in -> bytes out.  Waits once, for the sizes."""
+    torch = _torch()
+    n = len(chunks)
+    if n == 0:
+        return []
+    if len(indices) != n:
+        raise ZstdError(INVALID, "one entry index (or -1) per chunk")
+    host = _is_host(chunks[0])
+    s = stream if stream is not None else torch.cuda.current_stream()
+    ins = [(_to_device(c) if _is_host(c) else c).contiguous().view(torch.uint8) for c in chunks]
+    sizes = [t.numel() for t in ins]
+    max_chunk = max(max(sizes), 1)
+    bc = BatchedCompressor(level, checksum=checksum, dict_entropy=dict_entropy)
+    bc.set_dictionary_set(dict_set)
+    slot = ((bc.max_out(max_chunk) + 255) // 256) * 256
+    with torch.cuda.stream(s):
+        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
+        table = torch.tensor([[t.data_ptr() if t.numel() else 0 for t in ins], sizes, [out.data_ptr() + k * slot for k in range(n)]],
+                             dtype=torch.int64)
+        d_table = table.pin_memory().to("cuda", non_blocking=True)
+        d_index = torch.tensor([int(i) for i in indices], dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
+        if s != torch.cuda.current_stream():
+            for t in ins:
+                t.record_stream(s)
+        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
+        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
+        temp = torch.empty(bc.temp_size_dicts(n, max_chunk), dtype=torch.uint8, device="cuda")
+        bc.compress_dicts_async(d_table[0], d_table[1], d_index, max_chunk, d_table[2], d_sizes, d_status, temp, s)
+        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
+    bc.close()
+    res = []
+    for k in range(n):
+        if got_status[k] != OK:
+            raise ZstdError(got_status[k], f"compress_batch_dicts item {k}")
+        f = out[k * slot : k * slot + got_sizes[k]]
+        res.append(_host_bytes(f) if host else f)
+    return res
+
+
+def decompress_batch_dicts(frames: Sequence, dict_set: "DictionarySet", indices: Sequence[int] = None, capacities=None, stream=None) -> List:
+    """Decode frame i against dict_set in one stream-ordered call
+    (nvcomp_zstd_batched_decompress_dicts_async_v5): every frame's dictionary is resolved on the
+    device from its Dictionary_ID, or is entry indices[i] where that is >= 0 (the way to name a
+    raw-content entry).  capacities: one output capacity per frame (default: the frame header's
+    content size).  Hosts in -> bytes out, CUDA tensors in -> tensors."""
+    torch = _torch()
+    n = len(frames)
+    if n == 0:
+        return []
+    if indices is not None and len(indices) != n:
+        raise ZstdError(INVALID, "one entry index (or -1) per frame")
+    host = _is_host(frames[0])
+    s = stream if stream is not None else torch.cuda.current_stream()
+    ins = [(_to_device(c) if _is_host(c) else c).contiguous().view(torch.uint8) for c in frames]
+    caps = [int(c) for c in capacities] if capacities is not None else [_frame_size(t) for t in ins]
+    max_out = max(max(caps), 1)
+    slot = ((max_out + 255) // 256) * 256
+    bd = BatchedDecompressor()
+    bd.set_dictionary_set(dict_set)
+    with torch.cuda.stream(s):
+        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
+        table = torch.tensor([[t.data_ptr() if t.numel() else 0 for t in ins], [t.numel() for t in ins],
+                              [out.data_ptr() + k * slot for k in range(n)], caps], dtype=torch.int64)
+        d_table = table.pin_memory().to("cuda", non_blocking=True)
+        d_index = None if indices is None else torch.tensor([int(i) for i in indices], dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
+        if s != torch.cuda.current_stream():
+            for t in ins:
+                t.record_stream(s)
+        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
+        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
+        temp = torch.empty(bd.temp_size(n, max_out), dtype=torch.uint8, device="cuda")
+        bd.decompress_dicts_async(d_table[0], d_table[1], d_index, d_table[3], max_out, d_table[2], d_sizes, d_status, temp, s)
+        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
+    bd.close()
+    res = []
+    for k in range(n):
+        if got_status[k] != OK:
+            raise ZstdError(got_status[k], f"decompress_batch_dicts item {k}")
         f = out[k * slot : k * slot + got_sizes[k]]
         res.append(_host_bytes(f) if host else f)
     return res

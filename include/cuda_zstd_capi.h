@@ -231,6 +231,63 @@ int nvcomp_zstd_batched_decompress_prefix_async_v5(nvcomp_zstd_batch_manager_t *
                                                    size_t *d_actual_sizes, int *d_statuses, void *d_temp_storage,
                                                    size_t temp_storage_bytes, hipStream_t stream);
 
+/* A set of dictionaries on the device, for batches whose chunks use different dictionaries (one per
+ * table, tenant, column or schema version).  Created from n = 1 .. 4,096 handles (raw content or
+ * formatted, 256 B .. 128 KiB, as nvcomp_zstd_batch_set_dictionary_v5 accepts); the bytes are
+ * copied, so the handles may be destroyed afterwards, and the set is immutable.  One device
+ * allocation holds, per entry, what set_dictionary builds for one dictionary (the matchers' tables
+ * of its content; for a formatted dictionary the encoder's view of its entropy section): about
+ * 0.5 MiB per 64 KiB dictionary.  Two entries with the same non-zero Dictionary_ID are refused with
+ * 2; raw-content entries (ID 0) are allowed and reachable by index only.  create blocks until the
+ * tables are built (a constant number of launches per 64 dictionaries); destroy waits for the
+ * stream-ordered calls that read the set.  find: the entry index of a non-zero Dictionary_ID, or -1. */
+typedef struct cuda_zstd_dict_set_t cuda_zstd_dict_set_t;
+int cuda_zstd_dict_set_create(const cuda_zstd_dict_t *const *dicts, size_t n, hipStream_t stream, cuda_zstd_dict_set_t **out);
+void cuda_zstd_dict_set_destroy(cuda_zstd_dict_set_t *set);
+size_t cuda_zstd_dict_set_count(const cuda_zstd_dict_set_t *set);
+int cuda_zstd_dict_set_find(const cuda_zstd_dict_set_t *set, unsigned int dict_id);
+/* Binds a set to the batch handle (null clears) for the two entries below and for
+ * nvcomp_zstd_batched_decompress_async_v5 / nvcomp_zstd_batched_get_decompress_size_async_v5, which
+ * then resolve every frame's dictionary from its Dictionary_ID on the device.  The handle keeps the
+ * set's device memory alive while bound.  Not together with nvcomp_zstd_batch_set_dictionary_v5:
+ * either call while the other is in place returns 2. */
+int nvcomp_zstd_batch_set_dictionary_set_v5(nvcomp_zstd_batch_manager_t *mgr, cuda_zstd_dict_set_t *set);
+/* The batched call with one dictionary per chunk: d_dict_index[i] (a DEVICE int32 array, read only
+ * on the device) names chunk i's entry of the bound set, -1 none.  Stream-ordered like
+ * nvcomp_zstd_batched_compress_async_v5: nothing is allocated, synchronised or copied to the host,
+ * and the launches are the same whatever the set's size or the mix.
+ * Frame i is byte-identical to what a handle at the same level, checksum and dict_entropy setting
+ * with that one dictionary set writes for chunk i through nvcomp_zstd_batched_compress_async_v5: it
+ * carries the entry's Dictionary_ID, its first block starts from the entry's precomputed tables and,
+ * with dict_entropy, may use the entry's entropy section.  Index -1 gives the frame of a handle
+ * without a dictionary.  An index below -1 or past the set gives that chunk size 0 and status 2 and
+ * leaves its output untouched; neighbours are unaffected.
+ * Returns 2 for a handle without a bound set, a null required array (d_statuses is optional),
+ * max_uncompressed_chunk_bytes == 0 or enable_ldm; 7 for a workspace below
+ * nvcomp_zstd_batch_get_batched_dicts_temp_size_v5 (nothing is launched); num_chunks == 0 succeeds.
+ * Out of scope: a set together with per-chunk levels, with a per-chunk prefix, with long-distance
+ * matching, and the streaming managers.
+ * The workspace is nvcomp_zstd_batch_get_batched_prefix_temp_size_v5's. */
+size_t nvcomp_zstd_batch_get_batched_dicts_temp_size_v5(nvcomp_zstd_batch_manager_t *mgr, size_t num_chunks,
+                                                        size_t max_uncompressed_chunk_bytes);
+int nvcomp_zstd_batched_compress_dicts_async_v5(nvcomp_zstd_batch_manager_t *mgr, const void *const *d_uncompressed_ptrs,
+                                                const size_t *d_uncompressed_sizes, const int32_t *d_dict_index,
+                                                size_t max_uncompressed_chunk_bytes, size_t num_chunks, void *const *d_compressed_ptrs,
+                                                size_t *d_compressed_sizes, int *d_statuses, void *d_temp_storage,
+                                                size_t temp_storage_bytes, hipStream_t stream);
+/* nvcomp_zstd_batched_decompress_async_v5 with an entry index per buffer (a DEVICE int32 array, or
+ * null): -1 or null resolves every frame by its Dictionary_ID, an index >= 0 uses that entry (how a
+ * raw-content entry, whose frames carry no ID, is named), an index outside the set gives the buffer
+ * status 2.  Per frame: a non-zero ID that is not in the set, or that differs from the named
+ * entry's, gets the dictionary-wrong code; a frame without an ID and without an index is decoded
+ * without a dictionary; with an index the entry's content precedes it and a formatted entry's
+ * tables and repcodes seed it.  Same workspace as the plain entry; 2 without a bound set. */
+int nvcomp_zstd_batched_decompress_dicts_async_v5(nvcomp_zstd_batch_manager_t *mgr, const void *const *d_compressed_ptrs,
+                                                  const size_t *d_compressed_sizes, const int32_t *d_dict_index,
+                                                  const size_t *d_uncompressed_caps, size_t max_uncompressed_chunk_bytes, size_t num_chunks,
+                                                  void *const *d_uncompressed_ptrs, size_t *d_actual_sizes, int *d_statuses,
+                                                  void *d_temp_storage, size_t temp_storage_bytes, hipStream_t stream);
+
 /* Many streams in one call: num_streams streams, each with a device-resident window of its last
  * 64 KiB, compressed or decoded one chunk per stream per call.  create allocates everything the
  * object owns (the compress and decode workspaces, one pair of 64 KiB window buffers per stream and

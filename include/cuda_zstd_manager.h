@@ -48,6 +48,31 @@ class ZstdManager {
   virtual Status free_tables(hipStream_t stream = 0) { (void)stream; return Status::SUCCESS; }
 };
 
+// A set of dictionaries on the device, for batches whose chunks use different dictionaries (one per
+// table, tenant, column or schema version): ZstdBatchManager::set_dictionary_set binds it, and
+// compress_batch_device_dicts takes one entry index per chunk.  Created from 1 .. 4,096
+// dictionaries (raw content or formatted, MIN_DICT_SIZE .. MAX_DICT_SIZE bytes each, host or device
+// memory; the bytes are copied, so the sources may go away), each with everything set_dictionary
+// builds for one dictionary -- the matchers' tables of its content and, for a formatted dictionary,
+// the encoder's view of its entropy section -- in one device allocation of about 0.5 MiB per 64 KiB
+// dictionary.  Immutable.  Two entries with the same non-zero Dictionary_ID are refused
+// (ERROR_INVALID_PARAMETER); raw-content entries (ID 0) are reachable by index only.  Destruction
+// waits for the stream-ordered calls that read the set.
+class DictionarySet {
+ public:
+  static Status create(const dictionary::Dictionary *const *dicts, size_t count, hipStream_t stream, std::unique_ptr<DictionarySet> &out);
+  ~DictionarySet();
+  size_t count() const;
+  // entry index of a non-zero Dictionary_ID, or -1
+  int find(u32 dictionary_id) const;
+  class Impl;
+  const Impl &impl() const { return *pimpl_; }
+
+ private:
+  DictionarySet();
+  std::unique_ptr<Impl> pimpl_;
+};
+
 class ZstdBatchManager : public ZstdManager {
  public:
   ZstdBatchManager();
@@ -140,6 +165,29 @@ class ZstdBatchManager : public ZstdManager {
   // its workspace: that of a manager with a dictionary at this level (the 32 KiB split with staging
   // and gather above 32 KiB below level 5, the deep matcher's slots from level 5 on)
   size_t get_batch_device_prefix_temp_size(size_t count, size_t max_chunk_bytes) const;
+  // A batch against a set of dictionaries.  set_dictionary_set binds a set (null: none) for the
+  // calls below and for the decoding entries; the manager keeps the set's device memory alive while
+  // bound.  Not together with set_dictionary: either one while the other is in place is
+  // ERROR_INVALID_PARAMETER.
+  Status set_dictionary_set(const DictionarySet *set);
+  // compress_batch_device with one entry of the bound set per chunk: d_dict_index[i] (a device int32
+  // array, read on the device) names chunk i's dictionary, -1 none.  Frame i is byte-identical to
+  // what a manager at this level, checksum and dict_entropy setting with that one dictionary set
+  // writes for chunk i through compress_batch_device (it carries the entry's Dictionary_ID, starts
+  // from the entry's precomputed tables and, with dict_entropy, may use its entropy section); -1
+  // gives the frame of a manager without a dictionary.  An index below -1 or past the set gives that
+  // chunk size 0 and status ERROR_INVALID_PARAMETER and leaves its output untouched.  Stream-ordered:
+  // no allocation, no synchronisation, no copy to the host, and the same launches whatever the set's
+  // size or the mix.  ERROR_INVALID_PARAMETER without a bound set, for a null array, max_chunk_bytes
+  // == 0 or enable_ldm; ERROR_BUFFER_TOO_SMALL for a workspace below get_batch_device_dicts_temp_size
+  // (nothing is launched); count == 0 succeeds.
+  // Not covered: a set together with per-chunk levels, with a per-chunk prefix, with long-distance
+  // matching, and the streaming managers.
+  Status compress_batch_device_dicts(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int32_t *d_dict_index, size_t max_chunk_bytes,
+                                     size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp_workspace,
+                                     size_t temp_size, hipStream_t stream);
+  // its workspace: get_batch_device_prefix_temp_size's (the index array is read where it is)
+  size_t get_batch_device_dicts_temp_size(size_t count, size_t max_chunk_bytes) const;
 
   // Stream-ordered batched decompression over device arrays (no host sync; GPU decoder,
   // any RFC 8878 frames); used by nvcomp_zstd_batched_decompress_async_v5.
@@ -159,6 +207,19 @@ class ZstdBatchManager : public ZstdManager {
                                         const size_t *d_prefix_sizes, const size_t *d_out_caps, size_t max_uncompressed_chunk_bytes,
                                         size_t count, void *const *d_out_ptrs, size_t *d_out_sizes, int *d_statuses, void *temp_workspace,
                                         size_t temp_size, hipStream_t stream);
+  // Decoding against the bound dictionary set.  With a set bound, decompress_batch_device and
+  // get_decompressed_sizes_async resolve every frame's dictionary on the device from its
+  // Dictionary_ID (per frame: a buffer may hold frames naming different dictionaries); this entry
+  // adds d_dict_index, a device int32 array or null: -1 (or null) resolves by ID, an index >= 0 uses
+  // that entry -- the way to name a raw-content entry, whose frames carry no ID -- and an index
+  // outside the set makes the buffer ERROR_INVALID_PARAMETER.  A non-zero ID that is not in the set,
+  // or that differs from the named entry's, is answered with the dictionary-wrong code; a frame
+  // without an ID and without an index is decoded without a dictionary; with an index the entry's
+  // content precedes it, and a formatted entry's tables and repcodes seed it.  Same workspace as
+  // decompress_batch_device; ERROR_INVALID_PARAMETER without a bound set.
+  Status decompress_batch_device_dicts(const void *const *d_in_ptrs, const size_t *d_in_sizes, const int32_t *d_dict_index,
+                                       const size_t *d_out_caps, size_t max_uncompressed_chunk_bytes, size_t count, void *const *d_out_ptrs,
+                                       size_t *d_out_sizes, int *d_statuses, void *temp_workspace, size_t temp_size, hipStream_t stream);
   // The decompressed size of every buffer, computed on the device (nvCOMP's
   // nvcompBatchedZstdGetDecompressSizeAsync): all arrays are device arrays, one launch, no
   // workspace, no allocation, no synchronisation.  d_out_sizes[i] = the bytes all frames of buffer i

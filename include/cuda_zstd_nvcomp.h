@@ -61,6 +61,18 @@ class NvcompV5BatchManager {
                                  const size_t *d_prefix_sizes, const size_t *d_uncompressed_caps, size_t max_uncompressed_chunk_bytes,
                                  size_t num_chunks, void *const *d_uncompressed_ptrs, size_t *d_actual_sizes, int *d_statuses,
                                  void *d_temp_storage, size_t temp_storage_bytes, hipStream_t stream = 0);
+  // One entry of a dictionary set per chunk (batch_manager().set_dictionary_set binds the set;
+  // ZstdBatchManager::compress_batch_device_dicts / decompress_batch_device_dicts): device arrays
+  // only, stream-ordered, nothing is synchronised or allocated; workspaces of
+  // batch_manager().get_batch_device_dicts_temp_size and get_batch_device_decompress_temp_size.
+  Status compress_dicts_async(const void *const *d_uncompressed_ptrs, const size_t *d_uncompressed_sizes, const int32_t *d_dict_index,
+                              size_t max_uncompressed_chunk_bytes, size_t num_chunks, void *const *d_compressed_ptrs,
+                              size_t *d_compressed_sizes, int *d_statuses, void *d_temp_storage, size_t temp_storage_bytes,
+                              hipStream_t stream = 0);
+  Status decompress_dicts_async(const void *const *d_compressed_ptrs, const size_t *d_compressed_sizes, const int32_t *d_dict_index,
+                                const size_t *d_uncompressed_caps, size_t max_uncompressed_chunk_bytes, size_t num_chunks,
+                                void *const *d_uncompressed_ptrs, size_t *d_actual_sizes, int *d_statuses, void *d_temp_storage,
+                                size_t temp_storage_bytes, hipStream_t stream = 0);
   const CompressionStats &get_stats() const;
   ZstdBatchManager &batch_manager();
 
