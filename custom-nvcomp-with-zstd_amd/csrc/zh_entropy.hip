@@ -1937,6 +1937,150 @@ extern "C" void zh_hst_host(u32 *out6) {
 }
 #endif
 
+// ---- test hooks (tests/test_gpu_tables.py, not product entry points) ------------------------------
+// K2's table builders alone, one wave per case and one case per workgroup, on the LDS sub-layout
+// entropy_block gives them (the OFF_* offsets of one wave's copy).  Nothing is cleared first: a
+// case starts on whatever an earlier workgroup left in LDS, as a block does in K2.
+constexpr u32 ZH_TT_NC = 256;  // bytes of NCount / Huffman header copied back per case
+
+// FSE: par = {maxSV, total, tableLog, useLowProbCount}; count[64] as K2's code histogram holds it.
+// Out: the per-lane norm fse_normalize_wave returns, the norm[] it stored, the NCount bytes and
+// size, and (NCount size != 0) st[0, 2^tableLog) and the symbol transforms (dNb, dFS) of [0, maxSV].
+extern "C" __global__ __launch_bounds__(64) void zh_test_fse_table_kernel(const u32 *__restrict__ count, const u32 *__restrict__ par,
+                                                                           s32 *__restrict__ norm_lane, s16 *__restrict__ norm_st,
+                                                                           u8 *__restrict__ nc, u32 *__restrict__ nc_size, u16 *__restrict__ st_out,
+                                                                           u32 *__restrict__ sym_out) {
+  __shared__ __attribute__((aligned(16))) u8 smem[K2_WAVE_LDS];
+  u32 const lane = lane_id(), b = blockIdx.x;
+  u32 *hist = (u32 *)(smem + OFF_HIST);
+  u8 *hbuf = smem + OFF_HBUF;
+  u16 *st = (u16 *)(smem + OFF_ST_LL);
+  FseSym *sy = (FseSym *)(smem + OFF_SYM);
+  u8 *tsym = smem + OFF_TSYM;
+  s16 *norm = (s16 *)(smem + OFF_NORM);
+  SerialScratch *scr = (SerialScratch *)(smem + OFF_SCR);
+  u32 const maxSV = par[4 * b], total = par[4 * b + 1], tableLog = par[4 * b + 2], low = par[4 * b + 3];
+  hist[lane] = count[64 * b + lane];
+  wave_sync();
+  u32 const c = lane <= maxSV ? hist[lane] : 0u;
+  int const nv = fse_normalize_wave(norm, tableLog, c, total, maxSV, low != 0, lane, scr->cumul);
+  u32 const hs = fse_write_ncount_wave(hbuf, nv, maxSV, tableLog, lane);
+  wave_sync();
+  norm_lane[64 * b + lane] = nv;
+  if (lane <= maxSV) norm_st[64 * b + lane] = norm[lane];
+  if (lane == 0) nc_size[b] = hs;
+  for (u32 i = lane; i < hs && i < ZH_TT_NC; i += 64) nc[ZH_TT_NC * b + i] = hbuf[i];
+  if (hs) {
+    fse_build_ctable_par(st, sy, tsym, norm, maxSV, tableLog, scr);
+    wave_sync();
+    for (u32 i = lane; i < (1u << tableLog); i += 64) st_out[512 * b + i] = st[i];
+    if (lane <= maxSV) { sym_out[128 * b + 2 * lane] = sy[lane].dNb; sym_out[128 * b + 2 * lane + 1] = (u32)sy[lane].dFS; }
+  }
+}
+
+// Huffman: par = {maxSV, maxNbBits}; count[256] as K2's literal histogram holds it.  Out: the
+// huffLog huf_build_ctable_par returns, hnb[256], hval[0, maxSV] (0 above: the build writes no
+// value there), and (huffLog != 0) huf_write_ctable_wave's header bytes and size.
+extern "C" __global__ __launch_bounds__(64) void zh_test_huf_table_kernel(const u32 *__restrict__ count, const u32 *__restrict__ par,
+                                                                           u32 *__restrict__ huff_log, u8 *__restrict__ hnb_out,
+                                                                           u16 *__restrict__ hval_out, u8 *__restrict__ hdr, u32 *__restrict__ hdr_size) {
+  __shared__ __attribute__((aligned(16))) u8 smem[K2_WAVE_LDS];
+  u32 const lane = lane_id(), b = blockIdx.x;
+  u32 *hist = (u32 *)(smem + OFF_HIST);
+  u16 *hval = (u16 *)(smem + OFF_HVAL);
+  u8 *hnb = smem + OFF_HNB;
+  u8 *hbuf = smem + OFF_HBUF;
+  HufNode *nodes = (HufNode *)(smem + OFF_NODES);
+  u8 *wts = smem + OFF_WTS;
+  SerialScratch *scr = (SerialScratch *)(smem + OFF_SCR);
+  u32 const maxSV = par[2 * b], maxNbBits = par[2 * b + 1];
+  for (u32 i = lane; i < 256; i += 64) hist[i] = count[256 * b + i];
+  wave_sync();
+  u32 const hl = huf_build_ctable_par(nodes, hval, hnb, hist, maxSV, maxNbBits, scr);
+  u32 const hsz = hl ? huf_write_ctable_wave(hbuf, wts, hnb, maxSV, hl, (u16 *)(smem + OFF_W_ST), (FseSym *)(smem + OFF_W_SYM), smem + OFF_W_TSYM,
+                                             (s16 *)(smem + OFF_W_NORM), scr)
+                     : 0;
+  wave_sync();
+  if (lane == 0) { huff_log[b] = hl; hdr_size[b] = hsz; }
+  if (hl) {
+    for (u32 i = lane; i < 256; i += 64) { hnb_out[256 * b + i] = hnb[i]; hval_out[256 * b + i] = i <= maxSV ? hval[i] : (u16)0; }
+    for (u32 i = lane; i < hsz && i < ZH_TT_NC; i += 64) hdr[ZH_TT_NC * b + i] = hbuf[i];
+  }
+}
+
+namespace {
+// device copies of the host arrays in `in`, device buffers for `out` (filled with 0xA5), one launch
+// by `launch`, and the results copied back.  0, or 1 on a HIP error.
+struct TtBuf { const void *host_in; void *host_out; size_t bytes; void *dev; };
+template <typename F>
+int tt_run(TtBuf *bufs, u32 nbufs, F launch) {
+  int rc = 0;
+  for (u32 i = 0; i < nbufs && !rc; i++) {
+    if (hipMalloc(&bufs[i].dev, bufs[i].bytes) != hipSuccess) { bufs[i].dev = nullptr; rc = 1; }
+    else if (bufs[i].host_in) rc = hipMemcpy(bufs[i].dev, bufs[i].host_in, bufs[i].bytes, hipMemcpyHostToDevice) != hipSuccess;
+    else rc = hipMemset(bufs[i].dev, 0xA5, bufs[i].bytes) != hipSuccess;
+  }
+  if (!rc) {
+    launch();
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = 1;
+  }
+  for (u32 i = 0; i < nbufs; i++) {
+    if (!rc && bufs[i].host_out && hipMemcpy(bufs[i].host_out, bufs[i].dev, bufs[i].bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = 1;
+    if (bufs[i].dev) (void)hipFree(bufs[i].dev);
+  }
+  return rc;
+}
+}  // namespace
+
+// n cases, case i at count[64 i], par[4 i]; per case norm_lane[64], norm_st[64], nc[256], nc_size,
+// st[512], sym[128] (dNb, dFS pairs).  What a case does not write keeps the fill byte 0xA5.
+// Returns 0, 1 (HIP error) or 2 (arguments outside the builders' domain: nothing is launched).
+extern "C" int zh_test_fse_table(const u32 *count, const u32 *par, u32 n, s32 *norm_lane, s16 *norm_st, u8 *nc, u32 *nc_size, u16 *st, u32 *sym) {
+  if (!n) return 0;
+  for (u32 i = 0; i < n; i++) {
+    u32 const maxSV = par[4 * i], total = par[4 * i + 1], tableLog = par[4 * i + 2];
+    u64 sum = 0;
+    if (maxSV < 1 || maxSV > 63 || tableLog < 5 || tableLog > 9) return 2;  // the tables hold 512 states, the lanes 64 symbols
+    for (u32 s = 0; s <= maxSV; s++) {
+      sum += count[64 * i + s];
+      if (count[64 * i + s] == total) return 2;  // one symbol only: K2 takes RLE_Mode before it normalises
+    }
+    if (total < 2 || total > (1u << 17) || sum != total) return 2;
+    // FSE_normalizeCount's own argument check (FSE_minTableLog): below it the redistribution's
+    // unsigned arithmetic wraps, and K2 never asks for such a table
+    u32 const minSrc = 32u - (u32)__builtin_clz(total), minSym = 33u - (u32)__builtin_clz(maxSV);
+    if (tableLog < (minSrc < minSym ? minSrc : minSym)) return 2;
+  }
+  TtBuf b[] = {{count, nullptr, 256ull * n, nullptr},   {par, nullptr, 16ull * n, nullptr},     {nullptr, norm_lane, 256ull * n, nullptr},
+               {nullptr, norm_st, 128ull * n, nullptr}, {nullptr, nc, (size_t)ZH_TT_NC * n, nullptr}, {nullptr, nc_size, 4ull * n, nullptr},
+               {nullptr, st, 1024ull * n, nullptr},     {nullptr, sym, 512ull * n, nullptr}};
+  return tt_run(b, 8, [&] {
+    hipLaunchKernelGGL(zh_test_fse_table_kernel, dim3(n), dim3(64), 0, nullptr, (const u32 *)b[0].dev, (const u32 *)b[1].dev, (s32 *)b[2].dev,
+                       (s16 *)b[3].dev, (u8 *)b[4].dev, (u32 *)b[5].dev, (u16 *)b[6].dev, (u32 *)b[7].dev);
+  });
+}
+
+// n cases, case i at count[256 i], par[2 i]; per case huff_log, hnb[256], hval[256], hdr[256], hdr_size.
+extern "C" int zh_test_huf_table(const u32 *count, const u32 *par, u32 n, u32 *huff_log, u8 *hnb, u16 *hval, u8 *hdr, u32 *hdr_size) {
+  if (!n) return 0;
+  for (u32 i = 0; i < n; i++) {
+    u32 const maxSV = par[2 * i], maxNbBits = par[2 * i + 1];
+    u32 used = 0;
+    u64 sum = 0;
+    if (maxSV > 255 || maxNbBits < 1 || maxNbBits > 12) return 2;
+    for (u32 s = 0; s <= maxSV; s++) { used += count[256 * i + s] != 0; sum += count[256 * i + s]; }
+    // a tree needs two symbols, a code of maxNbBits bits room for all of them; K2's blocks hold <= 128 KiB of literals
+    if (used < 2 || (maxNbBits < 8 && used > (1u << maxNbBits)) || sum > (1u << 17)) return 2;
+  }
+  TtBuf b[] = {{count, nullptr, 1024ull * n, nullptr}, {par, nullptr, 8ull * n, nullptr},   {nullptr, huff_log, 4ull * n, nullptr},
+               {nullptr, hnb, 256ull * n, nullptr},    {nullptr, hval, 512ull * n, nullptr}, {nullptr, hdr, (size_t)ZH_TT_NC * n, nullptr},
+               {nullptr, hdr_size, 4ull * n, nullptr}};
+  return tt_run(b, 7, [&] {
+    hipLaunchKernelGGL(zh_test_huf_table_kernel, dim3(n), dim3(64), 0, nullptr, (const u32 *)b[0].dev, (const u32 *)b[1].dev, (u32 *)b[2].dev,
+                       (u8 *)b[3].dev, (u16 *)b[4].dev, (u8 *)b[5].dev, (u32 *)b[6].dev);
+  });
+}
+
 namespace zh {
 hipError_t entropy_init() {
   hipError_t e = hipFuncSetAttribute((const void *)zh_entropy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K2_LDS);

@@ -161,6 +161,46 @@ def error_string(code: int) -> str:
     return lib().cuda_zstd_get_error_string(code).decode()
 
 
+def _test_fse_table(count, par):
+    """Test hook (tests/test_gpu_tables.py): K2's FSE table builders alone, one wave per case.
+    count: uint32 (n, 64); par: uint32 (n, 4) rows of maxSV, total, tableLog, useLowProbCount.
+    Returns numpy arrays (norm per lane (n, 64), norm as stored (n, 64), NCount bytes (n, 256),
+    NCount sizes (n), states (n, 512), symbol transforms (n, 64, 2) of dNb, dFS); what a case does
+    not write keeps the fill byte 0xA5."""
+    import numpy as np
+
+    count, par = np.ascontiguousarray(count, np.uint32), np.ascontiguousarray(par, np.uint32)
+    n = len(par)
+    assert count.shape == (n, 64) and par.shape == (n, 4)
+    out = [np.zeros((n, 64), np.int32), np.zeros((n, 64), np.int16), np.zeros((n, 256), np.uint8), np.zeros(n, np.uint32),
+           np.zeros((n, 512), np.uint16), np.zeros((n, 64, 2), np.uint32)]
+    f = lib().zh_test_fse_table
+    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_uint32] + [ctypes.c_void_p] * 6
+    rc = f(count.ctypes.data, par.ctypes.data, n, *[a.ctypes.data for a in out])
+    if rc:
+        raise RuntimeError(f"zh_test_fse_table returned {rc}")
+    return out
+
+
+def _test_huf_table(count, par):
+    """Test hook: K2's Huffman table builders alone, one wave per case.  count: uint32 (n, 256);
+    par: uint32 (n, 2) rows of maxSV, maxNbBits.  Returns numpy arrays (huffLog (n), code lengths
+    (n, 256), code values (n, 256), header bytes (n, 256), header sizes (n))."""
+    import numpy as np
+
+    count, par = np.ascontiguousarray(count, np.uint32), np.ascontiguousarray(par, np.uint32)
+    n = len(par)
+    assert count.shape == (n, 256) and par.shape == (n, 2)
+    out = [np.zeros(n, np.uint32), np.zeros((n, 256), np.uint8), np.zeros((n, 256), np.uint16), np.zeros((n, 256), np.uint8),
+           np.zeros(n, np.uint32)]
+    f = lib().zh_test_huf_table
+    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_uint32] + [ctypes.c_void_p] * 5
+    rc = f(count.ctypes.data, par.ctypes.data, n, *[a.ctypes.data for a in out])
+    if rc:
+        raise RuntimeError(f"zh_test_huf_table returned {rc}")
+    return out
+
+
 def _torch():
     import torch
 

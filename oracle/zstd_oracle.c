@@ -101,6 +101,36 @@ static size_t bw_close(bitw_t *b) {
 }
 
 /* ------------------------------------------------------------------------ */
+/* Branch trace of the table builders (test infrastructure): one counter per  */
+/* named site, per thread; counting changes no output.  T_H_LARGEST_BITS      */
+/* holds a value (the deepest code length before the depth limit), not a count */
+/* ------------------------------------------------------------------------ */
+#define ORC_TRACE_SITES(X)                                                                          \
+  X(N_CALL) X(N_LOW) X(N_EQ_LOWTHR) X(N_EQ_LOWTHR1) X(N_RTB_UP) X(N_RTB_UP1) X(N_RTB_UP2) X(N_RTB_UP3)  \
+  X(N_RTB_UP4) X(N_RTB_UP5) X(N_RTB_UP6) X(N_RTB_UP7) X(N_RTB_DOWN) X(N_RTB_DOWN1) X(N_RTB_DOWN2)       \
+  X(N_RTB_DOWN3) X(N_RTB_DOWN4) X(N_RTB_DOWN5) X(N_RTB_DOWN6) X(N_RTB_DOWN7) X(N_TIE_LARGEST)           \
+  X(N_LARGEST_AT0) X(N_LARGEST_AT_MAXSV) X(N_M2) X(N_M2_EXACT) X(N_LARGEST_ONE_LESS) X(N_STILL_POS)     \
+  X(N_STILL_ZERO) X(N_STILL_NEG) X(M2_SECOND_PASS) X(M2_SECOND_PASS_TAKEN) X(M2_TODIST0) X(M2_ALLDIST) \
+  X(M2_ALLDIST_TIE) X(M2_TOTAL0) X(M2_TOTAL0_WRAP) X(M2_RSTEP) X(M2_WEIGHT0) X(NC_CALL) X(NC_RUN24)     \
+  X(NC_RUN3) X(NC_RUN_END) X(NC_FLUSH_RUN) X(NC_FLUSH_COUNT) X(NC_GE_THRESHOLD) X(NC_SHORT)             \
+  X(NC_REM1_EARLY) X(NC_FAIL) X(H_CALL) X(H_LIMIT) X(H_LARGEST_BITS) X(H_HIGHPOS_CONT) X(H_LOWPOS_BREAK) \
+  X(H_COUNT_BREAK) X(H_WALKUP) X(H_FILL_LOWER) X(H_RANKLAST0) X(H_RANK_EMPTIED) X(H_REPAY_NOSYM)        \
+  X(H_REPAY_SYM) X(H_TIE_LEAF_NODE) X(H_FAIL) X(SEQ_M2_LL) X(SEQ_M2_OF) X(SEQ_M2_ML) X(WEIGHTS_M2)
+#define ORC_TRACE_ENUM(n) T_##n,
+enum { ORC_TRACE_SITES(ORC_TRACE_ENUM) ORC_TRACE_COUNT };
+#define ORC_TRACE_NAME(n) #n,
+static const char *const orc_trace_names[ORC_TRACE_COUNT] = {ORC_TRACE_SITES(ORC_TRACE_NAME)};
+static _Thread_local u32 orc_trace[ORC_TRACE_COUNT];
+#define TR(site) (orc_trace[T_##site]++)
+void orc_trace_reset(void) { memset(orc_trace, 0, sizeof(orc_trace)); }
+/* copies min(cap, number of sites) counters of the calling thread; returns the number of sites */
+u32 orc_trace_read(u32 *out, u32 cap) {
+  for (u32 i = 0; i < cap && i < ORC_TRACE_COUNT; i++) out[i] = orc_trace[i];
+  return ORC_TRACE_COUNT;
+}
+const char *orc_trace_name(u32 site) { return site < ORC_TRACE_COUNT ? orc_trace_names[site] : 0; }
+
+/* ------------------------------------------------------------------------ */
 /* FSE (libzstd v1.4.9 fse_compress.c restated)                              */
 /* ------------------------------------------------------------------------ */
 #define FSE_MIN_TABLELOG 5
@@ -138,23 +168,31 @@ static int fse_normalize_m2(s16 *norm, u32 tableLog, const u32 *count, size_t to
     norm[s] = NOT_YET;
   }
   toDistribute = (1u << tableLog) - distributed;
-  if (toDistribute == 0) return 0;
+  if (toDistribute == 0) { TR(M2_TODIST0); return 0; }
   if ((total / toDistribute) > lowOne) {
+    TR(M2_SECOND_PASS);
     lowOne = (u32)((total * 3) / (toDistribute * 2));
     for (u32 s = 0; s <= maxSV; s++)
-      if (norm[s] == NOT_YET && count[s] <= lowOne) { norm[s] = 1; distributed++; total -= count[s]; }
+      if (norm[s] == NOT_YET && count[s] <= lowOne) { TR(M2_SECOND_PASS_TAKEN); norm[s] = 1; distributed++; total -= count[s]; }
     toDistribute = (1u << tableLog) - distributed;
   }
   if (distributed == maxSV + 1) {
     u32 maxV = 0, maxC = 0;
+    TR(M2_ALLDIST);
     for (u32 s = 0; s <= maxSV; s++) if (count[s] > maxC) { maxV = s; maxC = count[s]; }
+    for (u32 s = maxV + 1; s <= maxSV; s++) if (count[s] == maxC) { TR(M2_ALLDIST_TIE); break; }
     norm[maxV] += (s16)toDistribute;
     return 0;
   }
   if (total == 0) {
-    for (u32 s = 0; toDistribute > 0; s = (s + 1) % (maxSV + 1)) if (norm[s] > 0) { toDistribute--; norm[s]++; }
+    TR(M2_TOTAL0);
+    for (u32 s = 0; toDistribute > 0; s = (s + 1) % (maxSV + 1)) {
+      if (norm[s] > 0) { toDistribute--; norm[s]++; }
+      if (toDistribute > 0 && s == maxSV) TR(M2_TOTAL0_WRAP);
+    }
     return 0;
   }
+  TR(M2_RSTEP);
   {
     u64 const vStepLog = 62 - tableLog;
     u64 const mid = (1ull << (vStepLog - 1)) - 1;
@@ -166,7 +204,7 @@ static int fse_normalize_m2(s16 *norm, u32 tableLog, const u32 *count, size_t to
         u32 const sStart = (u32)(tmpTotal >> vStepLog);
         u32 const sEnd = (u32)(end >> vStepLog);
         u32 const weight = sEnd - sStart;
-        if (weight < 1) return -1;
+        if (weight < 1) { TR(M2_WEIGHT0); return -1; }
         norm[s] = (s16)weight;
         tmpTotal = end;
       }
@@ -189,22 +227,37 @@ int orc_fse_normalize(s16 *norm, u32 tableLog, const u32 *count, size_t total, u
   u32 largest = 0;
   s16 largestP = 0;
   u32 lowThreshold = (u32)(total >> tableLog);
+  TR(N_CALL);
   for (u32 s = 0; s <= maxSV; s++) {
     if (count[s] == total) return 0;
     if (count[s] == 0) { norm[s] = 0; continue; }
-    if (count[s] <= lowThreshold) { norm[s] = lowProbCount; stillToDistribute--; }
+    if (count[s] == lowThreshold) TR(N_EQ_LOWTHR);
+    if (count[s] == lowThreshold + 1) TR(N_EQ_LOWTHR1);
+    if (count[s] <= lowThreshold) { TR(N_LOW); norm[s] = lowProbCount; stillToDistribute--; }
     else {
       s16 proba = (s16)((count[s] * step) >> scale);
       if (proba < 8) {
         u64 restToBeat = vStep * rtbTable[proba];
-        proba += (count[s] * step) - ((u64)proba << scale) > restToBeat;
+        int const up = (count[s] * step) - ((u64)proba << scale) > restToBeat;
+        orc_trace[(up ? T_N_RTB_UP : T_N_RTB_DOWN) + proba]++; /* the eight sites of each side are consecutive */
+        proba += up;
       }
       if (proba > largestP) { largestP = proba; largest = s; }
       norm[s] = proba;
       stillToDistribute -= proba;
     }
   }
+  for (u32 s = largest + 1; largestP > 0 && s <= maxSV; s++)
+    if (count[s] > lowThreshold && norm[s] == largestP) { TR(N_TIE_LARGEST); break; } /* the first one won */
+  if (largestP > 0 && largest == 0) TR(N_LARGEST_AT0);
+  if (largestP > 0 && largest == maxSV) TR(N_LARGEST_AT_MAXSV);
+  if (stillToDistribute > 0) TR(N_STILL_POS);
+  else if (stillToDistribute == 0) TR(N_STILL_ZERO);
+  else TR(N_STILL_NEG);
+  if (-stillToDistribute == (norm[largest] >> 1)) TR(N_M2_EXACT);
+  if (-stillToDistribute == (norm[largest] >> 1) - 1) TR(N_LARGEST_ONE_LESS);
   if (-stillToDistribute >= (norm[largest] >> 1)) {
+    TR(N_M2);
     if (fse_normalize_m2(norm, tableLog, count, total, maxSV, lowProbCount)) return -1;
   } else norm[largest] += (s16)stillToDistribute;
   return (int)tableLog;
@@ -222,6 +275,7 @@ size_t orc_fse_write_ncount(u8 *out, size_t cap, const s16 *norm, u32 maxSV, u32
   int previousIs0 = 0;
   bitStream += (tableLog - FSE_MIN_TABLELOG) << bitCount;
   bitCount += 4;
+  TR(NC_CALL);
 #define NC_FLUSH16()                                   \
   do {                                                 \
     if (out + 2 > oend) return 0;                      \
@@ -232,30 +286,32 @@ size_t orc_fse_write_ncount(u8 *out, size_t cap, const s16 *norm, u32 maxSV, u32
     if (previousIs0) {
       u32 start = symbol;
       while (symbol < alphabetSize && !norm[symbol]) symbol++;
-      if (symbol == alphabetSize) break;
-      while (symbol >= start + 24) { start += 24; bitStream += 0xFFFFu << bitCount; NC_FLUSH16(); }
-      while (symbol >= start + 3) { start += 3; bitStream += 3u << bitCount; bitCount += 2; }
+      if (symbol == alphabetSize) { TR(NC_RUN_END); break; }
+      while (symbol >= start + 24) { TR(NC_RUN24); start += 24; bitStream += 0xFFFFu << bitCount; NC_FLUSH16(); }
+      while (symbol >= start + 3) { TR(NC_RUN3); start += 3; bitStream += 3u << bitCount; bitCount += 2; }
       bitStream += (symbol - start) << bitCount;
       bitCount += 2;
-      if (bitCount > 16) { NC_FLUSH16(); bitCount -= 16; }
+      if (bitCount > 16) { TR(NC_FLUSH_RUN); NC_FLUSH16(); bitCount -= 16; }
     }
     {
       int count = norm[symbol++];
       int const max = (2 * threshold - 1) - remaining;
       remaining -= count < 0 ? -count : count;
       count++;
-      if (count >= threshold) count += max;
+      if (count >= threshold) { TR(NC_GE_THRESHOLD); count += max; }
       bitStream += (u32)count << bitCount;
       bitCount += nbBits;
       bitCount -= (count < max);
+      if (count < max) TR(NC_SHORT);
       previousIs0 = (count == 1);
-      if (remaining < 1) return 0;
+      if (remaining < 1) { TR(NC_FAIL); return 0; }
       while (remaining < threshold) { nbBits--; threshold >>= 1; }
     }
-    if (bitCount > 16) { NC_FLUSH16(); bitCount -= 16; }
+    if (bitCount > 16) { TR(NC_FLUSH_COUNT); NC_FLUSH16(); bitCount -= 16; }
   }
 #undef NC_FLUSH16
-  if (remaining != 1) return 0;
+  if (remaining == 1 && symbol < alphabetSize) TR(NC_REM1_EARLY);
+  if (remaining != 1) { TR(NC_FAIL); return 0; }
   if (out + 2 > oend) return 0;
   out[0] = (u8)bitStream;
   out[1] = (u8)(bitStream >> 8);
@@ -338,7 +394,9 @@ typedef struct { u32 count; u16 parent; u8 byte; u8 nbBits; } huf_node_t;
 
 static u32 huf_set_max_height(huf_node_t *huffNode, u32 lastNonNull, u32 maxNbBits) {
   u32 const largestBits = huffNode[lastNonNull].nbBits;
+  orc_trace[T_H_LARGEST_BITS] = largestBits;
   if (largestBits <= maxNbBits) return largestBits;
+  TR(H_LIMIT);
   {
     int totalCost = 0;
     u32 const baseCost = 1u << (largestBits - maxNbBits);
@@ -367,32 +425,34 @@ static u32 huf_set_max_height(huf_node_t *huffNode, u32 lastNonNull, u32 maxNbBi
         for (; nBitsToDecrease > 1; nBitsToDecrease--) {
           u32 const highPos = rankLast[nBitsToDecrease];
           u32 const lowPos = rankLast[nBitsToDecrease - 1];
-          if (highPos == noSymbol) continue;
-          if (lowPos == noSymbol) break;
+          if (highPos == noSymbol) { TR(H_HIGHPOS_CONT); continue; }
+          if (lowPos == noSymbol) { TR(H_LOWPOS_BREAK); break; }
           {
             u32 const highTotal = huffNode[highPos].count;
             u32 const lowTotal = 2 * huffNode[lowPos].count;
-            if (highTotal <= lowTotal) break;
+            if (highTotal <= lowTotal) { TR(H_COUNT_BREAK); break; }
           }
         }
-        while ((nBitsToDecrease <= HUF_TABLELOG_MAX) && (rankLast[nBitsToDecrease] == noSymbol)) nBitsToDecrease++;
+        while ((nBitsToDecrease <= HUF_TABLELOG_MAX) && (rankLast[nBitsToDecrease] == noSymbol)) { TR(H_WALKUP); nBitsToDecrease++; }
         totalCost -= 1 << (nBitsToDecrease - 1);
-        if (rankLast[nBitsToDecrease - 1] == noSymbol) rankLast[nBitsToDecrease - 1] = rankLast[nBitsToDecrease];
+        if (rankLast[nBitsToDecrease - 1] == noSymbol) { TR(H_FILL_LOWER); rankLast[nBitsToDecrease - 1] = rankLast[nBitsToDecrease]; }
         huffNode[rankLast[nBitsToDecrease]].nbBits++;
-        if (rankLast[nBitsToDecrease] == 0) rankLast[nBitsToDecrease] = noSymbol;
+        if (rankLast[nBitsToDecrease] == 0) { TR(H_RANKLAST0); rankLast[nBitsToDecrease] = noSymbol; }
         else {
           rankLast[nBitsToDecrease]--;
-          if (huffNode[rankLast[nBitsToDecrease]].nbBits != maxNbBits - nBitsToDecrease) rankLast[nBitsToDecrease] = noSymbol;
+          if (huffNode[rankLast[nBitsToDecrease]].nbBits != maxNbBits - nBitsToDecrease) { TR(H_RANK_EMPTIED); rankLast[nBitsToDecrease] = noSymbol; }
         }
       }
       while (totalCost < 0) {
         if (rankLast[1] == noSymbol) {
+          TR(H_REPAY_NOSYM);
           while (huffNode[n].nbBits == maxNbBits) n--;
           huffNode[n + 1].nbBits--;
           rankLast[1] = (u32)(n + 1);
           totalCost++;
           continue;
         }
+        TR(H_REPAY_SYM);
         huffNode[rankLast[1] + 1].nbBits--;
         rankLast[1]++;
         totalCost++;
@@ -425,6 +485,7 @@ u32 orc_huf_build_ctable(huf_celt_t *tree, const u32 *count, u32 maxSV, u32 maxN
   int const STARTNODE = 256;
   int nonNullRank, lowS, lowN, nodeNb = STARTNODE, n, nodeRoot;
   if (maxNbBits == 0) maxNbBits = HUF_TABLELOG_DEFAULT;
+  TR(H_CALL);
   memset(huffNode0, 0, sizeof(huffNode0));
   huf_sort(huffNode, count, maxSV);
   nonNullRank = (int)maxSV;
@@ -436,6 +497,7 @@ u32 orc_huf_build_ctable(huf_celt_t *tree, const u32 *count, u32 maxSV, u32 maxN
   for (n = nodeNb; n <= nodeRoot; n++) huffNode[n].count = 1u << 30;
   huffNode0[0].count = 1u << 31;
   while (nodeNb <= nodeRoot) {
+    if (lowS >= 0 && lowN < nodeNb && huffNode[lowS].count == huffNode[lowN].count) TR(H_TIE_LEAF_NODE); /* the internal node goes first */
     int const n1 = (huffNode[lowS].count < huffNode[lowN].count) ? lowS-- : lowN++;
     int const n2 = (huffNode[lowS].count < huffNode[lowN].count) ? lowS-- : lowN++;
     huffNode[nodeNb].count = huffNode[n1].count + huffNode[n2].count;
@@ -446,7 +508,7 @@ u32 orc_huf_build_ctable(huf_celt_t *tree, const u32 *count, u32 maxSV, u32 maxN
   for (n = nodeRoot - 1; n >= STARTNODE; n--) huffNode[n].nbBits = huffNode[huffNode[n].parent].nbBits + 1;
   for (n = 0; n <= nonNullRank; n++) huffNode[n].nbBits = huffNode[huffNode[n].parent].nbBits + 1;
   maxNbBits = huf_set_max_height(huffNode, (u32)nonNullRank, maxNbBits);
-  if (maxNbBits > HUF_TABLELOG_MAX) return 0;
+  if (maxNbBits > HUF_TABLELOG_MAX) { TR(H_FAIL); return 0; }
   {
     u16 nbPerRank[HUF_TABLELOG_MAX + 1] = {0}, valPerRank[HUF_TABLELOG_MAX + 1] = {0};
     int const alphabetSize = (int)(maxSV + 1);
@@ -503,7 +565,10 @@ static size_t huf_compress_weights(u8 *dst, size_t cap, const u8 *w, size_t wtSi
   }
   {
     u32 tableLog = orc_fse_optimal_table_log(6, wtSize, maxSV);
-    if (orc_fse_normalize(norm, tableLog, count, wtSize, maxSV, 0) < 0) return 0;
+    u32 const m2_before = orc_trace[T_N_M2];
+    int const nr = orc_fse_normalize(norm, tableLog, count, wtSize, maxSV, 0);
+    if (orc_trace[T_N_M2] != m2_before) TR(WEIGHTS_M2);
+    if (nr < 0) return 0;
     size_t h = orc_fse_write_ncount(op, cap, norm, maxSV, tableLog);
     if (!h) return 0;
     op += h;
@@ -703,7 +768,9 @@ static size_t encode_sequences_section(u8 *dst, size_t cap, const u32 *llv, cons
     for (u32 s = 0; s <= max; s++) if (count[s] > mostFrequent) mostFrequent = count[s];
     int defaultAllowed = (t == 1) ? (max <= 28) : 1;
     types[t] = select_encoding_type(count, max, mostFrequent, nbSeq, defLogs[t], defaultAllowed);
+    u32 const m2_before = orc_trace[T_N_M2];
     size_t h = build_ctable(op, (size_t)(oend - op), cts[t], fseLogs[t], types[t], count, max, codes[t], nbSeq, defNorms[t], defLogs[t], defMax[t]);
+    if (orc_trace[T_N_M2] != m2_before) orc_trace[T_SEQ_M2_LL + t]++; /* which table's normalisation took m2: LL, OF, ML */
     if (h == (size_t)-1) { free(llC); free(mlC); free(ofC); return (size_t)-1; }
     op += h;
   }

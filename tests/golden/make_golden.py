@@ -144,6 +144,44 @@ def block_cases():
     return out
 
 
+def table_cases_directed():
+    """libzstd's FSE_normalizeCount / FSE_writeNCount and HUF_buildCTable / HUF_writeCTable on the
+    directed table-builder cases of tests/zh_table_cases.py (found with the oracle's branch trace):
+    pins the oracle on the branches the GPU hooks are compared against.  FSE cases carry their
+    counts; Huffman cases are rebuilt from their generator and pinned by the counts' digest.
+    Only what libzstd accepts is stored."""
+    import hashlib
+
+    import zh_table_cases as C
+    fse, huf = [], []
+    for c in C.fse_directed():
+        norm = np.zeros(256, np.int16)
+        cnt = np.ascontiguousarray(c.count, np.uint32)
+        r = z.FSE_normalizeCount(norm.ctypes.data_as(vp), ctypes.c_uint(c.tablelog), cnt.ctypes.data_as(vp), ctypes.c_size_t(c.total),
+                                 ctypes.c_uint(c.maxsv), ctypes.c_uint(c.low))
+        if is_err(r) or r == 0:
+            continue
+        hdr = np.zeros(512, np.uint8)
+        h = z.FSE_writeNCount(hdr.ctypes.data_as(vp), ctypes.c_size_t(512), norm.ctypes.data_as(vp), ctypes.c_uint(c.maxsv), ctypes.c_uint(c.tablelog))
+        if is_err(h):
+            continue
+        fse.append({"name": c.name, "counts": c.count[: c.maxsv + 1].tolist(), "maxsv": c.maxsv, "tablelog": c.tablelog, "lowprob": c.low,
+                    "norm": norm[: c.maxsv + 1].tolist(), "ncount": bytes(hdr[:h]).hex()})
+    for c in C.huf_directed():
+        ct = np.zeros(257 * 4, np.uint8)  # HUF_CElt {u16 val; u8 nbBits; pad}
+        cnt = np.ascontiguousarray(c.count, np.uint32)
+        r = z.HUF_buildCTable(ct.ctypes.data_as(vp), cnt.ctypes.data_as(vp), ctypes.c_uint(c.maxsv), ctypes.c_uint(c.maxbits))
+        if is_err(r):
+            continue
+        elts = ct.view(np.uint16).reshape(-1, 2)
+        hdr = np.zeros(512, np.uint8)
+        h = z.HUF_writeCTable(hdr.ctypes.data_as(vp), ctypes.c_size_t(512), ct.ctypes.data_as(vp), ctypes.c_uint(c.maxsv), ctypes.c_uint(r))
+        huf.append({"name": c.name, "counts_sha256": hashlib.sha256(cnt.astype("<u4").tobytes()).hexdigest(), "maxsv": c.maxsv,
+                    "maxbits": c.maxbits, "huflog": int(r), "nbits": (elts[: c.maxsv + 1, 1] & 0xFF).astype(np.uint8).tobytes().hex(),
+                    "val": elts[: c.maxsv + 1, 0].astype("<u2").tobytes().hex(), "header": bytes(hdr[:h]).hex() if not is_err(h) else None})
+    return fse, huf
+
+
 def main():
     ver = int(z.ZSTD_versionNumber())
     only = sys.argv[1:]  # e.g. "blocks": regenerate only the entropy-block fixtures (they follow the LZ parameters)
@@ -153,6 +191,14 @@ def main():
         json.dump({"libzstd_version": ver, "cases": huf_cases()}, open(os.path.join(HERE, "huf_ctable.json"), "w"))
     if not only or "blocks" in only:
         json.dump({"libzstd_version": ver, "cases": block_cases()}, open(os.path.join(HERE, "entropy_blocks.json"), "w"))
+    if not only or "tables" in only:
+        fse, huf = table_cases_directed()
+        sep = (",", ":")
+        json.dump({"libzstd_version": ver, "cases": fse}, open(os.path.join(HERE, "fse_tables_directed.json"), "w"), separators=sep)
+        json.dump({"libzstd_version": ver, "cases": huf}, open(os.path.join(HERE, "huf_tables_directed.json"), "w"), separators=sep)
+    if only and "tables" in only and len(only) == 1:
+        print("table fixtures written; libzstd", ver)
+        return
     ref = {
         "source": "reference tests/test_fse_header.cu:57-66,100-115; tests/test_fse_encoding.cu:15-60; tests/test_compressible_data.cu:272,311,325,363",
         "ncount": [{"norm": [16, 16], "maxsv": 1, "tablelog": 5, "bytes": "103f"},
