@@ -87,13 +87,13 @@ struct ZhWorkspace {
   u8 *base;          // nblocks * ZH_WS_BLOCK_BYTES
   u32 *ctr;          // K1's block counter (persistent workgroups take the next block from it)
   // K1 hash tables of the batch dictionary's content, precomputed once per dictionary
-  // (zh::lz_dict_tables; null: none): 2 x 2^14 u16 entries = tail position + 1 over the last
+  // (zh::lz_dict_tables_batch; null: none): 2 x 2^14 u16 entries = tail position + 1 over the last
   // dtab_P content bytes, positions [0, dtab_P - ZH_DTAB_MARGIN) inserted
   const u16 *dtab;
   u32 dtab_P;
   // The deep matcher's chains of the batch dictionary (levels >= ZH_DEEP_LEVEL; null: none):
   // links of staged positions [0, dd_split) of a first block with dd_pre staged content bytes, and
-  // the head table after them (zh_lz_deep.hip zh_deep_dict_kernel)
+  // the head table after them (zh_lz_deep.hip zh_deep_dict_batch_kernel)
   const u32 *dd_prev;
   const u32 *dd_head;
   u32 dd_pre, dd_split;
@@ -121,8 +121,9 @@ struct ZhWorkspace {
 
 #define ZH_DTAB_MARGIN 256u  // tail positions a block inserts itself (>= one inserter batch)
 
-// One dictionary of a batched table build (zh_lz.hip zh_dict_hash_batch_kernel / zh_dict_pack_batch_kernel,
-// zh_lz_deep.hip zh_deep_dict_batch_kernel): what the single builders take as arguments.
+// One dictionary of a table build (zh_lz.hip zh_dict_hash_batch_kernel / zh_dict_pack_batch_kernel,
+// zh_lz_deep.hip zh_deep_dict_batch_kernel): a handle's own dictionary is a build of one job, a
+// dictionary set's a group of them.
 struct ZhDictBuildJob {
   const u8 *tail;  // K1: the last P content bytes; B = P - ZH_DTAB_MARGIN positions hashed (0: no tables)
   u16 *dtab;       // 2^15 u16 out

@@ -14,7 +14,8 @@ struct ZhDictEnt;
 // of the ID array: ~0.5 MiB for a 64 KiB dictionary, 2 GiB for a full set of them.
 #define ZH_DICTSET_MAX 4096u
 
-// One entry: what DevDict::load builds for one dictionary.
+// One entry: all the device state of one dictionary.  A handle's own dictionary is the entry of a
+// set of one; a view of caller memory is buf and n alone, the rest 0 (zh_host.cpp DevDict).
 struct ZhDictSetEntry {
   const u8 *buf;        // the whole buffer (the decoder reads a formatted dictionary's tables from it)
   u32 n, off, id;       // its size, content offset and Dictionary_ID (0: raw content)

@@ -439,146 +439,47 @@ Status ensure_kernels() {
   return g_init_err == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
 }
 
-// A dictionary on the device: the whole buffer (the decoder reads a formatted
-// dictionary's tables and repcodes from it) and its content offset.
-struct DevDict {
-  u8 *d = nullptr;
-  size_t cap = 0, n = 0, off = 0;
-  u32 id = 0;
-  bool owned = true;  // false: a view of caller memory (streaming history)
-  // K1's hash tables of the content tail, built at load (owned dictionaries only): every
-  // record's first block starts from them instead of hashing the dictionary again
-  u16 *tabs = nullptr;
-  u32 *tabs_tmp = nullptr;
-  u32 tabs_P = 0;
-  // the deep matcher's chains of the content tail (levels >= ZH_DEEP_LEVEL), built at load
-  u32 *deep_prev = nullptr, *deep_head = nullptr;
-  u8 *deep_stg = nullptr;
-  u32 deep_P = 0, deep_split = 0;
-  // the entropy section of a formatted dictionary as the entropy kernel reads it (zh_dict_entropy.h),
-  // built at load (owned dictionaries only; has_ent false: raw content, or a section the encoder
-  // cannot use): CompressionConfig::dict_entropy
-  ZhDictEnt *ent = nullptr;
-  bool has_ent = false;
-  std::vector<u8> host;  // the loaded bytes (a reload of the same dictionary keeps everything)
-  // stream-ordered launches that may still read the buffers: one event per stream, recorded
-  // after each launch (the blocking entry points have finished reading when they return)
-  std::vector<std::pair<hipStream_t, hipEvent_t>> uses;
-  DevDict() = default;
-  DevDict(const DevDict &) = delete;
-  DevDict &operator=(const DevDict &) = delete;
-  ~DevDict() {
-    wait_uses();
-    for (auto &u : uses) (void)hipEventDestroy(u.second);
-    if (d && owned) (void)hipFree(d);
-    if (tabs) (void)hipFree(tabs);
-    if (tabs_tmp) (void)hipFree(tabs_tmp);
-    if (deep_prev) (void)hipFree(deep_prev);
-    if (deep_head) (void)hipFree(deep_head);
-    if (deep_stg) (void)hipFree(deep_stg);
-    if (ent) (void)hipFree(ent);
+// Stream-ordered launches that may still read a dictionary's device memory: one event per stream,
+// recorded after each launch (the blocking entry points have finished reading when they return).
+// Whoever owns the memory waits for them before it frees it.
+struct StreamUses {
+  std::mutex mu;
+  std::vector<std::pair<hipStream_t, hipEvent_t>> events;
+  StreamUses() = default;
+  StreamUses(const StreamUses &) = delete;
+  StreamUses &operator=(const StreamUses &) = delete;
+  ~StreamUses() {
+    for (auto &u : events) (void)hipEventDestroy(u.second);
   }
-  // raw-content view of device-resident history (never freed here)
-  static void view(DevDict &v, const void *p, size_t bytes) {
-    v.owned = false;
-    v.d = (u8 *)p;
-    v.cap = v.n = bytes;
-    v.off = 0;
-    v.id = 0;
-    v.tabs_P = 0;  // (a moving history window: hashed by every block)
-    v.deep_P = 0;
-    v.has_ent = false;
-  }
-  const u8 *content() const { return d + off; }
-  size_t content_n() const { return n - off; }
-  // a stream-ordered launch on `stream` reads this dictionary
-  Status note_use(hipStream_t stream) const {
-    auto *self = const_cast<DevDict *>(this);
-    for (auto &u : self->uses)
+  // a stream-ordered launch on `stream` reads the memory
+  Status note(hipStream_t stream) {
+    std::lock_guard<std::mutex> g(mu);
+    for (auto &u : events)
       if (u.first == stream) return hipEventRecord(u.second, stream) == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
     hipEvent_t e;
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return Status::ERROR_CUDA_ERROR;
-    self->uses.emplace_back(stream, e);
+    events.emplace_back(stream, e);
     return hipEventRecord(e, stream) == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
   }
-  // every stream-ordered launch that read the dictionary has finished (before it is replaced)
-  Status wait_uses() {
+  // every noted launch has finished
+  Status wait() {
+    std::lock_guard<std::mutex> g(mu);
     Status s = Status::SUCCESS;
-    for (auto &u : uses)
+    for (auto &u : events)
       if (hipEventSynchronize(u.second) != hipSuccess) s = Status::ERROR_CUDA_ERROR;
     return s;
   }
-  // raw content or a formatted dictionary (host or device buffer); replaces the previous one
-  Status load(const void *p, size_t bytes, hipStream_t stream) {
-    if (!p || !bytes || bytes > zh::kDictMaxBytes) return Status::ERROR_INVALID_PARAMETER;
-    std::vector<u8> h(bytes);
-    Status s = copy_any(h.data(), p, bytes, stream);
-    if (s != Status::SUCCESS) return s;
-    if (owned && d && n == bytes && host == h) return Status::SUCCESS;  // the same dictionary: tables kept
-    u32 did = 0;
-    size_t co = 0;
-    if (!zh::dict_layout(h.data(), bytes, did, co)) return Status::ERROR_DICTIONARY_FAILED;
-    if (d && wait_uses() != Status::SUCCESS) return Status::ERROR_CUDA_ERROR;  // stream-ordered launches still reading it
-    if (bytes > cap) {
-      if (d) (void)hipFree(d);
-      d = nullptr;
-      cap = 0;
-      n = 0;
-      if (hipMalloc(&d, bytes) != hipSuccess) { d = nullptr; return Status::ERROR_OUT_OF_MEMORY; }
-      cap = bytes;
-    }
-    if (hipMemcpy(d, h.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return Status::ERROR_CUDA_ERROR;
-    n = bytes;
-    off = co;
-    id = did;
-    tabs_P = 0;
-    if (!tabs && hipMalloc(&tabs, 2u * (1u << ZH_HASH_LOG_LONG) + 2u * (1u << ZH_HASH_LOG_SHORT)) != hipSuccess) tabs = nullptr;
-    if (!tabs_tmp && hipMalloc(&tabs_tmp, 4u * ((1u << ZH_HASH_LOG_LONG) + (1u << ZH_HASH_LOG_SHORT))) != hipSuccess) tabs_tmp = nullptr;
-    if (tabs && tabs_tmp) {
-      u32 P = 0;
-      if (zh::lz_dict_tables(content(), content_n(), tabs, tabs_tmp, P, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess)
-        tabs_P = P;
-    }
-    deep_P = deep_split = 0;
-    if (!deep_prev && hipMalloc(&deep_prev, 4u * ZH_DEEP_PRE) != hipSuccess) deep_prev = nullptr;
-    if (!deep_head && hipMalloc(&deep_head, 4u << ZH_HASH_LOG_SHORT) != hipSuccess) deep_head = nullptr;
-    if (!deep_stg && hipMalloc(&deep_stg, ZH_DEEP_PRE + 256) != hipSuccess) deep_stg = nullptr;
-    if (deep_prev && deep_head && deep_stg) {
-      u32 P = 0, sp = 0;
-      if (zh::lz_deep_dict_tables(content(), content_n(), deep_stg, deep_prev, deep_head, P, sp, stream) == hipSuccess &&
-          hipStreamSynchronize(stream) == hipSuccess) {
-        deep_P = P;
-        deep_split = sp;
-      }
-    }
-    has_ent = false;
-    if (co) {  // a formatted dictionary: its Huffman code, FSE encoding tables, bit costs and repcodes
-      ZhDictEnt he;
-      size_t co2 = 0;
-      if (zh::dent::parse(h.data(), bytes, &he, &co2) && co2 == co) {
-        if (!ent && hipMalloc(&ent, sizeof(ZhDictEnt)) != hipSuccess) ent = nullptr;
-        if (ent && hipMemcpy(ent, &he, sizeof(he), hipMemcpyHostToDevice) == hipSuccess) has_ent = true;
-      }
-    }
-    host.swap(h);
-    return Status::SUCCESS;
-  }
-  // the blob the entropy kernel takes when the configuration asks for the dictionary's entropy section
-  const ZhDictEnt *dent(const CompressionConfig &c) const { return c.dict_entropy && n && has_ent ? ent : nullptr; }
-  void fill(ZhDecArgs &a) const {
-    if (!n) return;
-    a.dict = d;
-    a.dict_n = n;
-    a.dict_off = (u32)off;
-    a.dict_id = id;
-  }
 };
 
-// A set of dictionaries on the device (zh_dictset.h): one allocation holding, per entry, what
-// DevDict::load builds for one dictionary, indexed by an entry table, with the non-zero IDs sorted
-// next to it.  Immutable once built.  The tables come from the batched builders (the dictionary is
-// a grid dimension), ZH_DICTSET_GROUP dictionaries at a time so that the build's scratch is bounded:
-// four stream operations per group, whatever the set's size.
+// A set of dictionaries on the device (zh_dictset.h): one allocation holding, per entry, the whole
+// buffer (the decoder reads a formatted dictionary's tables and repcodes from it), K1's hash tables
+// and the deep matcher's chains of the content tail (every record's first block starts from them
+// instead of hashing the dictionary again) and a formatted dictionary's entropy blob as the entropy
+// kernel reads it (zh_dict_entropy.h), indexed by an entry table, with the non-zero IDs sorted next
+// to it.  Immutable once built.  The tables come from the one pair of builders (the dictionary is a
+// grid dimension), ZH_DICTSET_GROUP dictionaries at a time so that the build's scratch is bounded:
+// four stream operations per group, whatever the set's size.  A handle's own dictionary is a set of
+// one (DevDict).
 #define ZH_DICTSET_GROUP 64u
 struct DictSetDev {
   u8 *mem = nullptr;
@@ -587,15 +488,12 @@ struct DictSetDev {
   std::vector<ZhDictSetId> ids;      // the non-zero IDs, sorted
   const ZhDictSetEntry *d_ents = nullptr;
   const ZhDictSetId *d_ids = nullptr;
-  // stream-ordered launches that may still read the set: one event per stream (as DevDict::uses)
-  std::mutex mu;
-  std::vector<std::pair<hipStream_t, hipEvent_t>> uses;
+  StreamUses uses;  // stream-ordered launches that may still read the set
   DictSetDev() = default;
   DictSetDev(const DictSetDev &) = delete;
   DictSetDev &operator=(const DictSetDev &) = delete;
   ~DictSetDev() {
-    (void)wait_uses();
-    for (auto &u : uses) (void)hipEventDestroy(u.second);
+    (void)uses.wait();
     if (mem) (void)hipFree(mem);
   }
   u32 count() const { return (u32)ents.size(); }
@@ -608,31 +506,17 @@ struct DictSetDev {
     a.set_nids = (u32)ids.size();
     a.dict_index = dict_index;
   }
-  Status note_use(hipStream_t stream) {
-    std::lock_guard<std::mutex> g(mu);
-    for (auto &u : uses)
-      if (u.first == stream) return hipEventRecord(u.second, stream) == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
-    hipEvent_t e;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return Status::ERROR_CUDA_ERROR;
-    uses.emplace_back(stream, e);
-    return hipEventRecord(e, stream) == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
-  }
-  Status wait_uses() {
-    std::lock_guard<std::mutex> g(mu);
-    Status s = Status::SUCCESS;
-    for (auto &u : uses)
-      if (hipEventSynchronize(u.second) != hipSuccess) s = Status::ERROR_CUDA_ERROR;
-    return s;
-  }
-  // bufs[i] / sizes[i]: host bytes of dictionary i, raw content or formatted
-  Status build(const u8 *const *bufs, const size_t *sizes, size_t n, hipStream_t stream) {
+  // bufs[i] / sizes[i]: host bytes of dictionary i, raw content or formatted, 1 .. kDictMaxBytes of
+  // them (a set's floor of MIN_DICT_SIZE is DictionarySet::create's rule).  need_tables false: a
+  // build whose table stage fails leaves the (host) entries without tables and succeeds.
+  Status build(const u8 *const *bufs, const size_t *sizes, size_t n, hipStream_t stream, bool need_tables = true) {
     if (!bufs || !sizes || n < 1 || n > ZH_DICTSET_MAX) return Status::ERROR_INVALID_PARAMETER;
     Status s = ensure_kernels();
     if (s != Status::SUCCESS) return s;
     std::vector<u32> raw_ids(n);
     std::vector<size_t> offs(n);
     for (size_t i = 0; i < n; i++) {
-      if (!bufs[i] || sizes[i] < dictionary::MIN_DICT_SIZE || sizes[i] > zh::kDictMaxBytes) return Status::ERROR_INVALID_PARAMETER;
+      if (!bufs[i] || !sizes[i] || sizes[i] > zh::kDictMaxBytes) return Status::ERROR_INVALID_PARAMETER;
       if (!zh::dict_layout(bufs[i], sizes[i], raw_ids[i], offs[i])) return Status::ERROR_DICTIONARY_FAILED;
     }
     ids.resize(n);
@@ -648,6 +532,8 @@ struct DictSetDev {
     std::vector<u8> has_ent(n, 0);
     for (size_t i = 0; i < n; i++) {
       o_buf[i] = take(sizes[i]);
+      // a formatted dictionary: its Huffman code, FSE encoding tables, bit costs and repcodes
+      // (none for a section the encoder cannot use)
       size_t co2 = 0;
       if (offs[i] && zh::dent::parse(bufs[i], sizes[i], &blobs[i], &co2) && co2 == offs[i]) {
         has_ent[i] = 1;
@@ -706,17 +592,74 @@ struct DictSetDev {
     u32 const group = (u32)std::min<size_t>(n, ZH_DICTSET_GROUP);
     size_t const tmp_bytes = align256((size_t)group * tab_entries * 4);
     u8 *scratch = nullptr;
-    if (hipMalloc(&scratch, tmp_bytes + (size_t)group * ZH_DEEP_DICT_STG) != hipSuccess) return Status::ERROR_OUT_OF_MEMORY;
-    const ZhDictBuildJob *const d_jobs = (const ZhDictBuildJob *)(mem + o_jobs);
-    hipError_t e = hipSuccess;
-    for (size_t g0 = 0; g0 < n && e == hipSuccess; g0 += group) {
-      u32 const cnt = (u32)std::min<size_t>(group, n - g0);
-      e = zh::lz_dict_tables_batch(d_jobs + g0, cnt, (u32 *)scratch, stream);
-      if (e == hipSuccess) e = zh::lz_deep_dict_tables_batch(d_jobs + g0, cnt, scratch + tmp_bytes, stream);
+    s = hipMalloc(&scratch, tmp_bytes + (size_t)group * ZH_DEEP_DICT_STG) == hipSuccess ? Status::SUCCESS : Status::ERROR_OUT_OF_MEMORY;
+    if (s == Status::SUCCESS) {
+      const ZhDictBuildJob *const d_jobs = (const ZhDictBuildJob *)(mem + o_jobs);
+      hipError_t e = hipSuccess;
+      for (size_t g0 = 0; g0 < n && e == hipSuccess; g0 += group) {
+        u32 const cnt = (u32)std::min<size_t>(group, n - g0);
+        e = zh::lz_dict_tables_batch(d_jobs + g0, cnt, (u32 *)scratch, stream);
+        if (e == hipSuccess) e = zh::lz_deep_dict_tables_batch(d_jobs + g0, cnt, scratch + tmp_bytes, stream);
+      }
+      if (hipStreamSynchronize(stream) != hipSuccess || e != hipSuccess) s = Status::ERROR_CUDA_ERROR;
+      (void)hipFree(scratch);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(scratch);
-    return e == hipSuccess ? Status::SUCCESS : Status::ERROR_CUDA_ERROR;
+    if (s == Status::SUCCESS || need_tables) return s;
+    for (ZhDictSetEntry &e : ents) {
+      e.dtab = nullptr;
+      e.dd_prev = e.dd_head = nullptr;
+      e.dtab_P = e.dd_pre = e.dd_split = 0;
+    }
+    return Status::SUCCESS;
+  }
+};
+
+// A handle's dictionary, or a stream's history, on the device: one entry
+// (zh_dictset.h) and what owns its memory.  A loaded dictionary is the entry of a one-entry set,
+// built as any set is.  A view is an entry of caller memory without tables.
+struct DevDict {
+  ZhDictSetEntry e{};               // n 0: none
+  std::unique_ptr<DictSetDev> own;  // the set e is entry 0 of (null: a view, or nothing loaded)
+  std::vector<u8> host;             // the loaded bytes (a reload of the same dictionary keeps everything)
+  // raw-content view of device-resident history (never freed here; a moving window: hashed by
+  // every block).  (An entry's size has 32 bits: the bytes next to the data, and no match reaches
+  // further back.)
+  static void view(DevDict &v, const void *p, size_t bytes) {
+    size_t const n = std::min<size_t>(bytes, 0xFFFFFFFFu);
+    v.e = ZhDictSetEntry{};
+    v.e.buf = (const u8 *)p + (bytes - n);
+    v.e.n = (u32)n;
+  }
+  const u8 *content() const { return e.buf + e.off; }
+  size_t content_n() const { return e.n - e.off; }
+  // a stream-ordered launch on `stream` reads this dictionary
+  Status note_use(hipStream_t stream) const { return own ? own->uses.note(stream) : Status::SUCCESS; }
+  // raw content or a formatted dictionary (host or device buffer, 1 .. kDictMaxBytes bytes);
+  // replaces the previous one, whose owner waits for the stream-ordered launches still reading it
+  // before its memory goes
+  Status load(const void *p, size_t bytes, hipStream_t stream) {
+    if (!p || !bytes || bytes > zh::kDictMaxBytes) return Status::ERROR_INVALID_PARAMETER;
+    std::vector<u8> h(bytes);
+    Status s = copy_any(h.data(), p, bytes, stream);
+    if (s != Status::SUCCESS) return s;
+    if (own && e.n == bytes && host == h) return Status::SUCCESS;  // the same dictionary: tables kept
+    auto set = std::make_unique<DictSetDev>();
+    const u8 *const buf = h.data();
+    s = set->build(&buf, &bytes, 1, stream, false);
+    if (s != Status::SUCCESS) return s;
+    own = std::move(set);
+    e = own->ents[0];
+    host.swap(h);
+    return Status::SUCCESS;
+  }
+  // the blob the entropy kernel takes when the configuration asks for the dictionary's entropy section
+  const ZhDictEnt *dent(const CompressionConfig &c) const { return c.dict_entropy && e.n ? e.dent : nullptr; }
+  void fill(ZhDecArgs &a) const {
+    if (!e.n) return;
+    a.dict = e.buf;
+    a.dict_n = e.n;
+    a.dict_off = e.off;
+    a.dict_id = e.id;
   }
 };
 
@@ -725,7 +668,7 @@ struct DictSetDev {
 // device routes, one per item on the host route) and the filled ZhWorkspace.  dd: the batch's
 // dictionary or null; stats: collect_entropy_stats' histograms or null.
 ZhBatch bind_batch(const WsLayout &L, u8 *base, const DevDict *dd, const CompressionConfig &c, u32 *stats = nullptr) {
-  if (dd && !dd->n) dd = nullptr;
+  if (dd && !dd->e.n) dd = nullptr;
   ZhBatch b{};
   b.descs = (ZhBlockDesc *)(base + L.descs);
   b.items = (ZhItemDesc *)(base + L.items);
@@ -747,18 +690,18 @@ ZhBatch bind_batch(const WsLayout &L, u8 *base, const DevDict *dd, const Compres
   if (dd) {
     b.plan.dict = dd->content();
     b.plan.dict_n = (u32)dd->content_n();
-    b.plan.dict_id = dd->id;
+    b.plan.dict_id = dd->e.id;
   }
   b.plan.staging = base + L.staging;
   b.ws.base = base + L.blocks;
   b.ws.ctr = (u32 *)(base + L.counter);
-  b.ws.dtab = dd && dd->tabs_P ? dd->tabs : nullptr;  // K1's tables of the dictionary's content tail
-  b.ws.dtab_P = dd ? dd->tabs_P : 0u;
-  if (dd && dd->deep_P) {  // the deep matcher's precomputed dictionary chains, when the dictionary has them
-    b.ws.dd_prev = dd->deep_prev;
-    b.ws.dd_head = dd->deep_head;
-    b.ws.dd_pre = dd->deep_P;
-    b.ws.dd_split = dd->deep_split;
+  if (dd) {  // K1's tables of the dictionary's content tail and the deep matcher's chains, when the dictionary has them
+    b.ws.dtab = dd->e.dtab;
+    b.ws.dtab_P = dd->e.dtab_P;
+    b.ws.dd_prev = dd->e.dd_prev;
+    b.ws.dd_head = dd->e.dd_head;
+    b.ws.dd_pre = dd->e.dd_pre;
+    b.ws.dd_split = dd->e.dd_split;
   }
   b.ws.deep_slots = L.deep_slots ? base + L.deep : nullptr;
   b.ws.deep_nslots = (u32)L.deep_slots;
@@ -791,7 +734,7 @@ class ZstdBatchManager::Impl {
   size_t pinned_bytes = 0;
   DevDict mgr_dict, call_dict;  // set_dictionary()'s / compress()'s per-call dictionary
   u32 *stats_dev = nullptr;     // collect_entropy_stats: run() asks the entropy kernel for its histograms (ZH_F_STATS)
-  const DevDict *active() const { return mgr_dict.n ? &mgr_dict : nullptr; }
+  const DevDict *active() const { return mgr_dict.e.n ? &mgr_dict : nullptr; }
   std::shared_ptr<DictSetDev> set;  // set_dictionary_set()'s dictionary set (never together with mgr_dict)
 
   explicit Impl(const CompressionConfig &c) : config(c) {}
@@ -875,7 +818,7 @@ class ZstdBatchManager::Impl {
     hipError_t e = zh::launch_plan(b, pa, stream);
     if (e == hipSuccess) e = zh::launch_compress(b, stream);
     if (e != hipSuccess) return Status::ERROR_CUDA_ERROR;
-    if (ds) return ds->note_use(stream);
+    if (ds) return ds->uses.note(stream);
     return dd ? dd->note_use(stream) : Status::SUCCESS;
   }
 
@@ -891,7 +834,7 @@ class ZstdBatchManager::Impl {
              void *temp, size_t temp_size, hipStream_t stream, const DevDict *dd = nullptr, bool allow_ldm = false) {
     Status s = ensure_kernels();
     if (s != Status::SUCCESS) return s;
-    bool const has_dict = dd && dd->n;
+    bool const has_dict = dd && dd->e.n;
     // long-distance matching (allow_ldm: compress() of one frame, whose workspace query sized for
     // it; the batch entries never ask): three slots per cell, the cells' descriptors come from
     // zh_ldm_cell_kernel instead of the loop below
@@ -1192,7 +1135,7 @@ Status ZstdBatchManager::set_dictionary(const dictionary::Dictionary &d) {
   Status s = pimpl_->mgr_dict.load(d.raw_content, d.raw_size, 0);
   if (s != Status::SUCCESS) return s;
   pimpl_->dict_hdr = d.header;
-  pimpl_->dict_hdr.dictionary_id = pimpl_->mgr_dict.id;
+  pimpl_->dict_hdr.dictionary_id = pimpl_->mgr_dict.e.id;
   pimpl_->dict_hdr.raw_content_size = d.raw_size;
   pimpl_->has_dict = true;
   return Status::SUCCESS;
@@ -1213,7 +1156,7 @@ Status ZstdBatchManager::clear_dictionary() {
   std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
   pimpl_->has_dict = false;
   pimpl_->dict_hdr = dictionary::DictionaryHeader{};
-  pimpl_->mgr_dict.n = 0;
+  pimpl_->mgr_dict.e.n = 0;
   return Status::SUCCESS;
 }
 const CompressionStats &ZstdBatchManager::get_stats() const { return pimpl_->stats; }
@@ -1395,7 +1338,7 @@ class DictionarySet::Impl {
   std::shared_ptr<DictSetDev> dev = std::make_shared<DictSetDev>();
 };
 DictionarySet::DictionarySet() : pimpl_(new Impl) {}
-DictionarySet::~DictionarySet() { (void)pimpl_->dev->wait_uses(); }  // (a manager it is still bound to keeps the memory)
+DictionarySet::~DictionarySet() { (void)pimpl_->dev->uses.wait(); }  // (a manager it is still bound to keeps the memory)
 size_t DictionarySet::count() const { return pimpl_->dev->count(); }
 int DictionarySet::find(u32 dictionary_id) const { return pimpl_->dev->find(dictionary_id); }
 Status DictionarySet::create(const dictionary::Dictionary *const *dicts, size_t count, hipStream_t stream, std::unique_ptr<DictionarySet> &out) {
@@ -1423,7 +1366,7 @@ Status DictionarySet::create(const dictionary::Dictionary *const *dicts, size_t 
 
 Status ZstdBatchManager::set_dictionary_set(const DictionarySet *set) {
   std::lock_guard<std::mutex> lock(pimpl_->api_mutex);
-  if (set && pimpl_->mgr_dict.n) return Status::ERROR_INVALID_PARAMETER;  // a dictionary is set: one or the other
+  if (set && pimpl_->mgr_dict.e.n) return Status::ERROR_INVALID_PARAMETER;  // a dictionary is set: one or the other
   pimpl_->set = set ? set->impl().dev : nullptr;
   return Status::SUCCESS;
 }
@@ -1478,7 +1421,7 @@ Status ZstdBatchManager::Impl::run_device_decompress(const void *const *d_in_ptr
   if (!count) return Status::SUCCESS;
   if (!d_in_ptrs || !d_in_sizes || !d_out_ptrs || !d_out_sizes || max_out == 0) return Status::ERROR_INVALID_PARAMETER;
   bool const prefix = d_prefix_ptrs || d_prefix_sizes;
-  if (prefix && (!d_prefix_ptrs || !d_prefix_sizes || pimpl_->mgr_dict.n || pimpl_->set)) return Status::ERROR_INVALID_PARAMETER;
+  if (prefix && (!d_prefix_ptrs || !d_prefix_sizes || pimpl_->mgr_dict.e.n || pimpl_->set)) return Status::ERROR_INVALID_PARAMETER;
   if (d_dict_index && !pimpl_->set) return Status::ERROR_INVALID_PARAMETER;
   DecLayout L = DecLayout::make(count, max_out);
   if (!temp || temp_size < L.total) return Status::ERROR_BUFFER_TOO_SMALL;
@@ -1498,8 +1441,8 @@ Status ZstdBatchManager::Impl::run_device_decompress(const void *const *d_in_ptr
   a.statuses = d_statuses ? (u32 *)d_statuses : (u32 *)(base + L.statuses);
   a.nvcomp_codes = 1;
   if (zh::launch_decompress(a, (u32)count, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
-  if (ds) return ds->note_use(stream);
-  return pimpl_->mgr_dict.n ? pimpl_->mgr_dict.note_use(stream) : Status::SUCCESS;
+  if (ds) return ds->uses.note(stream);
+  return pimpl_->mgr_dict.e.n ? pimpl_->mgr_dict.note_use(stream) : Status::SUCCESS;
 }
 
 // The decompressed size of every buffer, on the device (zh_dec_size_kernel): one launch, no
@@ -1522,8 +1465,8 @@ Status ZstdBatchManager::get_decompressed_sizes_async(const void *const *d_ptrs,
   a.statuses = (u32 *)d_statuses;
   a.nvcomp_codes = nvcomp_codes ? 1u : 0u;
   if (zh::launch_decompress_sizes(a, (u32)count, stream) != hipSuccess) return Status::ERROR_CUDA_ERROR;
-  if (ds) return ds->note_use(stream);
-  return pimpl_->mgr_dict.n ? pimpl_->mgr_dict.note_use(stream) : Status::SUCCESS;
+  if (ds) return ds->uses.note(stream);
+  return pimpl_->mgr_dict.e.n ? pimpl_->mgr_dict.note_use(stream) : Status::SUCCESS;
 }
 
 // ============================================================================
@@ -3002,32 +2945,30 @@ void cuda_zstd_dict_set_destroy(cuda_zstd_dict_set_t *set) { delete set; }
 size_t cuda_zstd_dict_set_count(const cuda_zstd_dict_set_t *set) { return (set && set->set) ? set->set->count() : 0; }
 int cuda_zstd_dict_set_find(const cuda_zstd_dict_set_t *set, unsigned int dict_id) { return (set && set->set) ? set->set->find(dict_id) : -1; }
 // Test hooks (tests/test_gpu_dictset.py, not product entry points): the precomputed tables of one
-// dictionary copied back -- entry `index` of a set (the batched builders), and a host buffer loaded
-// as set_dictionary loads it (the single builders, DevDict::load).  dtab: 2^15 u16, K1's packed
+// dictionary copied back -- entry `index` of a set, and a host buffer loaded as set_dictionary
+// loads it (DevDict::load: the same builders over a set of one, any size from 1 byte).  dtab: 2^15 u16, K1's packed
 // tables (written when *P != 0); prev: ZH_DEEP_PRE u32, the deep matcher's links, [0, *split)
 // written; head: 2^ZH_HASH_LOG_SHORT u32 (written when *dP != 0).  Returns 0, 1 (HIP error) or 2.
-static int copy_dict_tables(const u16 *tabs, u32 tP, const u32 *dprev, const u32 *dhead, u32 dP, u32 dsplit, u16 *dtab, u32 *P, u32 *prev, u32 *head,
-                            u32 *pdP, u32 *split) {
-  *P = tP;
-  *pdP = dP;
-  *split = dsplit;
+static int copy_dict_tables(const ZhDictSetEntry &e, u16 *dtab, u32 *P, u32 *prev, u32 *head, u32 *dP, u32 *split) {
+  *P = e.dtab_P;
+  *dP = e.dd_pre;
+  *split = e.dd_split;
   size_t const tab_bytes = ((size_t(1) << ZH_HASH_LOG_LONG) + (size_t(1) << ZH_HASH_LOG_SHORT)) * 2;
   if (hipDeviceSynchronize() != hipSuccess) return 1;
-  if (tP && hipMemcpy(dtab, tabs, tab_bytes, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-  if (dP && dsplit && hipMemcpy(prev, dprev, (size_t)dsplit * 4, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-  if (dP && hipMemcpy(head, dhead, size_t(4) << ZH_HASH_LOG_SHORT, hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  if (e.dtab_P && hipMemcpy(dtab, e.dtab, tab_bytes, hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  if (e.dd_pre && e.dd_split && hipMemcpy(prev, e.dd_prev, (size_t)e.dd_split * 4, hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  if (e.dd_pre && hipMemcpy(head, e.dd_head, size_t(4) << ZH_HASH_LOG_SHORT, hipMemcpyDeviceToHost) != hipSuccess) return 1;
   return 0;
 }
 int zh_test_dictset_tables(const cuda_zstd_dict_set_t *set, size_t index, u16 *dtab, u32 *P, u32 *prev, u32 *head, u32 *dP, u32 *split) {
   if (!set || !set->set || index >= set->set->count()) return 2;
-  ZhDictSetEntry const &e = set->set->impl().dev->ents[index];
-  return copy_dict_tables(e.dtab, e.dtab_P, e.dd_prev, e.dd_head, e.dd_pre, e.dd_split, dtab, P, prev, head, dP, split);
+  return copy_dict_tables(set->set->impl().dev->ents[index], dtab, P, prev, head, dP, split);
 }
 int zh_test_dict_tables(const void *buf, size_t n, u16 *dtab, u32 *P, u32 *prev, u32 *head, u32 *dP, u32 *split) {
   if (ensure_kernels() != Status::SUCCESS) return 1;
   DevDict d;
   if (d.load(buf, n, 0) != Status::SUCCESS) return 2;
-  return copy_dict_tables(d.tabs, d.tabs_P, d.deep_prev, d.deep_head, d.deep_P, d.deep_split, dtab, P, prev, head, dP, split);
+  return copy_dict_tables(d.e, dtab, P, prev, head, dP, split);
 }
 int nvcomp_zstd_batch_set_dictionary_set_v5(nvcomp_zstd_batch_manager_t *m, cuda_zstd_dict_set_t *set) {
   if (!m || !m->mgr || (set && !set->set)) return c_err(Status::ERROR_INVALID_PARAMETER);

@@ -85,15 +85,12 @@ hipError_t launch_decompress_sizes(const ZhDecArgs &a, u32 nitems, hipStream_t s
 hipError_t init_kernels();
 u32 lz_lds_bytes();
 u32 entropy_lds_bytes();
-// K1 hash tables of a dictionary's content tail, built once per dictionary (zh_lz.hip):
-// out = 2^15 u16, tmp32 = 2^15 u32 scratch; P = the tail length covered (0: none)
-hipError_t lz_dict_tables(const u8 *content, size_t cn, u16 *out, u32 *tmp32, u32 &P, hipStream_t stream);
-hipError_t lz_deep_dict_tables(const u8 *content, size_t cn, u8 *stg, u32 *dprev, u32 *dhead, u32 &P, u32 &split, hipStream_t stream);
-// The two builders with the dictionary as a grid dimension (a dictionary set's creation): the
-// tables of d_jobs[0, count) in one memset and three launches whatever count is, byte for byte
-// what the single builders give each dictionary.  tmp32: count x 2^15 u32, stg: count x
-// ZH_DEEP_DICT_STG bytes of scratch.  lz_dict_tables_P / lz_deep_dict_shape: the P (and split) the
-// single builders take for cn content bytes.
+// A dictionary's precomputed tables, built once per dictionary with the dictionary as a grid
+// dimension (one job for a handle's own dictionary, a group for a dictionary set): K1's hash tables
+// of the content tail (zh_lz.hip) and the deep matcher's chains (zh_lz_deep.hip) of d_jobs[0, count)
+// in one memset and three launches whatever count is.  tmp32: count x 2^15 u32, stg: count x
+// ZH_DEEP_DICT_STG bytes of scratch.  lz_dict_tables_P / lz_deep_dict_shape: the tail length P (and
+// split) the builders cover for cn content bytes (0: none), from which the caller fills the jobs.
 u32 lz_dict_tables_P(size_t cn);
 void lz_deep_dict_shape(size_t cn, u32 &P, u32 &split);
 hipError_t lz_dict_tables_batch(const ZhDictBuildJob *d_jobs, u32 count, u32 *tmp32, hipStream_t stream);

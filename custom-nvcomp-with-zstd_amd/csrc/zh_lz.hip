@@ -1951,24 +1951,12 @@ extern "C" __global__ __launch_bounds__(K1_THREADS) void zh_lz_greedy_ranged_ker
 
 extern "C" u32 zh_lz_lds_bytes() { return K1_LDS; }
 
-// A dictionary's K1 tables (ZhWorkspace::dtab), built once per dictionary: t32[slot] = max over
+// A dictionary's K1 tables (ZhWorkspace::dtab), built once per dictionary: t[slot] = max over
 // tail positions j < B hashing there of j + 1 (the latest, as K1's in-order insertion leaves
-// it), then packed to u16.  tail = the last P content bytes.
-extern "C" __global__ void zh_dict_hash_kernel(const u8 *__restrict__ tail, u32 B, u32 *__restrict__ t32) {
-  for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < B; j += gridDim.x * blockDim.x) {
-    u32 const lo = (u32)tail[j] | ((u32)tail[j + 1] << 8) | ((u32)tail[j + 2] << 16) | ((u32)tail[j + 3] << 24);
-    u32 const hi = (u32)tail[j + 4] | ((u32)tail[j + 5] << 8) | ((u32)tail[j + 6] << 16) | ((u32)tail[j + 7] << 24);
-    atomicMax(&t32[hash_of<true>(lo, hi)], j + 1);
-    atomicMax(&t32[HL_SIZE + hash_of<false>(lo, hi)], j + 1);
-  }
-}
-extern "C" __global__ void zh_dict_pack_kernel(const u32 *__restrict__ t32, u16 *__restrict__ out) {
-  u32 const i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < HL_SIZE + HS_SIZE) out[i] = (u16)t32[i];
-}
-// The same for a group of dictionaries (a dictionary set, zh_dictset.h): blockIdx.y is the
-// dictionary, jobs[y] its tail, positions and output, t32 + y * (HL_SIZE + HS_SIZE) its scratch
-// table (zeroed by the caller).  A job with B = 0 has no tables.
+// it), then packed to u16.  tail = the last P content bytes.  blockIdx.y is the dictionary (one
+// for a handle's own, a group of a dictionary set's, zh_dictset.h): jobs[y] its tail, positions
+// and output, t32 + y * (HL_SIZE + HS_SIZE) its scratch table (zeroed by the caller).  A job with
+// B = 0 has no tables.
 extern "C" __global__ void zh_dict_hash_batch_kernel(const ZhDictBuildJob *__restrict__ jobs, u32 *__restrict__ t32) {
   ZhDictBuildJob const job = jobs[blockIdx.y];
   const u8 *const tail = job.tail;
@@ -1996,25 +1984,15 @@ hipError_t lz_init() {
   }
   return hipSuccess;
 }
-// tables for the last P = min(cn, 65535) content bytes (positions [0, P - ZH_DTAB_MARGIN));
-// out: 2^15 u16 (long table, then short), tmp32: 2^15 u32 scratch.  P = 0: none (too short).
-hipError_t lz_dict_tables(const u8 *content, size_t cn, u16 *out, u32 *tmp32, u32 &P, hipStream_t stream) {
-  P = (u32)std::min(cn, (size_t)65535);
-  if (P < 2 * ZH_DTAB_MARGIN) { P = 0; return hipSuccess; }
-  u32 const B = P - ZH_DTAB_MARGIN;
-  hipError_t e = hipMemsetAsync(tmp32, 0, 4 * (HL_SIZE + HS_SIZE), stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(zh_dict_hash_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, content + cn - P, B, tmp32);
-  hipLaunchKernelGGL(zh_dict_pack_kernel, dim3((HL_SIZE + HS_SIZE + 255) / 256), dim3(256), 0, stream, tmp32, out);
-  return hipGetLastError();
-}
-// the tail length lz_dict_tables covers for cn content bytes (0: no tables)
+// The tables cover the last P = min(cn, 65535) of cn content bytes, positions [0, P -
+// ZH_DTAB_MARGIN) of them; P = 0: none (too short)
 u32 lz_dict_tables_P(size_t cn) {
   u32 const P = (u32)std::min(cn, (size_t)65535);
   return P < 2 * ZH_DTAB_MARGIN ? 0u : P;
 }
-// lz_dict_tables for the `count` dictionaries of d_jobs (tail = content + cn - P, B = P -
-// ZH_DTAB_MARGIN, or B = 0) in one memset and two launches: tmp32 = count x 2^15 u32 scratch
+// The tables of the `count` dictionaries of d_jobs (tail = content + cn - P, B = P -
+// ZH_DTAB_MARGIN, or B = 0; dtab: 2^15 u16, the long table, then the short) in one memset and two
+// launches: tmp32 = count x 2^15 u32 scratch
 hipError_t lz_dict_tables_batch(const ZhDictBuildJob *d_jobs, u32 count, u32 *tmp32, hipStream_t stream) {
   if (!count) return hipSuccess;
   hipError_t e = hipMemsetAsync(tmp32, 0, (size_t)count * 4 * (HL_SIZE + HS_SIZE), stream);

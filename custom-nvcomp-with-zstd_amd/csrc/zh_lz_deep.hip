@@ -679,7 +679,7 @@ __device__ void deep_block(const ZhBlockDesc &d, ZhWorkspace ws, u32 b, u8 *slot
     }
   }
   // A dictionary frame's first block starts from the dictionary's precomputed chains (built once
-  // per dictionary, zh_deep_dict_kernel): the head table after its positions [0, dd_split), whose
+  // per dictionary, zh_deep_dict_batch_kernel): the head table after its positions [0, dd_split), whose
   // links stay in ws.dd_prev; the block links only [dd_split, lim) -- the same chains.
   // (a dictionary-set batch: the chains of the block's own entry, zh_dictset.h)
   const u32 *dd_head = ws.dd_head, *dd_prev = ws.dd_prev;
@@ -896,20 +896,9 @@ extern "C" u32 zh_deep_fix_host() {
 // A dictionary's deep-matcher chains, built once per dictionary (one workgroup): the last P =
 // min(content, ZH_DEEP_PRE) content bytes staged as a record's first block stages them, the links
 // of positions [0, split) (split = (P - ZH_HASH_READ) & ~3: every byte they hash is dictionary
-// content) into dprev and the head table after them into dhead.
-extern "C" __global__ __launch_bounds__(DT) void zh_deep_dict_kernel(const u8 *__restrict__ tail, u32 P, u8 *stg, u32 *dprev, u32 *dhead) {
-  extern __shared__ __attribute__((aligned(16))) u8 smem[];
-  u32 *head = (u32 *)(smem + L_HEAD);
-  u32 const tid = threadIdx.x;
-  for (u32 i = tid; i < P + 64; i += DT) stg[i] = i < P ? tail[i] : (u8)0;
-  for (u32 i = tid; i < HSIZE + 4; i += DT) head[i] = 0;
-  __syncthreads();
-  u32 const split = (P > ZH_HASH_READ ? P - ZH_HASH_READ : 0u) & ~3u;
-  deep_chains((const u32 *)stg, dprev, head, (u16 *)(smem + L_TM), 0, split, tid);
-  for (u32 i = tid; i < HSIZE; i += DT) dhead[i] = head[i];
-}
-// The same for a group of dictionaries (a dictionary set, zh_dictset.h): workgroup g builds
-// jobs[g]'s chains in its own staging area stg + g * stride.  A job with dP = 0 has none.
+// content) into dprev and the head table after them into dhead.  Workgroup g builds jobs[g]'s
+// chains (one job for a handle's own dictionary, a group of a dictionary set's, zh_dictset.h) in
+// its own staging area stg_all + g * stride.  A job with dP = 0 has none.
 extern "C" __global__ __launch_bounds__(DT) void zh_deep_dict_batch_kernel(const ZhDictBuildJob *__restrict__ jobs, u8 *stg_all, u32 stride) {
   extern __shared__ __attribute__((aligned(16))) u8 smem[];
   ZhDictBuildJob const job = jobs[blockIdx.x];
@@ -928,24 +917,16 @@ extern "C" __global__ __launch_bounds__(DT) void zh_deep_dict_batch_kernel(const
 }
 
 namespace zh {
-// chains of a dictionary's last min(cn, ZH_DEEP_PRE) content bytes: dprev u32[ZH_DEEP_PRE],
-// dhead u32[2^ZH_HASH_LOG_SHORT], stg >= ZH_DEEP_PRE + 64 bytes; P = 0: none (too short)
-static void deep_dict_split(size_t cn, u32 &P, u32 &split) {
+// The chains cover the last P = min(cn, ZH_DEEP_PRE) of cn content bytes, positions [0, split) of
+// them; 0, 0: none (too short)
+void lz_deep_dict_shape(size_t cn, u32 &P, u32 &split) {
   P = (u32)std::min(cn, (size_t)ZH_DEEP_PRE);
   split = (P > ZH_HASH_READ ? P - ZH_HASH_READ : 0u) & ~3u;
   if (split < 64) P = split = 0;
 }
-hipError_t lz_deep_dict_tables(const u8 *content, size_t cn, u8 *stg, u32 *dprev, u32 *dhead, u32 &P, u32 &split, hipStream_t stream) {
-  deep_dict_split(cn, P, split);
-  if (!P) return hipSuccess;
-  hipLaunchKernelGGL(zh_deep_dict_kernel, dim3(1), dim3(DT), DEEP_LDS, stream, content + cn - P, P, stg, dprev, dhead);
-  return hipGetLastError();
-}
-
-// the staged bytes and split lz_deep_dict_tables takes for cn content bytes (0, 0: no chains)
-void lz_deep_dict_shape(size_t cn, u32 &P, u32 &split) { deep_dict_split(cn, P, split); }
-// lz_deep_dict_tables for the `count` dictionaries of d_jobs (dtail = content + cn - dP, or dP = 0)
-// in one launch: stg = count x ZH_DEEP_DICT_STG bytes of staging
+// The chains of the `count` dictionaries of d_jobs (dtail = content + cn - dP, or dP = 0; dprev:
+// >= split u32, dhead: 2^ZH_HASH_LOG_SHORT u32) in one launch: stg = count x ZH_DEEP_DICT_STG
+// bytes of staging
 hipError_t lz_deep_dict_tables_batch(const ZhDictBuildJob *d_jobs, u32 count, u8 *stg, hipStream_t stream) {
   if (!count) return hipSuccess;
   hipLaunchKernelGGL(zh_deep_dict_batch_kernel, dim3(count), dim3(DT), DEEP_LDS, stream, d_jobs, stg, (u32)ZH_DEEP_DICT_STG);
@@ -956,7 +937,6 @@ hipError_t lz_deep_init() {
   hipError_t e = hipFuncSetAttribute((const void *)zh_lz_deep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_lz_deep_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_deep_dict_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_deep_dict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)zh_lz_deep_ranged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEEP_LDS);
   return e;
 }
@@ -1002,9 +982,9 @@ extern "C" int zh_test_deep_path(u32 pre, u32 nb, u32 s0, u32 *segl) {
   if (segl) *segl = dp.demand ? dp.segl : 64u;
   return (int)dp.path();
 }
-// The staged content bytes P and the split lz_deep_dict_tables takes for cn content bytes (0, 0:
+// The staged content bytes P and the split the chain builder takes for cn content bytes (0, 0:
 // no tables).
-extern "C" void zh_test_deep_split(u64 cn, u32 *P, u32 *split) { zh::deep_dict_split((size_t)cn, *P, *split); }
+extern "C" void zh_test_deep_split(u64 cn, u32 *P, u32 *split) { zh::lz_deep_dict_shape((size_t)cn, *P, *split); }
 // The deep matcher alone at search depth `depth` over single-block items: item i is the block
 // blk[i * blk_stride, + n[i]) (n <= ZH_BLOCK_MAX) staged behind the prefix pre[i * pre_stride,
 // + pre_n[i]) (host bytes; pre_n may be 0), both placed in device memory at byte offset align[i]
@@ -1013,8 +993,9 @@ extern "C" void zh_test_deep_split(u64 cn, u32 *P, u32 *split) { zh::deep_dict_s
 //     history and of a multi-block frame's later blocks.  One launch over all items on
 //     min(nitems, nslots) scratch slots; nslots = 1 runs the items in order in one slot.
 //   tables = 1: the prefix is a dictionary's content (any length; its last ZH_DEEP_PRE bytes are
-//     staged): lz_deep_dict_tables on it and ZH_F_DICT | ZH_F_FIRST | ZH_F_DEEP as zh_host.cpp
-//     sets them; one launch per item (the tables are one dictionary's).
+//     staged): its chains from lz_deep_dict_tables_batch (one ZhDictBuildJob per item) and ZH_F_DICT |
+//     ZH_F_FIRST | ZH_F_DEEP as zh_host.cpp sets them; one launch per item (the tables are one
+//     dictionary's).
 // Copied back per item as zh_test_lz does: ZH_SEQ_CAP records, ZH_LIT_BYTES of the literal area,
 // meta {nseq, nlit, rle}.  off (may be null; one item only): the slot's off << 8 | len of the n
 // block positions -- every position on the full-search paths, the searched ones on the demand path.
@@ -1033,13 +1014,14 @@ extern "C" int zh_test_lz_deep(const u8 *pre, const u32 *pre_n, u32 pre_stride, 
   ZhBlockDesc *dd = nullptr;
   u8 *in = nullptr, *base = nullptr, *slots = nullptr, *dstg = nullptr;
   u32 *ctr = nullptr, *dprev = nullptr, *dhead = nullptr;
+  ZhDictBuildJob *djob = nullptr;
   std::vector<ZhBlockDesc> descs(nitems);
   int rc = 0;
   if (zh::lz_deep_init() != hipSuccess || hipMalloc(&dd, sizeof(ZhBlockDesc) * nitems) != hipSuccess ||
       hipMalloc(&in, item_area * nitems) != hipSuccess || hipMalloc(&base, (size_t)ZH_WS_BLOCK_BYTES * nitems) != hipSuccess ||
       hipMalloc(&slots, ZH_DEEP_SLOT_BYTES * nslots) != hipSuccess || hipMalloc(&ctr, 4) != hipSuccess ||
       hipMalloc(&dprev, 4u * ZH_DEEP_PRE) != hipSuccess || hipMalloc(&dhead, 4u << ZH_HASH_LOG_SHORT) != hipSuccess ||
-      hipMalloc(&dstg, ZH_DEEP_PRE + 256) != hipSuccess) {
+      hipMalloc(&dstg, ZH_DEEP_DICT_STG) != hipSuccess || hipMalloc(&djob, sizeof(ZhDictBuildJob)) != hipSuccess) {
     rc = 1;
   } else {
     // (a fresh slot holds arbitrary bytes; the length caps keep them out of the result)
@@ -1075,9 +1057,15 @@ extern "C" int zh_test_lz_deep(const u8 *pre, const u32 *pre_n, u32 pre_stride, 
         u32 P = 0, split = 0;
         ZhWorkspace w1 = ws;
         w1.base = base + (size_t)i * ZH_WS_BLOCK_BYTES;
-        if (descs[i].pre_n &&
-            zh::lz_deep_dict_tables(descs[i].pre, descs[i].pre_n, dstg, dprev, dhead, P, split, nullptr) != hipSuccess) rc = 1;
+        zh::lz_deep_dict_shape(descs[i].pre_n, P, split);
         if (P) {
+          ZhDictBuildJob job{};
+          job.dtail = descs[i].pre + descs[i].pre_n - P;
+          job.dprev = dprev;
+          job.dhead = dhead;
+          job.dP = P;
+          if (hipMemcpy(djob, &job, sizeof(job), hipMemcpyHostToDevice) != hipSuccess ||
+              zh::lz_deep_dict_tables_batch(djob, 1, dstg, nullptr) != hipSuccess) rc = 1;
           w1.dd_prev = dprev;
           w1.dd_head = dhead;
           w1.dd_pre = P;
@@ -1105,5 +1093,6 @@ extern "C" int zh_test_lz_deep(const u8 *pre, const u32 *pre_n, u32 pre_stride, 
   (void)hipFree(dprev);
   (void)hipFree(dhead);
   (void)hipFree(dstg);
+  (void)hipFree(djob);
   return rc;
 }

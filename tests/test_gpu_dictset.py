@@ -163,11 +163,24 @@ def frame_dict_id(frame):
     return int.from_bytes(frame[at:at + n], "little") if n else 0
 
 
-def test_tables_equal_single_builders(libzstd):
-    """Every entry's K1 tables, deep-matcher links [0, split), head table, P and split: byte-equal to
-    what lz_dict_tables / lz_deep_dict_tables give that dictionary (zh_test_dictset_tables against
-    zh_test_dict_tables)."""
+@functools.lru_cache(maxsize=None)
+def table_entries():
+    """entries() and six more raw ones, so that content lengths 511, 512, 513, 65,535, 65,536, 65,537
+    and 131,072, a formatted dictionary, a constant byte and a period-3 pattern are all in one set."""
+    rng = np.random.default_rng(0x5EED0D30)
+    out = entries() + [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (513, 65535, 65536, 65537)]
+    out += [bytes([0x41]) * 4099, bytes([1, 2, 3]) * 1667]
+    assert all(T.dict_layout(e)[0] == 0 for e in out[NENT:])
+    return out
+
+
+def test_tables_equal_host_model(libzstd):
+    """Every dictionary's K1 tables, deep-matcher links [0, split), head table, P, dP and split equal
+    the host model (zh_dict_tables_model.py) exactly: through entry k of a set (zh_test_dictset_tables)
+    and through a handle's load of the same bytes (zh_test_dict_tables, a set of one), which alone
+    takes dictionaries under 256 bytes."""
     import cuda_zstd
+    import zh_dict_tables_model as M
 
     L = cuda_zstd.lib()
     vp, u32p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)
@@ -182,21 +195,42 @@ def test_tables_equal_single_builders(libzstd):
         assert call(*first, dtab.ctypes.data, ctypes.byref(P), prev.ctypes.data, head.ctypes.data, ctypes.byref(dP), ctypes.byref(split)) == 0
         return dtab, prev, head, P.value, dP.value, split.value
 
-    s = dset()
-    assert len(s) == NENT
+    def check(got, e, tag):
+        dtab, prev, head, P, dP, split = got
+        content = np.frombuffer(e, np.uint8)[T.dict_layout(e)[1]:]
+        cn = len(content)
+        wP, wtab = M.k1_tables(content)
+        wdP, wsplit, wprev, whead = M.deep_chains(content)
+        assert (P, dP, split) == (wP, wdP, wsplit), (tag, P, dP, split)
+        assert P == (0 if cn < 512 else min(cn, 65535)) and (dP, split) == ((0, 0) if cn < 72 else (min(cn, 65536), (min(cn, 65536) - 8) & ~3)), tag
+        if P:
+            assert np.array_equal(dtab, wtab), tag
+        else:  # untouched
+            assert bool((dtab == 0xBEEF).all()), tag
+        if dP:
+            assert np.array_equal(prev[:split], wprev) and np.array_equal(head, whead), tag
+        else:
+            assert bool((head == 0xDEADBEEF).all()), tag
+        assert bool((prev[split:] == 0xDEADBEEF).all()), tag
+        return P, dP
+
+    ents = table_entries()
+    s = cuda_zstd.DictionarySet([cuda_zstd.Dictionary.load(e) for e in ents])
+    assert len(s) == len(ents) == NENT + 6
     seen = []
-    for k, e in enumerate(entries()):
+    for k, e in enumerate(ents):
         buf = np.frombuffer(e, np.uint8).copy()
-        a = tables(L.zh_test_dictset_tables, s._h, k)
-        b = tables(L.zh_test_dict_tables, buf.ctypes.data, len(buf))
-        assert a[3:] == b[3:], k
-        P, dP, split = a[3:]
-        cn = len(e) - T.dict_layout(e)[1]
-        assert P == (0 if cn < 512 else min(cn, 65535)) and dP == min(cn, 65536) and split == (dP - 8) & ~3, (k, P, dP, split)
-        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1][:split], b[1][:split]) and np.array_equal(a[2], b[2]), k
-        assert (P == 0) == bool((a[0] == 0xBEEF).all()) and not (a[2] == 0xDEADBEEF).all()
-        seen.append((P, dP))
+        seen.append(check(tables(L.zh_test_dictset_tables, s._h, k), e, ("set", k)))
+        assert check(tables(L.zh_test_dict_tables, buf.ctypes.data, len(buf)), e, ("load", k)) == seen[-1]
+    s.close()
     assert seen[0][0] == 0 and seen[1][0] == 0 and seen[2][0] == 512 and seen[5] == (65535, 65536)
+    assert seen[NENT:] == [(513, 513), (65535, 65535), (65535, 65536), (65535, 65536), (4099, 4099), (5001, 5001)]
+    assert 0 < seen[JSON_D][0] < 16384 and 0 < seen[TEXT_D][0] < 16384  # the formatted entries: their content alone
+    # a handle's dictionary may be shorter than a set's entries: no chains below 72 bytes
+    rng = np.random.default_rng(0x5EED0D31)
+    small = {n: rng.integers(0, 256, n, dtype=np.uint8) for n in (1, 71, 72, 75, 255)}
+    got = {n: check(tables(L.zh_test_dict_tables, b.ctypes.data, n), b.tobytes(), ("load", n)) for n, b in small.items()}
+    assert got == {1: (0, 0), 71: (0, 0), 72: (0, 72), 75: (0, 75), 255: (0, 255)}
 
 
 @pytest.mark.parametrize("level,max_chunk,checksum", [(1, 65536, False), (3, 65536, False), (3, 32768, False), (3, 65536, True), (5, 65536, False),

@@ -8,13 +8,11 @@ across round, span and window boundaries, a queue that fills more than once per 
 different long / short candidates, exact match lengths around the 5- and 8-byte minimums and the
 64-byte cap, matches that end at the block's last byte, and a window whose tables stay empty up to
 its last tile.  Every comparison is exact."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 import zh_testlib as T
+from zh_hash_model import P, hash_long, hash_short
 from test_gpu_k1 import _compare, k1_raw, oracle_parse  # noqa: F401  (k1_raw, oracle_parse: _compare's parts)
 
 pytestmark = pytest.mark.gpu
@@ -24,32 +22,7 @@ W = 2048    # K1's window
 TILE = 128  # hash insertion granularity
 
 
-def _params():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = open(os.path.join(root, "include", "zstd_hip_params.h")).read()
-    return {k: int(v, 0) for k, v in re.findall(r"#define (ZH_HK_[LS]\d|ZH_HASH_LOG_LONG|ZH_HASH_LOG_SHORT|ZH_WINDOW|ZH_TILE)\s+(\w+?)u?\s", txt)}
-
-
-P = _params()
 assert P["ZH_WINDOW"] == W and P["ZH_TILE"] == TILE
-
-
-def _le(b, lo, n):
-    v = np.zeros(b.shape[:-1], dtype=np.uint64)
-    for k in range(n):
-        v |= b[..., lo + k].astype(np.uint64) << np.uint64(8 * k)
-    return v
-
-
-def hash_long(b):
-    """The long table's slot of the 8 bytes b[..., 0:8] (include/zstd_hip_params.h)."""
-    t = _le(b, 0, 3) * np.uint64(P["ZH_HK_L0"]) + _le(b, 3, 3) * np.uint64(P["ZH_HK_L1"]) + _le(b, 6, 2) * np.uint64(P["ZH_HK_L2"])
-    return (t & np.uint64(0xFFFFFFFF)) >> np.uint64(32 - P["ZH_HASH_LOG_LONG"])
-
-
-def hash_short(b):
-    t = _le(b, 0, 3) * np.uint64(P["ZH_HK_S0"]) + _le(b, 3, 2) * np.uint64(P["ZH_HK_S1"])
-    return (t & np.uint64(0xFFFFFFFF)) >> np.uint64(32 - P["ZH_HASH_LOG_SHORT"])
 
 
 def _filler(seed, n):

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Resource figures of the kernels in a gfx950 code object, from its AMDGPU metadata note:
-VGPRs, SGPRs, LDS bytes (group segment), scratch bytes (private segment).
+VGPRs, SGPRs, LDS bytes (group segment), scratch bytes (private segment), and each kernel's code
+bytes from the symbol table.
 
   hipcc --offload-arch=gfx950 --cuda-device-only --no-gpu-bundle-output -O3 -std=c++17 \\
         -I../include -Icsrc -c csrc/zh_decode.hip -o dec.co
   tools/kernel_meta.py dec.co [name-prefix]
 
-Prints one JSON object {kernel: {"vgpr", "sgpr", "lds", "scratch"}}.  Two builds (two commits) are
+Prints one JSON object {kernel: {"vgpr", "sgpr", "lds", "scratch", "code"}}.  Two builds (two commits) are
 compared by comparing the two objects; nothing runs on a GPU."""
 import json
 import re
@@ -36,6 +37,11 @@ def kernel_meta(path, prefix=""):
             if cur["name"].startswith(prefix):
                 out[cur.pop("name")] = cur
             cur = {}
+    syms = subprocess.run([READELF, "--symbols", "--wide", path], check=True, capture_output=True, text=True).stdout
+    for line in syms.splitlines():  # Num: Value Size Type Bind Vis Ndx Name
+        f = line.split()
+        if len(f) == 8 and f[3] == "FUNC" and f[7] in out:
+            out[f[7]]["code"] = int(f[2], 0)
     return out
 
 
