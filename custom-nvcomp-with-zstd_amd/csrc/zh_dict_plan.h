@@ -107,37 +107,116 @@ struct CoverCtl {  // the trainer's state in device memory
   uint32_t done;
 };
 
+// ---- groups: one dictionary per run of consecutive samples ------------------------------------
+// The samples of all groups lie back to back; group g owns the positions [base, base + plan.N) of
+// the concatenation.  Epochs, windows and commits are cover_epoch / cover_range /
+// cover_commit_bytes in group-local positions; only the loads of dm, prev and the corpus add base,
+// and the look-back of a position stops at its group's first one (cover_lookback).  One
+// dictionary from all samples is the call with one group.
+constexpr size_t kCoverGroupsInFlight = 64;  // slots of per-group state; more groups run as successive waves
+constexpr size_t kCoverMaxGroups = 4096;     // what a dictionary set holds
+
+struct CoverGroup {
+  CoverPlan plan;  // cover_plan(the group's own bytes, dict_size, k, d)
+  uint64_t base;   // its first position in the concatenation
+  uint32_t s0, s1;  // its samples [s0, s1)
+  uint32_t slot;    // its slot of the per-group temp arrays: g % kCoverGroupsInFlight
+  uint32_t ntiles;  // scan tiles of one of its epochs (its windows plus the entry after the last one)
+};
+
+ZH_PLAN_HD inline size_t cover_scan_tiles(const CoverPlan &p) { return (p.esz + 1 + kCoverScanTile - 1) / kCoverScanTile; }
+
+// records of the ng groups of counts[g] consecutive samples each (the counts sum to the number
+// of sizes); returns the bytes of all samples
+inline uint64_t cover_groups(const size_t *sizes, const size_t *counts, size_t ng, size_t dict_size, uint32_t k, uint32_t d, CoverGroup *out) {
+  uint64_t base = 0;
+  size_t s = 0;
+  for (size_t g = 0; g < ng; g++) {
+    uint64_t n = 0;
+    for (size_t j = 0; j < counts[g]; j++) n += sizes[s + j];
+    CoverGroup &G = out[g];
+    G.plan = cover_plan((size_t)n, dict_size, k, d);
+    G.base = base;
+    G.s0 = (uint32_t)s;
+    G.s1 = (uint32_t)(s + counts[g]);
+    G.slot = (uint32_t)(g % kCoverGroupsInFlight);
+    G.ntiles = (uint32_t)cover_scan_tiles(G.plan);
+    s += counts[g];
+    base += n;
+  }
+  return base;
+}
+
+// farthest look-back of the group-local position `local`: inside the segment and inside the group
+ZH_PLAN_HD inline uint32_t cover_lookback(size_t seg, uint64_t local) { return (uint32_t)(local < seg - 1 ? local : seg - 1); }
+
+// waves of at most kCoverGroupsInFlight groups: wave w holds the groups [w * 64, min(ng, w * 64 + 64))
+ZH_PLAN_HD inline size_t cover_waves(size_t ng) { return (ng + kCoverGroupsInFlight - 1) / kCoverGroupsInFlight; }
+
 struct CoverTempLayout {
-  size_t ctl, ends, dm, prev, freq, diff, tsum, tbest, dict;  // byte offsets, each a multiple of 256
-  size_t ntiles;  // scan tiles of one epoch
+  // byte offsets, each a multiple of 256.  groups, ends, dm and prev belong to the call; ctl, freq,
+  // diff, tsum, tbest and dict hold `slots` slots of the strides below, the offset being slot 0's
+  size_t groups, ends, dm, prev, ctl, freq, diff, tsum, tbest, dict;
+  size_t slots;   // groups in flight
+  size_t ntiles;  // scan tiles of one epoch of the largest group
+  size_t freq_stride, diff_stride, tsum_stride, tbest_stride, dict_stride;  // bytes (ctl: sizeof(CoverCtl))
   size_t total;
 };
 
 ZH_PLAN_HD inline size_t cover_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-ZH_PLAN_HD inline CoverTempLayout cover_temp_layout(const CoverPlan &p, size_t num_samples, size_t dict_size) {
+// total_bytes: the bytes of all samples; max_ntiles: the largest cover_scan_tiles of the groups
+ZH_PLAN_HD inline CoverTempLayout cover_temp_layout(size_t total_bytes, size_t num_samples, size_t num_groups, size_t max_ntiles,
+                                                    size_t dict_size) {
   CoverTempLayout L;
   size_t o = 0;
-  L.ctl = o, o += 256;
+  L.slots = num_groups < kCoverGroupsInFlight ? num_groups : kCoverGroupsInFlight;
+  L.ntiles = max_ntiles;
+  L.groups = o, o += cover_align256(num_groups * sizeof(CoverGroup));
   L.ends = o, o += cover_align256(num_samples * 4);
-  L.dm = o, o += cover_align256(p.nd * 4);
-  L.prev = o, o += cover_align256(p.nd * 2);
-  L.freq = o, o += ((size_t)4 << kCoverHashBits);
-  // one epoch's windows plus the entry after the last one
-  L.ntiles = (p.esz + 1 + kCoverScanTile - 1) / kCoverScanTile;
-  L.diff = o, o += L.ntiles * kCoverScanTile * 8;
-  L.tsum = o, o += cover_align256(L.ntiles * 8);
-  L.tbest = o, o += cover_align256(L.ntiles * 16);
-  L.dict = o, o += cover_align256(dict_size);
+  L.dm = o, o += cover_align256(total_bytes * 4);
+  L.prev = o, o += cover_align256(total_bytes * 2);
+  L.ctl = o, o += cover_align256(L.slots * sizeof(CoverCtl));
+  L.freq_stride = (size_t)4 << kCoverHashBits;
+  L.freq = o, o += L.slots * L.freq_stride;
+  L.diff_stride = L.ntiles * kCoverScanTile * 8;
+  L.diff = o, o += L.slots * L.diff_stride;
+  L.tsum_stride = cover_align256(L.ntiles * 8);
+  L.tsum = o, o += L.slots * L.tsum_stride;
+  L.tbest_stride = cover_align256(L.ntiles * 16);
+  L.tbest = o, o += L.slots * L.tbest_stride;
+  L.dict_stride = cover_align256(dict_size);
+  L.dict = o, o += L.slots * L.dict_stride;
   L.total = o + 256;  // the caller's pointer is aligned up to 256
   return L;
 }
 
-// what cuda_zstd_train_dictionary_device_get_temp_size reports: enough for every d of [4, 8]
+// what cuda_zstd_train_dictionaries_device_get_temp_size reports: enough for every d of [4, 8]
+inline size_t cover_temp_bytes(const size_t *sizes, size_t num_samples, const size_t *counts, size_t num_groups, size_t dict_size, uint32_t k) {
+  size_t m = 0;
+  for (uint32_t d = 4; d <= 8; d++) {
+    size_t s = 0, nt = 0;
+    uint64_t total = 0;
+    for (size_t g = 0; g < num_groups; g++) {
+      uint64_t n = 0;
+      for (size_t j = 0; j < counts[g]; j++) n += sizes[s + j];
+      s += counts[g];
+      total += n;
+      size_t const t = cover_scan_tiles(cover_plan((size_t)n, dict_size, k ? k : kCoverDefaultK, d));
+      if (t > nt) nt = t;
+    }
+    size_t const t = cover_temp_layout((size_t)total, num_samples, num_groups, nt, dict_size).total;
+    if (t > m) m = t;
+  }
+  return m;
+}
+
+// what cuda_zstd_train_dictionary_device_get_temp_size reports: the call with one group
 inline size_t cover_temp_bytes(size_t total_sample_bytes, size_t num_samples, size_t dict_size, uint32_t k) {
   size_t m = 0;
   for (uint32_t d = 4; d <= 8; d++) {
-    size_t const t = cover_temp_layout(cover_plan(total_sample_bytes, dict_size, k ? k : kCoverDefaultK, d), num_samples, dict_size).total;
+    size_t const nt = cover_scan_tiles(cover_plan(total_sample_bytes, dict_size, k ? k : kCoverDefaultK, d));
+    size_t const t = cover_temp_layout(total_sample_bytes, num_samples, 1, nt, dict_size).total;
     if (t > m) m = t;
   }
   return m;

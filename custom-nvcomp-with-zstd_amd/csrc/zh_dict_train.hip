@@ -5,11 +5,12 @@
 //
 // Once per call
 //   zh_cover_ids_kernel      dm[i]: hashed d-mer id of every position (NONE across a sample end)
-//   zh_cover_freq_kernel     freq[h]: samples that contain bucket h; a workgroup walks whole
-//                            samples with a 2^20-bit set in LDS and clears only the bits it set
 //   zh_cover_prev_kernel     prevdist[i]: nearest earlier equal id within seg - 1 positions,
 //                            a backward look over a tile of dm and its halo (in LDS while
 //                            they fit in 64 KiB, from global memory for larger k)
+// Once per wave of groups
+//   zh_cover_freq_kernel     freq[h]: samples that contain bucket h; a workgroup walks whole
+//                            samples with a 2^20-bit set in LDS and clears only the bits it set
 // Once per epoch visit (the host trainer's loop body), all no-ops once the trainer is done
 //   zh_cover_contrib_kernel  +f / -f of every live position into the difference array
 //   zh_cover_tilesum_kernel  sum of each 2048-entry tile of it
@@ -18,6 +19,14 @@
 //   zh_cover_commit_kernel   one workgroup: the epoch's first maximum, trim, zero the segment's
 //                            frequencies, copy its bytes in front of the dictionary's tail
 // Scores are sums of frequencies (at most num_samples * seg): the accumulators are 64-bit.
+//
+// One call trains one dictionary per group of consecutive samples (zh_dict_plan.h, CoverGroup);
+// a single dictionary is the call with one group.  ids and prevdist run once over the whole
+// concatenation (a d-mer never crosses a sample end, so one ends array gives every group's ids;
+// the look-back stops at the group's first position).  The other kernels take the group from
+// blockIdx.y: the groups of a wave (at most 64) share each launch, every group with its own
+// CoverCtl, freq, diff, tsum, tbest and dict slot, and a workgroup past its group's samples or
+// tiles, or of a group that is done, returns at once.
 #include "zh_common.h"
 #include "zh_dict_train.h"
 #include "zh_scan.h"
@@ -28,6 +37,7 @@ namespace {
 
 using zh::CoverCtl;
 using zh::CoverEpoch;
+using zh::CoverGroup;
 using zh::CoverPlan;
 using zh::kCoverNone;
 
@@ -89,6 +99,18 @@ __device__ __forceinline__ u32 block_min32(u32 v, u32 *lds) {
   return m;
 }
 
+// the per-group arrays of the temp buffer: slot 0 and the byte strides of cover_temp_layout
+struct Slots {
+  u8 *ctl, *freq, *diff, *tsum, *tbest, *dict;
+  u64 freq_stride, diff_stride, tsum_stride, tbest_stride, dict_stride;
+  __host__ __device__ CoverCtl *ctl_of(u32 s) const { return (CoverCtl *)ctl + s; }
+  __host__ __device__ u32 *freq_of(u32 s) const { return (u32 *)(freq + s * freq_stride); }
+  __host__ __device__ u64 *diff_of(u32 s) const { return (u64 *)(diff + s * diff_stride); }
+  __host__ __device__ u64 *tsum_of(u32 s) const { return (u64 *)(tsum + s * tsum_stride); }
+  __host__ __device__ TileBest *tbest_of(u32 s) const { return (TileBest *)(tbest + s * tbest_stride); }
+  __host__ __device__ u8 *dict_of(u32 s) const { return dict + s * dict_stride; }
+};
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -123,31 +145,9 @@ extern "C" __global__ __launch_bounds__(256) void zh_cover_ids_kernel(const u8 *
   dm[i] = id;
 }
 
-extern "C" __global__ __launch_bounds__(1024) void zh_cover_freq_kernel(const u32 *__restrict__ dm, const u32 *__restrict__ ends, u32 ns, u64 nd,
-                                                                        u32 *__restrict__ freq) {
-  extern __shared__ u32 bits[];  // FREQ_WORDS: the buckets seen in the current sample
-  u32 const tid = threadIdx.x;
-  for (u32 k = tid; k < FREQ_WORDS; k += FREQ_T) bits[k] = 0;
-  __syncthreads();
-  for (u32 s = blockIdx.x; s < ns; s += gridDim.x) {
-    u64 const a = s ? ends[s - 1] : 0u, e = min((u64)ends[s], nd);
-    for (u64 i = a + tid; i < e; i += FREQ_T) {
-      u32 const h = dm[i];
-      if (h == kCoverNone) continue;
-      u32 const m = 1u << (h & 31u);
-      if (!(atomicOr(&bits[h >> 5], m) & m)) atomicAdd(&freq[h], 1u);
-    }
-    __syncthreads();
-    for (u64 i = a + tid; i < e; i += FREQ_T) {  // every set bit of a word is this sample's
-      u32 const h = dm[i];
-      if (h != kCoverNone) bits[h >> 5] = 0;
-    }
-    __syncthreads();
-  }
-}
-
 template <bool IN_LDS>
-__global__ __launch_bounds__(256) void zh_cover_prev_kernel(const u32 *__restrict__ dm, u64 nd, u32 seg, u16 *__restrict__ prev) {
+__global__ __launch_bounds__(256) void zh_cover_prev_kernel(const u32 *__restrict__ dm, u64 nd, u32 seg, const CoverGroup *__restrict__ groups,
+                                                            u32 ng, u16 *__restrict__ prev) {
   extern __shared__ u32 win[];  // IN_LDS: dm[w0, tend)
   u32 const tid = threadIdx.x, halo = seg - 1;
   u64 const t0 = (u64)blockIdx.x * PREV_TILE, tend = min(t0 + PREV_TILE, nd);
@@ -163,7 +163,15 @@ __global__ __launch_bounds__(256) void zh_cover_prev_kernel(const u32 *__restric
     u32 const h = src[c];
     u32 r = 0;
     if (h != kCoverNone) {
-      u32 const maxj = (u32)min((u64)halo, i);
+      // the group that holds i: the last whose base is not past it (groups without bytes share
+      // their base with the next one, which is as good)
+      u32 lo = 0, hi = ng - 1;
+      while (lo < hi) {
+        u32 const mid = lo + ((hi - lo + 1) >> 1);
+        if (groups[mid].base <= i) lo = mid;
+        else hi = mid - 1;
+      }
+      u32 const maxj = zh::cover_lookback(seg, i - groups[lo].base);  // <= min(halo, i)
       u32 j = 1;
       for (; j + 3 <= maxj; j += 4) {
         u32 const x0 = src[c - j], x1 = src[c - j - 1], x2 = src[c - j - 2], x3 = src[c - j - 3];
@@ -182,42 +190,83 @@ __global__ __launch_bounds__(256) void zh_cover_prev_kernel(const u32 *__restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// one epoch visit
+// once per wave of groups: blockIdx.y is the group of the wave
 // ---------------------------------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(256) void zh_cover_contrib_kernel(const CoverCtl *__restrict__ ctl, CoverPlan p,
-                                                                          const u32 *__restrict__ dm, const u16 *__restrict__ prev,
-                                                                          const u32 *__restrict__ freq, u64 *__restrict__ diff) {
+extern "C" __global__ __launch_bounds__(1024) void zh_cover_freq_kernel(const CoverGroup *__restrict__ groups, Slots S,
+                                                                        const u32 *__restrict__ dm, const u32 *__restrict__ ends) {
+  extern __shared__ u32 bits[];  // FREQ_WORDS: the buckets seen in the current sample
+  CoverGroup const &g = groups[blockIdx.y];
+  // = g.slot, as a wave starts at a multiple of the slot count: the slot's addresses do not wait for the load of g
+  u32 const slot = blockIdx.y;
+  if (g.plan.empty || g.s0 + blockIdx.x >= g.s1) return;
+  u32 const tid = threadIdx.x;
+  u32 *const freq = S.freq_of(slot);
+  u64 const gend = g.base + g.plan.nd;  // the group's last d-mer starts before it
+  for (u32 k = tid; k < FREQ_WORDS; k += FREQ_T) bits[k] = 0;
+  __syncthreads();
+  for (u32 s = g.s0 + blockIdx.x; s < g.s1; s += gridDim.x) {
+    u64 const a = s ? ends[s - 1] : 0u, e = min((u64)ends[s], gend);
+    for (u64 i = a + tid; i < e; i += FREQ_T) {
+      u32 const h = dm[i];
+      if (h == kCoverNone) continue;
+      u32 const m = 1u << (h & 31u);
+      if (!(atomicOr(&bits[h >> 5], m) & m)) atomicAdd(&freq[h], 1u);
+    }
+    __syncthreads();
+    for (u64 i = a + tid; i < e; i += FREQ_T) {  // every set bit of a word is this sample's
+      u32 const h = dm[i];
+      if (h != kCoverNone) bits[h >> 5] = 0;
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// one epoch visit of every group of the wave: positions, windows and tiles are group-local, the
+// loads of dm, prev and the corpus add the group's base
+// ---------------------------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(256) void zh_cover_contrib_kernel(const CoverGroup *__restrict__ groups, Slots S,
+                                                                          const u32 *__restrict__ dm, const u16 *__restrict__ prev) {
+  CoverGroup const &g = groups[blockIdx.y];
+  u32 const slot = blockIdx.y;  // = g.slot
+  const CoverCtl *const ctl = S.ctl_of(slot);
   if (ctl->done) return;
-  CoverEpoch const ep = zh::cover_epoch(p, ctl->epoch);
+  CoverEpoch const ep = zh::cover_epoch(g.plan, ctl->epoch);
   u64 const i = ep.b + (u64)blockIdx.x * CT + threadIdx.x;
   if (i >= ep.end) return;
-  u32 const h = dm[i];
+  u32 const h = dm[g.base + i];
   if (h == kCoverNone) return;
-  u64 const f = freq[h];
+  u64 const f = S.freq_of(slot)[h];
   if (!f) return;
   size_t lo, hi;
-  if (!zh::cover_range(i, prev[i], p.seg, ep, lo, hi)) return;
-  // lo - b <= hi + 1 - b <= wmax + 1 - b <= esz: inside the ntiles * 2048 entries of diff
+  if (!zh::cover_range(i, prev[g.base + i], g.plan.seg, ep, lo, hi)) return;
+  // lo - b <= hi + 1 - b <= wmax + 1 - b <= esz: inside the group's ntiles * 2048 entries of diff
+  u64 *const diff = S.diff_of(slot);
   atomicAdd((unsigned long long *)&diff[lo - ep.b], (unsigned long long)f);
   atomicAdd((unsigned long long *)&diff[hi + 1 - ep.b], (unsigned long long)(0ull - f));
 }
 
-extern "C" __global__ __launch_bounds__(256) void zh_cover_tilesum_kernel(const CoverCtl *__restrict__ ctl, const u64 *__restrict__ diff,
-                                                                          u64 *__restrict__ tsum) {
+extern "C" __global__ __launch_bounds__(256) void zh_cover_tilesum_kernel(const CoverGroup *__restrict__ groups, Slots S) {
   __shared__ u64 lds[CT / 64];
-  if (ctl->done) return;
-  const u64 *const q = diff + (size_t)blockIdx.x * zh::kCoverScanTile + (size_t)threadIdx.x * SCAN_PER_THREAD;
+  CoverGroup const &g = groups[blockIdx.y];
+  u32 const slot = blockIdx.y;  // = g.slot
+  if (blockIdx.x >= g.ntiles || S.ctl_of(slot)->done) return;
+  const u64 *const q = S.diff_of(slot) + (size_t)blockIdx.x * zh::kCoverScanTile + (size_t)threadIdx.x * SCAN_PER_THREAD;
   u64 s = 0;
 #pragma unroll
   for (u32 j = 0; j < SCAN_PER_THREAD; j++) s += q[j];
   u64 total;
   (void)block_scan_excl64(s, lds, total);
-  if (threadIdx.x == 0) tsum[blockIdx.x] = total;
+  if (threadIdx.x == 0) S.tsum_of(slot)[blockIdx.x] = total;
 }
 
-extern "C" __global__ __launch_bounds__(256) void zh_cover_tilescan_kernel(const CoverCtl *__restrict__ ctl, u64 *__restrict__ tsum, u32 ntiles) {
+extern "C" __global__ __launch_bounds__(256) void zh_cover_tilescan_kernel(const CoverGroup *__restrict__ groups, Slots S) {
   __shared__ u64 lds[CT / 64];
-  if (ctl->done) return;
+  CoverGroup const &g = groups[blockIdx.y];
+  u32 const slot = blockIdx.y;  // = g.slot
+  if (S.ctl_of(slot)->done) return;
+  u64 *const tsum = S.tsum_of(slot);
+  u32 const ntiles = g.ntiles;
   u64 carry = 0;
   for (u32 t0 = 0; t0 < ntiles; t0 += CT) {
     u32 const t = t0 + threadIdx.x;
@@ -229,15 +278,17 @@ extern "C" __global__ __launch_bounds__(256) void zh_cover_tilescan_kernel(const
   }
 }
 
-extern "C" __global__ __launch_bounds__(256) void zh_cover_argmax_kernel(const CoverCtl *__restrict__ ctl, CoverPlan p, u64 *__restrict__ diff,
-                                                                         const u64 *__restrict__ tsum, TileBest *__restrict__ tbest) {
+extern "C" __global__ __launch_bounds__(256) void zh_cover_argmax_kernel(const CoverGroup *__restrict__ groups, Slots S) {
   __shared__ u64 lds[CT / 64];
   __shared__ u32 ldw[CT / 64];
-  if (ctl->done) return;
-  CoverEpoch const ep = zh::cover_epoch(p, ctl->epoch);
+  CoverGroup const &g = groups[blockIdx.y];
+  u32 const slot = blockIdx.y;  // = g.slot
+  const CoverCtl *const ctl = S.ctl_of(slot);
+  if (blockIdx.x >= g.ntiles || ctl->done) return;
+  CoverEpoch const ep = zh::cover_epoch(g.plan, ctl->epoch);
   u64 const nw = ep.wmax - ep.b + 1;
   u64 const i0 = (u64)blockIdx.x * zh::kCoverScanTile + (u64)threadIdx.x * SCAN_PER_THREAD;
-  u64 *const q = diff + i0;
+  u64 *const q = S.diff_of(slot) + i0;
   u64 v[SCAN_PER_THREAD], s = 0;
 #pragma unroll
   for (u32 j = 0; j < SCAN_PER_THREAD; j++) {
@@ -246,7 +297,7 @@ extern "C" __global__ __launch_bounds__(256) void zh_cover_argmax_kernel(const C
     s += v[j];
   }
   u64 total;
-  u64 run = tsum[blockIdx.x] + block_scan_excl64(s, lds, total);
+  u64 run = S.tsum_of(slot)[blockIdx.x] + block_scan_excl64(s, lds, total);
   u64 best = 0;
   u32 bw = ~0u;
 #pragma unroll
@@ -263,23 +314,29 @@ extern "C" __global__ __launch_bounds__(256) void zh_cover_argmax_kernel(const C
     b.score = best;
     b.w = bw;
     b.pad = 0;
-    tbest[blockIdx.x] = b;
+    S.tbest_of(slot)[blockIdx.x] = b;
   }
 }
 
-extern "C" __global__ __launch_bounds__(256) void zh_cover_commit_kernel(CoverCtl *__restrict__ ctl, CoverPlan p, u32 ntiles,
-                                                                         const TileBest *__restrict__ tbest, const u32 *__restrict__ dm,
-                                                                         u32 *__restrict__ freq, const u8 *__restrict__ corpus,
-                                                                         u8 *__restrict__ dict) {
+extern "C" __global__ __launch_bounds__(256) void zh_cover_commit_kernel(const CoverGroup *__restrict__ groups, Slots S,
+                                                                         const u32 *__restrict__ dm, const u8 *__restrict__ corpus) {
   __shared__ u64 lds[CT / 64];
   __shared__ u32 ldw[CT / 64];
   u32 const tid = threadIdx.x;
+  CoverGroup const &g = groups[blockIdx.y];
+  u32 const slot = blockIdx.y;  // = g.slot
+  CoverCtl *const ctl = S.ctl_of(slot);
   if (ctl->done) return;
+  CoverPlan const &p = g.plan;
+  const TileBest *const tbest = S.tbest_of(slot);
+  u32 *const freq = S.freq_of(slot);
+  const u32 *const gdm = dm + g.base;  // the group's ids and bytes, by group-local position
+  const u8 *const gcorpus = corpus + g.base;
   u32 const e = ctl->epoch, tail = ctl->tail, zero_run = ctl->zero_run;
   CoverEpoch const ep = zh::cover_epoch(p, e);
   u64 best = 0;
   u32 bw = ~0u;
-  for (u32 t = tid; t < ntiles; t += CT) best_merge(best, bw, tbest[t].score, tbest[t].w);
+  for (u32 t = tid; t < g.ntiles; t += CT) best_merge(best, bw, tbest[t].score, tbest[t].w);
   block_best(best, bw, lds, ldw);  // (its barriers also order the reads of ctl above before the writes below)
   u32 const next = (u32)((e + 1) % p.epochs);
   if (best == 0) {
@@ -295,7 +352,7 @@ extern "C" __global__ __launch_bounds__(256) void zh_cover_commit_kernel(CoverCt
   u32 const len = (u32)(se0 - sb0);
   u32 first = len, last1 = 0;  // first live offset; 1 + the last live offset (max as min of the complement)
   for (u32 o = tid; o < len; o += CT) {
-    u32 const h = dm[sb0 + o];
+    u32 const h = gdm[sb0 + o];
     if (h != kCoverNone && freq[h] != 0) {
       first = min(first, o);
       last1 = max(last1, o + 1);
@@ -306,7 +363,7 @@ extern "C" __global__ __launch_bounds__(256) void zh_cover_commit_kernel(CoverCt
   u64 const sb = sb0 + first, se = last1 > first ? sb0 + last1 : sb;  // (none live: empty, as the host's loops leave it)
   __syncthreads();  // every read of freq is done
   for (u64 i = sb + tid; i < se; i += CT) {
-    u32 const h = dm[i];
+    u32 const h = gdm[i];
     if (h != kCoverNone) freq[h] = 0;
   }
   size_t const bytes = zh::cover_commit_bytes(sb, se, p.d, tail);
@@ -315,8 +372,9 @@ extern "C" __global__ __launch_bounds__(256) void zh_cover_commit_kernel(CoverCt
     return;
   }
   u32 const ntail = tail - (u32)bytes;
-  // sb + bytes <= se + d - 1 <= nd + d - 1 = N; ntail + bytes = tail <= dict_size
-  for (u32 o = tid; o < (u32)bytes; o += CT) dict[ntail + o] = corpus[sb + o];
+  // sb + bytes <= se + d - 1 <= nd + d - 1 = N of the group; ntail + bytes = tail <= dict_size
+  u8 *const dict = S.dict_of(slot);
+  for (u32 o = tid; o < (u32)bytes; o += CT) dict[ntail + o] = gcorpus[sb + o];
   if (tid == 0) {
     ctl->tail = ntail;
     ctl->zero_run = 0;
@@ -327,12 +385,23 @@ extern "C" __global__ __launch_bounds__(256) void zh_cover_commit_kernel(CoverCt
 
 namespace zh {
 
-hipError_t cover_train_device(const uint8_t *d_corpus, const uint32_t *ends, size_t ns, const CoverPlan &plan, size_t dict_size, void *temp,
-                              hipStream_t stream, std::vector<uint8_t> &out, float *phase_ms) {
-  out.clear();
-  if (!d_corpus || !ends || !ns || !temp || plan.empty || plan.k > kCoverMaxK || ns >= (1ull << 32) || plan.N >= (1ull << 32) - 64 ||
-      dict_size >= (1ull << 32))
+hipError_t cover_train_groups_device(const uint8_t *d_corpus, const uint32_t *ends, size_t ns, const CoverGroup *groups, size_t ng,
+                                     size_t dict_size, void *temp, hipStream_t stream, std::vector<std::vector<uint8_t>> &out, float *phase_ms) {
+  out.assign(ng, std::vector<uint8_t>());
+  if (phase_ms) phase_ms[0] = phase_ms[1] = phase_ms[2] = 0.f;
+  if (!d_corpus || !ends || !ns || !groups || !ng || ng > kCoverMaxGroups || !temp || ns >= (1ull << 32) || dict_size >= (1ull << 32))
     return hipErrorInvalidValue;
+  u64 const N = groups[ng - 1].base + groups[ng - 1].plan.N;
+  if (N >= (1ull << 32) - 64 || groups[0].plan.k > kCoverMaxK || groups[ng - 1].s1 != ns) return hipErrorInvalidValue;
+  size_t max_ntiles = 0;
+  bool any = false;
+  for (size_t g = 0; g < ng; g++) {
+    max_ntiles = std::max<size_t>(max_ntiles, groups[g].ntiles);
+    any = any || !groups[g].plan.empty;
+  }
+  if (!any) return hipSuccess;  // every group has fewer than k bytes: the host trainer's empty results
+  // ids and prevdist of the whole concatenation: k, d, the mask and seg are the same in every plan
+  CoverPlan const whole = cover_plan((size_t)N, dict_size, groups[0].plan.k, groups[0].plan.d);
   // (per device, so set on every call; it costs no launch)
   hipError_t const ia = hipFuncSetAttribute((const void *)zh_cover_freq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FREQ_LDS);
   if (ia != hipSuccess) return ia;
@@ -341,18 +410,22 @@ hipError_t cover_train_device(const uint8_t *d_corpus, const uint32_t *ends, siz
   else (void)hipGetDevice(&dev);
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
 
-  CoverTempLayout const L = cover_temp_layout(plan, ns, dict_size);
+  CoverTempLayout const L = cover_temp_layout((size_t)N, ns, ng, max_ntiles, dict_size);
   u8 *const base = (u8 *)(((uintptr_t)temp + 255) & ~(uintptr_t)255);
-  CoverCtl *const ctl = (CoverCtl *)(base + L.ctl);
-  u32 *const d_ends = (u32 *)(base + L.ends), *const dm = (u32 *)(base + L.dm), *const freq = (u32 *)(base + L.freq);
+  CoverGroup *const d_groups = (CoverGroup *)(base + L.groups);
+  u32 *const d_ends = (u32 *)(base + L.ends), *const dm = (u32 *)(base + L.dm);
   u16 *const prev = (u16 *)(base + L.prev);
-  u64 *const diff = (u64 *)(base + L.diff), *const tsum = (u64 *)(base + L.tsum);
-  TileBest *const tbest = (TileBest *)(base + L.tbest);
-  u8 *const dict = base + L.dict;
-  u32 const ntiles = (u32)L.ntiles;
+  Slots S;
+  S.ctl = base + L.ctl, S.freq = base + L.freq, S.diff = base + L.diff, S.tsum = base + L.tsum, S.tbest = base + L.tbest, S.dict = base + L.dict;
+  S.freq_stride = L.freq_stride, S.diff_stride = L.diff_stride, S.tsum_stride = L.tsum_stride, S.tbest_stride = L.tbest_stride;
+  S.dict_stride = L.dict_stride;
 
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  CoverCtl h_ctl = {(u32)dict_size, 0u, 0u, 0u};
+  // the host sides of every copy below live until the function's last synchronisation
+  std::vector<CoverCtl> ctl0(ng), h_ctl(L.slots);
+  for (size_t g = 0; g < ng; g++) ctl0[g] = CoverCtl{(u32)dict_size, 0u, 0u, groups[g].plan.empty ? 1u : 0u};
+  std::vector<u8> h_dict(L.slots * L.dict_stride);
+
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // call: 0 ids 1 prev 2; wave: 3 freq 4 steps 5
   hipError_t err = hipSuccess;
   auto ok = [&](hipError_t e) {
     if (err == hipSuccess && e != hipSuccess) err = e;
@@ -361,63 +434,97 @@ hipError_t cover_train_device(const uint8_t *d_corpus, const uint32_t *ends, siz
   auto mark = [&](int k) {
     if (phase_ms && err == hipSuccess) ok(hipEventRecord(ev[k], stream));
   };
+  auto add = [&](int phase, int k) {  // after a synchronisation
+    float ms = 0.f;
+    if (phase_ms && ok(hipEventElapsedTime(&ms, ev[k], ev[k + 1]))) phase_ms[phase] += ms;
+  };
   if (phase_ms)
     for (auto &e : ev) ok(hipEventCreate(&e));
 
-  ok(hipMemcpyAsync(ctl, &h_ctl, sizeof h_ctl, hipMemcpyHostToDevice, stream)) &&
-      ok(hipMemcpyAsync(d_ends, ends, ns * 4, hipMemcpyHostToDevice, stream)) &&
-      ok(hipMemsetAsync(freq, 0, (size_t)4 << kCoverHashBits, stream)) &&
-      ok(hipMemsetAsync(diff, 0, L.ntiles * kCoverScanTile * 8, stream));
+  ok(hipMemcpyAsync(d_groups, groups, ng * sizeof(CoverGroup), hipMemcpyHostToDevice, stream)) &&
+      ok(hipMemcpyAsync(d_ends, ends, ns * 4, hipMemcpyHostToDevice, stream));
   mark(0);
   if (err == hipSuccess) {
-    hipLaunchKernelGGL(zh_cover_ids_kernel, dim3((u32)((plan.nd + CT - 1) / CT)), dim3(CT), 0, stream, d_corpus, d_ends, (u32)ns, plan, dm);
-    hipLaunchKernelGGL(zh_cover_freq_kernel, dim3((u32)std::min<size_t>(ns, (size_t)cus)), dim3(FREQ_T), FREQ_LDS, stream, dm, d_ends, (u32)ns,
-                       (u64)plan.nd, freq);
+    hipLaunchKernelGGL(zh_cover_ids_kernel, dim3((u32)((whole.nd + CT - 1) / CT)), dim3(CT), 0, stream, d_corpus, d_ends, (u32)ns, whole, dm);
     ok(hipGetLastError());
   }
   mark(1);
   if (err == hipSuccess) {
-    u32 const grid = (u32)((plan.nd + PREV_TILE - 1) / PREV_TILE);
-    size_t const lds = (PREV_TILE + plan.seg - 1) * 4;
+    u32 const grid = (u32)((whole.nd + PREV_TILE - 1) / PREV_TILE);
+    size_t const lds = (PREV_TILE + whole.seg - 1) * 4;
     if (lds <= PREV_LDS_MAX)
-      hipLaunchKernelGGL(zh_cover_prev_kernel<true>, dim3(grid), dim3(CT), (u32)lds, stream, dm, (u64)plan.nd, (u32)plan.seg, prev);
+      hipLaunchKernelGGL(zh_cover_prev_kernel<true>, dim3(grid), dim3(CT), (u32)lds, stream, dm, (u64)whole.nd, (u32)whole.seg, d_groups, (u32)ng,
+                         prev);
     else
-      hipLaunchKernelGGL(zh_cover_prev_kernel<false>, dim3(grid), dim3(CT), 0, stream, dm, (u64)plan.nd, (u32)plan.seg, prev);
+      hipLaunchKernelGGL(zh_cover_prev_kernel<false>, dim3(grid), dim3(CT), 0, stream, dm, (u64)whole.nd, (u32)whole.seg, d_groups, (u32)ng, prev);
     ok(hipGetLastError());
   }
   mark(2);
-  // The flag comes back once per pass over the epochs (at most 64 steps, so a corpus of many
-  // epochs does not queue thousands of no-op steps behind a dictionary that is already full).
-  // Every step that is not a no-op shrinks tail or grows zero_run, so the loop ends.
-  size_t const pass = std::min<size_t>(plan.epochs, 64);
-  u32 const cgrid = (u32)((plan.esz + CT - 1) / CT);
-  while (err == hipSuccess && !h_ctl.done) {
-    for (size_t s = 0; s < pass; s++) {
-      hipLaunchKernelGGL(zh_cover_contrib_kernel, dim3(cgrid), dim3(CT), 0, stream, ctl, plan, dm, prev, freq, diff);
-      hipLaunchKernelGGL(zh_cover_tilesum_kernel, dim3(ntiles), dim3(CT), 0, stream, ctl, diff, tsum);
-      hipLaunchKernelGGL(zh_cover_tilescan_kernel, dim3(1), dim3(CT), 0, stream, ctl, tsum, ntiles);
-      hipLaunchKernelGGL(zh_cover_argmax_kernel, dim3(ntiles), dim3(CT), 0, stream, ctl, plan, diff, tsum, tbest);
-      hipLaunchKernelGGL(zh_cover_commit_kernel, dim3(1), dim3(CT), 0, stream, ctl, plan, ntiles, tbest, dm, freq, d_corpus, dict);
+
+  bool first_wave = true;
+  for (size_t g0 = 0; g0 < ng && err == hipSuccess; g0 += kCoverGroupsInFlight) {
+    u32 const gn = (u32)std::min<size_t>(kCoverGroupsInFlight, ng - g0);
+    // what the launches of this wave must cover: its live groups' samples, epochs, positions and tiles
+    size_t samples = 0, epochs = 0, esz = 0, ntiles = 0;
+    for (u32 j = 0; j < gn; j++) {
+      CoverGroup const &G = groups[g0 + j];
+      if (G.plan.empty) continue;
+      samples = std::max<size_t>(samples, G.s1 - G.s0);
+      epochs = std::max(epochs, G.plan.epochs);
+      esz = std::max(esz, G.plan.esz);
+      ntiles = std::max<size_t>(ntiles, G.ntiles);
     }
-    ok(hipGetLastError()) && ok(hipMemcpyAsync(&h_ctl, ctl, sizeof h_ctl, hipMemcpyDeviceToHost, stream)) && ok(hipStreamSynchronize(stream));
-  }
-  mark(3);
-  if (err == hipSuccess && h_ctl.tail <= dict_size) {
-    out.resize(dict_size - h_ctl.tail);
-    if (!out.empty()) ok(hipMemcpyAsync(out.data(), dict + h_ctl.tail, out.size(), hipMemcpyDeviceToHost, stream));
+    if (!samples) continue;  // no live group
+    const CoverGroup *const wg = d_groups + g0;
+    ok(hipMemcpyAsync(S.ctl, &ctl0[g0], gn * sizeof(CoverCtl), hipMemcpyHostToDevice, stream)) &&
+        ok(hipMemsetAsync(S.freq, 0, gn * L.freq_stride, stream)) && ok(hipMemsetAsync(S.diff, 0, gn * L.diff_stride, stream));
+    mark(3);
+    if (err == hipSuccess) {
+      // about one workgroup per CU over the wave (each holds 128 KiB of LDS), at most one per sample
+      u32 const bx = (u32)std::min<size_t>(samples, std::max<size_t>(1, ((size_t)cus + gn - 1) / gn));
+      hipLaunchKernelGGL(zh_cover_freq_kernel, dim3(bx, gn), dim3(FREQ_T), FREQ_LDS, stream, wg, S, dm, d_ends);
+      ok(hipGetLastError());
+    }
+    mark(4);
+    // The control words come back once per pass over the epochs (at most 64 steps, so a corpus of
+    // many epochs does not queue thousands of no-op steps behind dictionaries that are already
+    // full).  Every step of a group that is not a no-op shrinks its tail or grows its zero_run,
+    // so the loop ends.
+    size_t const pass = std::min<size_t>(epochs, 64);
+    u32 const cgrid = (u32)((esz + CT - 1) / CT), nt = (u32)ntiles;
+    bool done = false;
+    while (err == hipSuccess && !done) {
+      for (size_t s = 0; s < pass; s++) {
+        hipLaunchKernelGGL(zh_cover_contrib_kernel, dim3(cgrid, gn), dim3(CT), 0, stream, wg, S, dm, prev);
+        hipLaunchKernelGGL(zh_cover_tilesum_kernel, dim3(nt, gn), dim3(CT), 0, stream, wg, S);
+        hipLaunchKernelGGL(zh_cover_tilescan_kernel, dim3(1, gn), dim3(CT), 0, stream, wg, S);
+        hipLaunchKernelGGL(zh_cover_argmax_kernel, dim3(nt, gn), dim3(CT), 0, stream, wg, S);
+        hipLaunchKernelGGL(zh_cover_commit_kernel, dim3(1, gn), dim3(CT), 0, stream, wg, S, dm, d_corpus);
+      }
+      ok(hipGetLastError()) && ok(hipMemcpyAsync(h_ctl.data(), S.ctl, gn * sizeof(CoverCtl), hipMemcpyDeviceToHost, stream)) &&
+          ok(hipStreamSynchronize(stream));
+      done = true;
+      for (u32 j = 0; j < gn; j++) done = done && h_ctl[j].done;
+    }
+    mark(5);
+    ok(hipMemcpyAsync(h_dict.data(), S.dict, gn * L.dict_stride, hipMemcpyDeviceToHost, stream)) && ok(hipStreamSynchronize(stream));
+    if (err != hipSuccess) break;
+    for (u32 j = 0; j < gn; j++) {
+      if (groups[g0 + j].plan.empty || h_ctl[j].tail > dict_size) continue;
+      const u8 *const d = h_dict.data() + j * L.dict_stride;
+      out[g0 + j].assign(d + h_ctl[j].tail, d + dict_size);
+    }
+    if (first_wave) add(0, 0), add(1, 1);
+    first_wave = false;
+    add(0, 3), add(2, 4);
   }
   // the host sources of the copies above stay alive until the stream has drained, errors included
-  ok(hipStreamSynchronize(stream));
-  if (phase_ms) {
-    for (int k = 0; k < 3; k++) {
-      phase_ms[k] = 0.f;
-      if (err == hipSuccess) ok(hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]));
-    }
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  if (err != hipSuccess) out.clear();
+  (void)hipStreamSynchronize(stream);
+  for (auto &e : ev)
+    if (e) (void)hipEventDestroy(e);
+  if (err != hipSuccess) out.assign(ng, std::vector<uint8_t>());
   return err;
 }
 
 }  // namespace zh
+

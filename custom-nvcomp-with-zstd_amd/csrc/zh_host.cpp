@@ -1690,14 +1690,23 @@ namespace {
 bool g_train_profile = false;  // cuda_zstd_hip_dict_train_profile: HIP events around the device trainer's kernel groups
 float g_train_phase_ms[3] = {0.f, 0.f, 0.f};
 
-// The device trainer (zh_dict_train.hip) over samples back to back at d_corpus; sizes is a host
-// array.  temp == nullptr: the function's own hipMalloc.  content = zh::cover_train's bytes.
-Status train_device(const u8 *d_corpus, const size_t *sizes, size_t n, size_t dict_size, u32 k, u32 d, void *temp, size_t temp_bytes,
-                    bool own_temp, hipStream_t stream, std::vector<u8> &content) {
-  content.clear();
-  if (!d_corpus || !sizes || n == 0 || n >= (1ull << 32)) return Status::ERROR_INVALID_PARAMETER;
+// The device trainer (zh_dict_train.hip) over samples back to back at d_corpus, one dictionary per
+// group of counts[g] consecutive samples; sizes and counts are host arrays.  temp == nullptr: the
+// function's own hipMalloc.  contents[g] = zh::cover_train's bytes for group g's samples alone
+// (none where the group has fewer than k bytes: the host trainer's empty result).
+Status train_groups_device(const u8 *d_corpus, const size_t *sizes, size_t n, const size_t *counts, size_t ng, size_t dict_size, u32 k, u32 d,
+                           void *temp, size_t temp_bytes, bool own_temp, hipStream_t stream, std::vector<std::vector<u8>> &contents) {
+  contents.clear();
+  if (!d_corpus || !sizes || !counts || n == 0 || n >= (1ull << 32) || ng == 0 || ng > zh::kCoverMaxGroups) return Status::ERROR_INVALID_PARAMETER;
+  contents.resize(ng);
   k = k ? k : zh::kCoverDefaultK;
   d = d ? d : zh::kCoverDefaultD;
+  size_t counted = 0;
+  for (size_t g = 0; g < ng; g++) {
+    if (counts[g] > n - counted) return Status::ERROR_INVALID_PARAMETER;
+    counted += counts[g];
+  }
+  if (counted != n) return Status::ERROR_INVALID_PARAMETER;
   std::vector<u32> ends(n);
   u64 total = 0;
   for (size_t i = 0; i < n; i++) {
@@ -1706,21 +1715,34 @@ Status train_device(const u8 *d_corpus, const size_t *sizes, size_t n, size_t di
     ends[i] = (u32)total;
   }
   if (total == 0) return Status::ERROR_INVALID_PARAMETER;
-  zh::CoverPlan const plan = zh::cover_plan((size_t)total, dict_size, k, d);
-  if (plan.k > zh::kCoverMaxK) return Status::ERROR_INVALID_PARAMETER;  // prevdist is a u16
-  size_t const need = zh::cover_temp_bytes((size_t)total, n, dict_size, k);
+  std::vector<zh::CoverGroup> groups(ng);
+  (void)zh::cover_groups(sizes, counts, ng, dict_size, k, d, groups.data());
+  if (groups[0].plan.k > zh::kCoverMaxK) return Status::ERROR_INVALID_PARAMETER;  // prevdist is a u16
+  size_t const need = zh::cover_temp_bytes(sizes, n, counts, ng, dict_size, k);
   if (!own_temp && (!temp || temp_bytes < need)) return Status::ERROR_BUFFER_TOO_SMALL;
-  if (plan.empty) return Status::SUCCESS;  // fewer than k bytes: the host trainer's empty result
+  bool any = false;
+  for (auto const &g : groups) any = any || !g.plan.empty;
+  if (!any) return Status::SUCCESS;
   void *mine = nullptr;
   if (own_temp) {
     if (hipMalloc(&mine, need) != hipSuccess) { (void)hipGetLastError(); return Status::ERROR_OUT_OF_MEMORY; }
     temp = mine;
   }
-  hipError_t const e = zh::cover_train_device(d_corpus, ends.data(), n, plan, dict_size, temp, stream, content,
-                                              g_train_profile ? g_train_phase_ms : nullptr);
+  hipError_t const e = zh::cover_train_groups_device(d_corpus, ends.data(), n, groups.data(), ng, dict_size, temp, stream, contents,
+                                                     g_train_profile ? g_train_phase_ms : nullptr);
   if (mine) (void)hipFree(mine);
   if (e != hipSuccess) { (void)hipGetLastError(); return Status::ERROR_CUDA_ERROR; }
   return Status::SUCCESS;
+}
+
+// one dictionary from all samples: the call with one group
+Status train_device(const u8 *d_corpus, const size_t *sizes, size_t n, size_t dict_size, u32 k, u32 d, void *temp, size_t temp_bytes,
+                    bool own_temp, hipStream_t stream, std::vector<u8> &content) {
+  content.clear();
+  std::vector<std::vector<u8>> c;
+  Status const st = train_groups_device(d_corpus, sizes, n, &n, 1, dict_size, k, d, temp, temp_bytes, own_temp, stream, c);
+  if (st == Status::SUCCESS) content = std::move(c[0]);
+  return st;
 }
 
 // trained content -> the dict_size bytes of dict_buffer (host or device memory)
@@ -2708,6 +2730,45 @@ int cuda_zstd_train_dictionary_device(const void *d_samples, const size_t *sizes
     *dict_out = h;
     return 0;
   } catch (...) {
+    return c_err(Status::ERROR_OUT_OF_MEMORY);
+  }
+}
+size_t cuda_zstd_train_dictionaries_device_get_temp_size(const size_t *sizes, size_t num, const size_t *counts, size_t num_groups, size_t dict_size,
+                                                         unsigned k) {
+  if (!sizes || !counts || num_groups == 0 || num_groups > zh::kCoverMaxGroups) return 0;
+  size_t counted = 0;
+  for (size_t g = 0; g < num_groups; g++) {
+    if (counts[g] > num - counted) return 0;
+    counted += counts[g];
+  }
+  return counted == num ? zh::cover_temp_bytes(sizes, num, counts, num_groups, dict_size, k) : 0;
+}
+int cuda_zstd_train_dictionaries_device(const void *d_samples, const size_t *sizes, size_t num, const size_t *counts, size_t num_groups,
+                                        size_t dict_size, unsigned k, unsigned d, void *d_temp, size_t temp_bytes, hipStream_t stream,
+                                        cuda_zstd_dict_t **dicts_out, int *group_status) {
+  if (!dicts_out || num_groups == 0 || num_groups > zh::kCoverMaxGroups) return c_err(Status::ERROR_INVALID_PARAMETER);
+  for (size_t g = 0; g < num_groups; g++) dicts_out[g] = nullptr;
+  if (group_status)
+    for (size_t g = 0; g < num_groups; g++) group_status[g] = status_to_nvcomp_error(Status::ERROR_COMPRESSION);
+  if (!d_samples || !sizes || !counts || num == 0 || !dictionary::is_valid_dictionary_size(dict_size)) return c_err(Status::ERROR_INVALID_PARAMETER);
+  try {
+    std::vector<std::vector<u8>> c;
+    Status const st =
+        dictionary::train_groups_device((const u8 *)d_samples, sizes, num, counts, num_groups, dict_size, k, d, d_temp, temp_bytes, false, stream, c);
+    if (st != Status::SUCCESS) return c_err(st);
+    for (size_t g = 0; g < num_groups; g++) {
+      if (c[g].size() < dictionary::MIN_DICT_SIZE) continue;  // (where the host entry returns NULL): the group's status stays 12
+      auto *h = new cuda_zstd_dict_t;
+      h->set(std::move(c[g]), 0);
+      dicts_out[g] = h;
+      if (group_status) group_status[g] = 0;
+    }
+    return 0;
+  } catch (...) {
+    for (size_t g = 0; g < num_groups; g++) {
+      delete dicts_out[g];
+      dicts_out[g] = nullptr;
+    }
     return c_err(Status::ERROR_OUT_OF_MEMORY);
   }
 }

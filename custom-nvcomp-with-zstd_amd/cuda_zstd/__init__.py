@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CUDA_ZSTD_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libcuda_zstd_hip.so")
@@ -68,6 +68,8 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_train_dictionary_params": (vp, [pvp, psz, sz, sz, ctypes.c_uint, ctypes.c_uint]),
             "cuda_zstd_train_dictionary_device_get_temp_size": (sz, [sz, sz, sz, ctypes.c_uint]),
             "cuda_zstd_train_dictionary_device": (i, [vp, psz, sz, sz, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, pvp]),
+            "cuda_zstd_train_dictionaries_device_get_temp_size": (sz, [psz, sz, psz, sz, sz, ctypes.c_uint]),
+            "cuda_zstd_train_dictionaries_device": (i, [vp, psz, sz, psz, sz, sz, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, pvp, pi]),
             "cuda_zstd_hip_dict_train_profile": (None, [i, ctypes.POINTER(ctypes.c_double)]),
             "cuda_zstd_load_dictionary": (vp, [vp, sz]),
             "cuda_zstd_finalize_dictionary": (i, [vp, pvp, psz, sz, i, ctypes.c_uint, vp, pvp]),
@@ -552,6 +554,54 @@ class Dictionary:
             raise ZstdError(rc, "cuda_zstd_train_dictionary_device")
         return cls(h.value, "cuda_zstd_train_dictionary_device")
 
+    @classmethod
+    def train_groups(cls, groups, dict_size: int, k: int = 0, d: int = 0, stream=None) -> List[Optional["Dictionary"]]:
+        """One COVER dictionary (raw content) per group of samples, all trained on the device in one
+        call (cuda_zstd_train_dictionaries_device): up to 4,096 groups, 64 of them in flight at a
+        time.  Each group is a list or tuple of torch CUDA tensors, or one 2-D uint8 CUDA tensor
+        with a sample per row (the forms train takes on the device); a group may be empty.  The
+        concatenation and the temp buffer are ordered on `stream`.  Entry g equals
+        Dictionary.train on group g's samples alone; it is None where the group gave fewer than
+        256 bytes (status 12).  dict_size, k and d are common to the call, and all samples
+        together stay under 2^32 - 64 bytes: train more data in a second call.
+        Not done here: finalizing the contents (Dictionary.finalize per dictionary), host samples,
+        per-group dict_size / k / d, and keeping the trained bytes on the device."""
+        torch = _torch()
+        s = stream if stream is not None else torch.cuda.current_stream()
+        groups = list(groups)
+        ng = len(groups)
+        with torch.cuda.stream(s):  # the concatenation and the temp buffer are ordered on the same stream
+            views, sizes, counts = [], [], []
+            for grp in groups:
+                if _is_cuda_tensor(grp):
+                    if grp.dim() != 2 or grp.dtype != torch.uint8:
+                        raise TypeError("Dictionary.train_groups: a group given as one tensor must be 2-D uint8, one sample per row")
+                    views.append(grp.contiguous().view(-1))
+                    sizes += [grp.shape[1]] * grp.shape[0]
+                    counts.append(grp.shape[0])
+                elif isinstance(grp, (list, tuple)) and all(_is_cuda_tensor(t) for t in grp):
+                    rows = [t.contiguous().view(torch.uint8).view(-1) for t in grp]
+                    views += rows
+                    sizes += [v.numel() for v in rows]
+                    counts.append(len(rows))
+                else:
+                    raise TypeError("Dictionary.train_groups: a group is a list or tuple of CUDA tensors, or one 2-D uint8 CUDA tensor")
+            n = len(sizes)
+            if n == 0:
+                raise ZstdError(INVALID, "Dictionary.train_groups: no samples")
+            flat = torch.cat(views) if len(views) > 1 else views[0]
+            csz = (ctypes.c_size_t * n)(*sizes)
+            ccn = (ctypes.c_size_t * max(ng, 1))(*counts)
+            need = lib().cuda_zstd_train_dictionaries_device_get_temp_size(csz, n, ccn, ng, dict_size, k)
+            temp = torch.empty(max(need, 256), dtype=torch.uint8, device=flat.device)
+            hs = (ctypes.c_void_p * max(ng, 1))()
+            st = (ctypes.c_int * max(ng, 1))()
+            rc = lib().cuda_zstd_train_dictionaries_device(flat.data_ptr(), csz, n, ccn, ng, dict_size, k, d, temp.data_ptr(), temp.numel(),
+                                                           s.cuda_stream, hs, st)
+        if rc:
+            raise ZstdError(rc, "cuda_zstd_train_dictionaries_device")
+        return [cls(hs[g], "cuda_zstd_train_dictionaries_device") if hs[g] else None for g in range(ng)]
+
     def finalize(self, samples, level: int = 3, dict_id: int = 0, stream=None) -> "Dictionary":
         """This dictionary's content plus entropy tables -> a formatted RFC 8878 dictionary
         (libzstd's ZDICT_finalizeDictionary; cuda_zstd_finalize_dictionary).  The tables come from
@@ -637,6 +687,20 @@ class DictionarySet:
         if rc:
             raise ZstdError(rc, "cuda_zstd_dict_set_create")
         self._h = h.value
+
+    @classmethod
+    def train(cls, groups, dict_size: int, k: int = 0, d: int = 0, stream=None) -> "DictionarySet":
+        """Dictionary.train_groups(groups, ...) straight into a set: entry g is the raw-content
+        dictionary trained on group g's device samples.  Raises ZstdError(12) naming the first
+        group that gave fewer than 256 bytes.  The same limits hold (common dict_size / k / d,
+        under 2^32 - 64 sample bytes per call, device samples only), and the contents are not
+        finalized: for formatted entries, finalize the dictionaries of train_groups one by one
+        and build the set from them."""
+        ds = Dictionary.train_groups(groups, dict_size, k, d, stream)
+        for g, one in enumerate(ds):
+            if one is None:
+                raise ZstdError(12, f"DictionarySet.train: group {g} gave no dictionary")
+        return cls(ds, stream)
 
     def __len__(self) -> int:
         return lib().cuda_zstd_dict_set_count(self._h)

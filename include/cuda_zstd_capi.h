@@ -55,6 +55,28 @@ size_t cuda_zstd_train_dictionary_device_get_temp_size(size_t total_sample_bytes
 int cuda_zstd_train_dictionary_device(const void *d_samples, const size_t *sample_sizes, size_t num_samples, size_t dict_size,
                                       unsigned k, unsigned d, void *d_temp, size_t temp_bytes, hipStream_t stream,
                                       cuda_zstd_dict_t **dict_out);
+/* device trainer, one dictionary per group of samples in one call: d_samples = all samples back to
+ * back in device memory, sample_sizes a HOST array (zero sizes allowed), group_counts a HOST array
+ * of num_groups counts of consecutive samples (0 allowed) that sum to num_samples; 1 <= num_groups
+ * <= 4096, what a dictionary set holds.  dict_size, k and d are common to the call, with the
+ * single entry's limits: 256 B .. 128 KiB, k <= 65535 and fewer than 2^32 - 64 sample bytes PER
+ * CALL (positions are 32-bit): a caller with more data calls twice.  Stream-ordered on `stream`
+ * for its reads of d_samples; blocking on return (the handles hold host bytes).
+ * dicts_out[g] = a raw-content handle whose bytes equal the host trainer's for group g's samples
+ * alone, or NULL; group_status (optional) gets 0, or 12 where the group gave fewer than 256 bytes
+ * (no samples, no bytes, fewer than k bytes).  A failed group does not affect its neighbours.
+ * Returns 0 when the arguments were valid, whatever the groups report; 2 for a NULL required
+ * pointer, no samples or no sample bytes at all, counts that do not sum to num_samples, num_groups
+ * outside 1 .. 4096, or the limits above; 7 when temp_bytes is below what _get_temp_size reports
+ * for the same arrays (nothing is launched); 4 on a HIP error.  Whenever it does not return 0,
+ * every dicts_out[g] is NULL.  At most 64 groups are in flight (each with a 4 MiB frequency table
+ * in d_temp, so the temp size stops growing with num_groups there); more groups run as successive
+ * waves inside the call.  _get_temp_size returns 0 for arguments the call answers with 2. */
+size_t cuda_zstd_train_dictionaries_device_get_temp_size(const size_t *sample_sizes, size_t num_samples, const size_t *group_counts,
+                                                         size_t num_groups, size_t dict_size, unsigned k);
+int cuda_zstd_train_dictionaries_device(const void *d_samples, const size_t *sample_sizes, size_t num_samples, const size_t *group_counts,
+                                        size_t num_groups, size_t dict_size, unsigned k, unsigned d, void *d_temp, size_t temp_bytes,
+                                        hipStream_t stream, cuda_zstd_dict_t **dicts_out, int *group_status);
 /* dictionary::finalize_dictionary: the content of `content` (raw, or a formatted dictionary's) plus
  * entropy tables gathered by compressing the samples (an array of num_samples host or device
  * pointers) against it at `level` on the device -> a new formatted dictionary handle in *dict_out
