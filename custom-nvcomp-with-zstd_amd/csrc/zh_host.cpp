@@ -3453,6 +3453,52 @@ int cuda_zstd_seekable_read(nvcomp_zstd_batch_manager_t *mgr, const void *d_stre
   return 0;
 }
 
+// Temp of a batched read whose ranges touch at most max_jobs frames with content
+size_t cuda_zstd_seekable_read_ranges_get_temp_size(size_t num_frames, size_t num_ranges, size_t max_jobs, size_t max_frame_uncompressed) {
+  size_t const jobs = std::min(max_jobs, num_frames);
+  size_t const dec = ZstdBatchManager::get_batch_device_decompress_temp_size(jobs, std::max<size_t>(max_frame_uncompressed, 1));
+  return zh::seek_ranges_layout(num_frames, num_ranges, jobs, max_frame_uncompressed, dec).total;
+}
+
+int cuda_zstd_seekable_read_ranges(nvcomp_zstd_batch_manager_t *mgr, const void *d_stream, size_t size, const unsigned long long *d_offsets,
+                                   const size_t *d_lengths, void *const *d_out_ptrs, size_t num_ranges, size_t max_length, int verify_checksums,
+                                   int *d_range_statuses, size_t *frames_decoded, void *d_temp, size_t temp_bytes, hipStream_t stream) {
+  if (frames_decoded) *frames_decoded = 0;
+  if (!mgr || !mgr->mgr || !d_stream) return c_err(Status::ERROR_INVALID_PARAMETER);
+  if (num_ranges == 0) return 0;
+  if (!d_offsets || !d_lengths || !d_out_ptrs || !d_range_statuses) return c_err(Status::ERROR_INVALID_PARAMETER);
+  ZhSeekFooter f;
+  int rc = seek_fetch_footer(d_stream, size, true, f, stream);
+  if (rc) return rc;
+  size_t const n = (size_t)f.n;
+  // the part in front of the staging slots depends on the table and the ranges alone
+  if (!d_temp || temp_bytes < zh::seek_ranges_layout(n, num_ranges, 0, 0, 0).staging + 256) return 7;  // nothing launched
+  u8 *const base = aligned_base(d_temp);
+  if (zh::seek_ranges_index_launch(d_stream, size, n, f.entry, d_offsets, d_lengths, num_ranges, max_length, base, stream) != hipSuccess) return 4;
+  zh::SeekReadCtl ctl;
+  if (hipMemcpyAsync(&ctl, base, sizeof(ctl), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return 4;
+  if (ctl.status) return (int)ctl.status;
+  // the staging slots and the decoder's workspace, sized now that the job count is known: the
+  // buffer must be what get_temp_size asks for this many jobs
+  size_t const max_out = std::max<size_t>(ctl.max_d, 1);
+  size_t const dec = ctl.njobs ? ZstdBatchManager::get_batch_device_decompress_temp_size(ctl.njobs, max_out) : 0;
+  ZhSeekRangesLayout const L = zh::seek_ranges_layout(n, num_ranges, ctl.njobs, ctl.max_d, dec);
+  if (ctl.njobs > n || (ctl.njobs && temp_bytes < L.total)) return 7;  // the decoder is not launched
+  if (ctl.njobs) {
+    zh::SeekJobs const j = zh::seek_read_jobs(base, n);
+    Status const s = mgr->mgr->batch_manager().decompress_batch_device(j.in_ptrs, j.in_sizes, j.out_caps, max_out, ctl.njobs, j.out_ptrs, j.out_sizes,
+                                                                       j.statuses, base + L.dec, dec, stream);
+    if (s != Status::SUCCESS) return c_err(s);
+  }
+  // (no range longer than the content is copied: the scatter grid is sized by the smaller bound)
+  if (zh::seek_ranges_finish_launch(d_stream, size, n, f.entry, ctl.njobs, d_offsets, d_lengths, d_out_ptrs, num_ranges,
+                                    (size_t)std::min<u64>(max_length, ctl.total_u), verify_checksums, d_range_statuses, base, stream) != hipSuccess)
+    return 4;
+  if (hipStreamSynchronize(stream) != hipSuccess) return 4;
+  if (frames_decoded) *frames_decoded = ctl.njobs;
+  return 0;
+}
+
 // ---- adaptive level selection (zh_adaptive.hip; the rule in zh_adaptive.h) ---------------------
 size_t cuda_zstd_adaptive_get_temp_size(size_t num_chunks) { return num_chunks * ZH_AD_REC_WORDS * sizeof(u32); }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "zh_common.h"
 #include "zh_seek_format.h"
+#include "zh_seek_ranges.h"
 
 namespace zh {
 
@@ -53,6 +54,23 @@ hipError_t seek_index_launch(const void *d_stream, size_t size, size_t nframes, 
 // bounced edge frames' overlap into d_out.
 hipError_t seek_trim_launch(const void *d_stream, size_t size, size_t nframes, u32 entry, u32 njobs, u64 offset, u64 length, void *d_out,
                             int verify, u8 *base, hipStream_t stream);
+
+// ---- read of many ranges ---------------------------------------------------------------------
+// Temp buffer of a batched read (zh_seek_ranges.h): the fixed part of a read, the arrays sized by
+// N and by the number of ranges, `jobs` staging slots of align256(max_d) bytes, dec_bytes of
+// decoder workspace.  Everything in front of the staging slots depends on N and the ranges only.
+ZhSeekRangesLayout seek_ranges_layout(size_t nframes, size_t num_ranges, size_t jobs, size_t max_d, size_t dec_bytes);
+// Parse + validate + scan the table as a read does, then give every range its verdict and its
+// first and last entry, mark the entries the ranges touch and emit one decode job (into a
+// staging slot) per marked entry with content.  The control block holds the table's status and
+// the job count.  No range status and no destination is written.
+hipError_t seek_ranges_index_launch(const void *d_stream, size_t size, size_t nframes, u32 entry, const unsigned long long *d_offsets,
+                                    const size_t *d_lengths, size_t num_ranges, size_t max_length, u8 *base, hipStream_t stream);
+// After the decoder: check every job, write every range's status, and copy the bytes of the
+// ranges that touch only good frames to their destinations.
+hipError_t seek_ranges_finish_launch(const void *d_stream, size_t size, size_t nframes, u32 entry, u32 njobs,
+                                     const unsigned long long *d_offsets, const size_t *d_lengths, void *const *d_out_ptrs, size_t num_ranges,
+                                     size_t max_length, int verify, int *d_range_statuses, u8 *base, hipStream_t stream);
 
 // ---- info ------------------------------------------------------------------------------------
 struct SeekInfoRes {

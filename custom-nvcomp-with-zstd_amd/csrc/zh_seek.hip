@@ -11,9 +11,16 @@
 //   zh_seek_pack_entries*_kernel: the table's entries (with checksums: one wave per frame)
 // Read: the table is parsed, validated and scanned on the device, and turned into the job
 // arrays of the batched decoder; a last kernel checks the decodes and trims the edge frames.
+// Read of many ranges (arithmetic: zh_seek_ranges.h): the same table scan, then
+//   zh_seek_ranges_mark_kernel   : one wave per range: verdict, first and last entry, entry bitmap
+//   zh_seek_ranges_jobs_kernel   : one decode job into a staging slot per marked entry with content
+//   zh_seek_ranges_check_kernel  : one wave per job: the trim kernel's check of the decode
+//   zh_seek_ranges_status_kernel : one wave per range: the lowest failing frame's code
+//   zh_seek_ranges_scatter_kernel: one workgroup per (range, 16 KiB piece): staging -> destination
 #include "zh_common.h"
 #include "zh_scan.h"
 #include "zh_seek.h"
+#include "zh_seek_ranges.h"
 #include "zh_xxh64.h"
 
 #include <algorithm>
@@ -25,6 +32,7 @@ constexpr u32 SK_PER_THREAD = 4;
 constexpr u32 SK_TILE = SK_THREADS * SK_PER_THREAD;  // items per scan tile
 constexpr u32 SK_PIECE = 16384;                      // bytes per copy workgroup: 256 lanes x 16 B x 4
 constexpr u64 SK_NONE = ~0ull;
+static_assert(SK_TILE == ZH_SEEK_TILE && SK_PIECE == ZH_SEEK_PIECE, "zh_seek_ranges.h states the tile and the piece");
 
 __host__ __device__ inline size_t sk_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline size_t sk_tiles(size_t n) { return (n + SK_TILE - 1) / SK_TILE; }
@@ -39,6 +47,12 @@ struct JobMeta {
   u32 flags;  // bit 0: bounced; bit 1: the bounce slot
   u64 dstart;
 };
+
+struct RangeJobMeta {  // a batched read's job, in the same array
+  u32 frame;
+  u32 code;  // the check kernel's verdict
+};
+static_assert(sizeof(RangeJobMeta) <= sizeof(JobMeta), "the meta array is sized for JobMeta");
 
 __device__ __forceinline__ u64 block_min64(u64 v, u64 *lds) {
   u32 const tid = threadIdx.x;
@@ -83,6 +97,29 @@ __device__ __forceinline__ void copy_bytes(u8 *dst, const u8 *src, u32 n, u32 ti
   if (tid < h) dst[tid] = src[tid];
   u32 const t0 = h + 16u * nv;  // tail: fewer than 16 bytes
   if (tid < n - t0) dst[t0 + tid] = src[t0 + tid];
+}
+
+// A decoded job against the table, by one wave: the decoder's status, the produced size and,
+// when asked and the table has them, the checksum over the whole frame at `got`.  e: the
+// frame's table entry.  Returns the job's code (0: good), the same in every lane.
+__device__ __forceinline__ u32 check_job(const u8 *e, u32 entry, const u8 *got, int status, u64 produced, int verify, u64 *xb) {
+  u64 const d = zh_seek_ld32(e + 4);
+  u32 code = (u32)status;
+  if (code == 0 && produced != d) code = ZH_SEEK_CORRUPT;
+  if (code == 0 && verify && entry == 12) {
+    u64 const h = zh_xxh64_wave(got, d, xb);
+    if ((u32)h != zh_seek_ld32(e + 8)) code = ZH_SEEK_CHECKSUM;
+  }
+  return code;
+}
+
+__device__ __forceinline__ u64 wave_min64(u64 v) {
+#pragma unroll
+  for (u32 o = 32; o; o >>= 1) {
+    u64 const t = __shfl_xor((unsigned long long)v, o, 64);
+    v = t < v ? t : v;
+  }
+  return v;
 }
 
 }  // namespace
@@ -318,12 +355,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_seek_trim_kernel(const u8 *_
   const u8 *const e = stream + (size - table_bytes) + 8 + (u64)m.frame * entry;
   u64 const d = zh_seek_ld32(e + 4);
   const u8 *const got = (const u8 *)jobs.out_ptrs[j];
-  u32 code = (u32)jobs.statuses[j];
-  if (code == 0 && jobs.out_sizes[j] != d) code = ZH_SEEK_CORRUPT;
-  if (code == 0 && verify && entry == 12) {  // an edge frame: over the bounce slot's full frame
-    u64 const h = zh_xxh64_wave(got, d, xb);
-    if ((u32)h != zh_seek_ld32(e + 8)) code = ZH_SEEK_CHECKSUM;
-  }
+  u32 const code = check_job(e, entry, got, jobs.statuses[j], jobs.out_sizes[j], verify, xb);  // an edge frame: over the bounce slot's full frame
   if (code) {
     if (lane == 0) atomicMin((unsigned long long *)&ctl->errkey, (unsigned long long)((u64)m.frame << 8 | (code & 0xFFu)));
     return;
@@ -331,6 +363,128 @@ extern "C" __global__ __launch_bounds__(64) void zh_seek_trim_kernel(const u8 *_
   if (m.flags & 1u) {
     u64 const lo = max(m.dstart, offset), hi = min(m.dstart + d, offset + length);
     copy_bytes<64>(d_out + (lo - offset), got + (lo - m.dstart), (u32)(hi - lo), lane);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Read of many ranges: the table is scanned once (the two index kernels above), every frame a
+// range touches is decoded once into a staging slot, and each range's bytes are copied from the
+// slots to its destination.
+// ---------------------------------------------------------------------------------------------
+// One wave per range: its verdict (kept in first[]), its first and last entry, and the bits of
+// the entries between them.
+extern "C" __global__ __launch_bounds__(256) void zh_seek_ranges_mark_kernel(const u64 *__restrict__ offsets, const size_t *__restrict__ lengths,
+                                                                             u64 nranges, u64 max_length, u32 n, const u64 *__restrict__ ld,
+                                                                             const u64 *__restrict__ tbd, const zh::SeekReadCtl *__restrict__ ctl,
+                                                                             u32 *__restrict__ first, u32 *__restrict__ last, u32 *bitmap) {
+  if (ctl->status != ZH_SEEK_OK) return;  // no table to trust
+  u32 const wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  ZhSeekIndex const x{ld, tbd, n, ctl->total_u};
+  u64 const nwaves = (u64)gridDim.x * (SK_THREADS / 64);
+  for (u64 r = (u64)blockIdx.x * (SK_THREADS / 64) + wave; r < nranges; r += nwaves) {
+    u64 const off = offsets[r], len = lengths[r];
+    if (!zh_seek_range_ok(off, len, x.total, max_length) || len == 0) {
+      if (lane == 0) first[r] = len == 0 && off <= x.total ? ZH_SEEK_RANGE_EMPTY : ZH_SEEK_RANGE_INVALID;
+      continue;
+    }
+    u32 const a = (u32)zh_seek_cover(x, off), b = (u32)zh_seek_cover(x, off + len - 1);
+    if (lane == 0) {
+      first[r] = a;
+      last[r] = b;
+    }
+    for (u32 w = (a >> 5) + lane; w <= (b >> 5); w += 64) {
+      u32 m = ~0u;
+      if (w == (a >> 5)) m &= ~0u << (a & 31u);
+      if (w == (b >> 5)) m &= ~0u >> (31u - (b & 31u));
+      atomicOr(&bitmap[w], m);
+    }
+  }
+}
+
+// One lane per entry: a marked entry with content becomes one decode job into its staging slot.
+// The job arrays hold n items and at most n jobs exist; the slot's address is only computed
+// here: the host launches the decoder after it has seen that the temp buffer holds njobs slots.
+extern "C" __global__ __launch_bounds__(256) void zh_seek_ranges_jobs_kernel(const u8 *__restrict__ stream, u64 size, u32 n, u32 entry,
+                                                                             u64 table_bytes, const u64 *__restrict__ lc,
+                                                                             const u64 *__restrict__ tbc, const u32 *__restrict__ bitmap,
+                                                                             u8 *staging, zh::SeekReadCtl *ctl, zh::SeekJobs jobs,
+                                                                             u32 *__restrict__ job_of_frame) {
+  if (ctl->status != ZH_SEEK_OK) return;
+  u64 const i = (u64)blockIdx.x * SK_THREADS + threadIdx.x;
+  if (i >= n || !(bitmap[i >> 5] >> (i & 31u) & 1u)) return;
+  const u8 *const e = stream + (size - table_bytes) + 8 + i * entry;
+  u64 const c = zh_seek_ld32(e), d = zh_seek_ld32(e + 4);
+  if (d == 0) return;  // an empty frame, or a skippable frame listed as an entry
+  u32 const j = atomicAdd(&ctl->njobs, 1u);
+  jobs.in_ptrs[j] = stream + tbc[i / SK_TILE] + lc[i];
+  jobs.in_sizes[j] = (size_t)c;
+  jobs.out_ptrs[j] = staging + (size_t)j * sk_align256(ctl->max_d);
+  jobs.out_caps[j] = (size_t)d;
+  RangeJobMeta m;
+  m.frame = (u32)i;
+  m.code = 0;
+  ((RangeJobMeta *)jobs.meta)[j] = m;
+  job_of_frame[i] = j;
+}
+
+// One wave per job: the decode against the table (the trim kernel's check).
+extern "C" __global__ __launch_bounds__(64) void zh_seek_ranges_check_kernel(const u8 *__restrict__ stream, u64 size, u32 entry, u64 table_bytes,
+                                                                             int verify, zh::SeekJobs jobs) {
+  __shared__ u64 xb[512];
+  u32 const j = blockIdx.x;
+  RangeJobMeta *const m = (RangeJobMeta *)jobs.meta + j;
+  const u8 *const e = stream + (size - table_bytes) + 8 + (u64)m->frame * entry;
+  u32 const code = check_job(e, entry, (const u8 *)jobs.out_ptrs[j], jobs.statuses[j], jobs.out_sizes[j], verify, xb);
+  if (threadIdx.x == 0 && code) m->code = (code & 0xFFu) ? (code & 0xFFu) : 1u;
+}
+
+// One wave per range: the code of the lowest failing frame it touches, or its own verdict.
+extern "C" __global__ __launch_bounds__(256) void zh_seek_ranges_status_kernel(u64 nranges, const u32 *__restrict__ first,
+                                                                               const u32 *__restrict__ last, const u32 *__restrict__ job_of_frame,
+                                                                               zh::SeekJobs jobs, int *__restrict__ statuses) {
+  u32 const wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const RangeJobMeta *const meta = (const RangeJobMeta *)jobs.meta;
+  u64 const nwaves = (u64)gridDim.x * (SK_THREADS / 64);
+  for (u64 r = (u64)blockIdx.x * (SK_THREADS / 64) + wave; r < nranges; r += nwaves) {
+    u32 const a = first[r];
+    u32 code = a == ZH_SEEK_RANGE_INVALID ? (u32)ZH_SEEK_INVALID : (u32)ZH_SEEK_OK;
+    if (a < ZH_SEEK_RANGE_EMPTY) {
+      u64 key = SK_NONE;
+      u64 const b = last[r];
+      for (u64 i = (u64)a + lane; i <= b; i += 64) {
+        u32 const j = job_of_frame[i];
+        if (j == ZH_SEEK_NO_JOB) continue;  // an entry of size 0
+        u32 const c = meta[j].code;
+        if (c) key = min(key, i << 8 | c);
+      }
+      key = wave_min64(key);
+      if (key != SK_NONE) code = (u32)(key & 0xFFu);
+    }
+    if (lane == 0) statuses[r] = (int)code;
+  }
+}
+
+// One workgroup per (range, 16 KiB piece of its content): the piece's segments, one per frame
+// with content, from the frames' staging slots to the range's destination.
+extern "C" __global__ __launch_bounds__(256) void zh_seek_ranges_scatter_kernel(const u64 *__restrict__ offsets, const size_t *__restrict__ lengths,
+                                                                                void *const *__restrict__ out_ptrs, const int *__restrict__ statuses,
+                                                                                u64 nranges, u32 ppr, u32 n, const u64 *__restrict__ ld,
+                                                                                const u64 *__restrict__ tbd, const zh::SeekReadCtl *__restrict__ ctl,
+                                                                                const u32 *__restrict__ job_of_frame, const u8 *__restrict__ staging) {
+  ZhSeekIndex const x{ld, tbd, n, ctl->total_u};
+  size_t const slot = sk_align256(ctl->max_d);
+  u64 const nwork = nranges * ppr;
+  for (u64 w = blockIdx.x; w < nwork; w += gridDim.x) {
+    u64 const r = w / ppr, po = (w % ppr) * SK_PIECE;
+    if (statuses[r] != 0) continue;  // a failed range: nothing of its destination is written
+    u64 const len = lengths[r];
+    if (po >= len) continue;
+    u64 const p0 = offsets[r] + po, end = p0 + min((u64)SK_PIECE, len - po);
+    u8 *const dst = (u8 *)out_ptrs[r] + po;
+    u64 i = zh_seek_cover(x, p0), pos = p0;
+    ZhSeekSeg s;
+    while (zh_seek_next_seg(x, &i, &pos, end, &s))
+      copy_bytes<SK_THREADS>(dst + (s.pos - p0), staging + (size_t)job_of_frame[s.frame] * slot + s.in_frame, (u32)s.len, threadIdx.x);
   }
 }
 
@@ -460,20 +614,31 @@ SeekJobs seek_read_jobs(u8 *base, size_t n) {
   return j;
 }
 
+// The control block zeroed, then the two scan kernels: the table's verdict, and the range's when
+// one is given (a batched read gives offset 0, length 0 and judges its ranges itself).
+static hipError_t seek_scan_launch(const void *d_stream, size_t size, size_t n, u32 entry, u64 offset, u64 length, u8 *base, hipStream_t stream) {
+  ReadLayout const L = ReadLayout::make(n);
+  SeekReadCtl *const ctl = (SeekReadCtl *)(base + L.ctl);
+  u64 *const tbc = (u64 *)(base + L.tbc), *const tbd = (u64 *)(base + L.tbd);
+  hipError_t e = hipMemsetAsync(ctl, 0, sizeof(SeekReadCtl), stream);
+  if (e != hipSuccess) return e;
+  u32 const nt = (u32)sk_tiles(n);
+  // (n == 0: the footer is still parsed on the device, by one workgroup that finds no entry)
+  hipLaunchKernelGGL(zh_seek_index_tile_kernel, dim3(std::max(nt, 1u)), dim3(SK_THREADS), 0, stream, (const u8 *)d_stream, (u64)size, (u32)n,
+                     (u64 *)(base + L.lc), (u64 *)(base + L.ld), tbc, tbd, ctl);
+  hipLaunchKernelGGL(zh_seek_index_sums_kernel, dim3(1), dim3(SK_THREADS), 0, stream, tbc, tbd, n ? nt : 0u, (u64)size,
+                     (u64)n * entry + ZH_SEEK_OVERHEAD, offset, length, ctl);
+  return hipSuccess;
+}
+
 hipError_t seek_index_launch(const void *d_stream, size_t size, size_t n, u32 entry, u64 offset, u64 length, void *d_out, u8 *base,
                              hipStream_t stream) {
   ReadLayout const L = ReadLayout::make(n);
   SeekReadCtl *const ctl = (SeekReadCtl *)(base + L.ctl);
   u64 *const lc = (u64 *)(base + L.lc), *const ld = (u64 *)(base + L.ld), *const tbc = (u64 *)(base + L.tbc), *const tbd = (u64 *)(base + L.tbd);
-  hipError_t e = hipMemsetAsync(ctl, 0, sizeof(SeekReadCtl), stream);
+  hipError_t const e = seek_scan_launch(d_stream, size, n, entry, offset, length, base, stream);
   if (e != hipSuccess) return e;
-  u32 const nt = (u32)sk_tiles(n);
-  // (n == 0: the footer is still parsed on the device, by one workgroup that finds no entry)
-  hipLaunchKernelGGL(zh_seek_index_tile_kernel, dim3(std::max(nt, 1u)), dim3(SK_THREADS), 0, stream, (const u8 *)d_stream, (u64)size, (u32)n, lc, ld,
-                     tbc, tbd, ctl);
   u64 const table_bytes = (u64)n * entry + ZH_SEEK_OVERHEAD;
-  hipLaunchKernelGGL(zh_seek_index_sums_kernel, dim3(1), dim3(SK_THREADS), 0, stream, tbc, tbd, n ? nt : 0u, (u64)size, table_bytes, offset, length,
-                     ctl);
   if (n)
     hipLaunchKernelGGL(zh_seek_index_jobs_kernel, dim3((u32)((n + SK_THREADS - 1) / SK_THREADS)), dim3(SK_THREADS), 0, stream,
                        (const u8 *)d_stream, (u64)size, (u32)n, entry, table_bytes, lc, ld, tbc, tbd, offset, length, (u8 *)d_out, base + L.total,
@@ -487,6 +652,59 @@ hipError_t seek_trim_launch(const void *d_stream, size_t size, size_t n, u32 ent
   ReadLayout const L = ReadLayout::make(n);
   hipLaunchKernelGGL(zh_seek_trim_kernel, dim3(njobs), dim3(64), 0, stream, (const u8 *)d_stream, (u64)size, entry,
                      (u64)n * entry + ZH_SEEK_OVERHEAD, offset, length, (u8 *)d_out, verify, (SeekReadCtl *)(base + L.ctl), seek_read_jobs(base, n));
+  return hipGetLastError();
+}
+
+ZhSeekRangesLayout seek_ranges_layout(size_t n, size_t num_ranges, size_t jobs, size_t max_d, size_t dec_bytes) {
+  return zh_seek_ranges_layout(ReadLayout::make(n).total, n, num_ranges, jobs, max_d, dec_bytes);
+}
+
+hipError_t seek_ranges_index_launch(const void *d_stream, size_t size, size_t n, u32 entry, const unsigned long long *d_offsets,
+                                    const size_t *d_lengths, size_t num_ranges, size_t max_length, u8 *base, hipStream_t stream) {
+  ReadLayout const L = ReadLayout::make(n);
+  ZhSeekRangesLayout const R = seek_ranges_layout(n, num_ranges, 0, 0, 0);
+  SeekReadCtl *const ctl = (SeekReadCtl *)(base + L.ctl);
+  const u64 *const lc = (const u64 *)(base + L.lc), *const ld = (const u64 *)(base + L.ld), *const tbc = (const u64 *)(base + L.tbc),
+                   *const tbd = (const u64 *)(base + L.tbd);
+  u32 *const bitmap = (u32 *)(base + R.bitmap), *const jof = (u32 *)(base + R.job_of_frame);
+  // (offset 0, length 0: the table's verdict alone; the ranges get theirs from the mark kernel)
+  hipError_t e = seek_scan_launch(d_stream, size, n, entry, 0, 0, base, stream);
+  if (e != hipSuccess) return e;
+  u64 const table_bytes = (u64)n * entry + ZH_SEEK_OVERHEAD;
+  if (n) {
+    if ((e = hipMemsetAsync(bitmap, 0, R.bitmap_bytes, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(jof, 0xFF, n * 4, stream)) != hipSuccess) return e;
+  }
+  u32 const rgrid = (u32)std::min<u64>(((u64)num_ranges + 3) / 4, 1u << 20);  // more ranges stride the grid
+  hipLaunchKernelGGL(zh_seek_ranges_mark_kernel, dim3(rgrid), dim3(SK_THREADS), 0, stream, (const u64 *)d_offsets, d_lengths, (u64)num_ranges,
+                     (u64)max_length, (u32)n, ld, tbd, ctl, (u32 *)(base + R.first), (u32 *)(base + R.last), bitmap);
+  if (n)
+    hipLaunchKernelGGL(zh_seek_ranges_jobs_kernel, dim3((u32)((n + SK_THREADS - 1) / SK_THREADS)), dim3(SK_THREADS), 0, stream,
+                       (const u8 *)d_stream, (u64)size, (u32)n, entry, table_bytes, lc, tbc, bitmap, base + R.staging, ctl, seek_read_jobs(base, n),
+                       jof);
+  return hipGetLastError();
+}
+
+hipError_t seek_ranges_finish_launch(const void *d_stream, size_t size, size_t n, u32 entry, u32 njobs, const unsigned long long *d_offsets,
+                                     const size_t *d_lengths, void *const *d_out_ptrs, size_t num_ranges, size_t max_length, int verify,
+                                     int *d_range_statuses, u8 *base, hipStream_t stream) {
+  ReadLayout const L = ReadLayout::make(n);
+  ZhSeekRangesLayout const R = seek_ranges_layout(n, num_ranges, 0, 0, 0);
+  SeekJobs const jobs = seek_read_jobs(base, n);
+  const u32 *const jof = (const u32 *)(base + R.job_of_frame);
+  if (njobs)
+    hipLaunchKernelGGL(zh_seek_ranges_check_kernel, dim3(njobs), dim3(64), 0, stream, (const u8 *)d_stream, (u64)size, entry,
+                       (u64)n * entry + ZH_SEEK_OVERHEAD, verify, jobs);
+  u32 const rgrid = (u32)std::min<u64>(((u64)num_ranges + 3) / 4, 1u << 20);
+  hipLaunchKernelGGL(zh_seek_ranges_status_kernel, dim3(rgrid), dim3(SK_THREADS), 0, stream, (u64)num_ranges, (const u32 *)(base + R.first),
+                     (const u32 *)(base + R.last), jof, jobs, d_range_statuses);
+  if (njobs && max_length) {
+    u64 const ppr = std::min<u64>(((u64)max_length + SK_PIECE - 1) / SK_PIECE, 0xFFFFFFFFull);
+    u32 const grid = (u32)std::min<u64>((u64)num_ranges * ppr, 1u << 22);  // larger batches stride the grid
+    hipLaunchKernelGGL(zh_seek_ranges_scatter_kernel, dim3(grid), dim3(SK_THREADS), 0, stream, (const u64 *)d_offsets, d_lengths, d_out_ptrs,
+                       (const int *)d_range_statuses, (u64)num_ranges, (u32)ppr, (u32)n, (const u64 *)(base + L.ld), (const u64 *)(base + L.tbd),
+                       (const SeekReadCtl *)(base + L.ctl), jof, (const u8 *)(base + R.staging));
+  }
   return hipGetLastError();
 }
 

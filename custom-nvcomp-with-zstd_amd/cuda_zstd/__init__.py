@@ -139,6 +139,8 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_seekable_read_get_temp_size": (sz, [sz, sz]),
             "cuda_zstd_seekable_read_get_temp_size_jobs": (sz, [sz, sz, sz]),
             "cuda_zstd_seekable_read": (i, [vp, vp, sz, ctypes.c_ulonglong, sz, vp, psz, i, vp, sz, vp]),
+            "cuda_zstd_seekable_read_ranges_get_temp_size": (sz, [sz, sz, sz, sz]),
+            "cuda_zstd_seekable_read_ranges": (i, [vp, vp, sz, vp, vp, vp, sz, sz, i, vp, psz, vp, sz, vp]),
             "cuda_zstd_set_long_distance": (i, [vp, i, ctypes.c_uint, ctypes.c_uint]),
             "cuda_zstd_set_checksum": (i, [vp, i]),
             "cuda_zstd_set_dict_entropy": (i, [vp, i]),
@@ -1300,6 +1302,68 @@ class SeekableReader:
 
     def read_all(self, verify: bool = False, stream=None):
         return self.read(0, self.size, verify, stream)
+
+    def read_ranges(self, offsets, lengths, verify: bool = False, stream=None, raise_on_error: bool = True):
+        """Many ranges in one device call (cuda_zstd_seekable_read_ranges): the table is scanned
+        once and a frame that several ranges touch is decoded once.  offsets, lengths: sequences
+        of ints or CUDA int64 tensors (the offsets then never leave the device).  Returns one
+        view per range of a packed device buffer, range i at the sum of the earlier lengths (a
+        list of bytes from a reader over host bytes).  A failed range (past the content, or over
+        a frame that does not decode or verify) raises ZstdError with the first such range's
+        code; with raise_on_error=False the result is (list, statuses), statuses an int32 host
+        tensor, and a failed range's bytes are unspecified."""
+        torch = _torch()
+        dev = self._buf.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if len(lengths) == 0 and len(offsets) == 0:
+            return [] if raise_on_error else ([], torch.zeros(0, dtype=torch.int32))
+        with torch.cuda.stream(s):
+            d_off = offsets.to(torch.int64).contiguous() if _is_cuda_tensor(offsets) else \
+                torch.tensor([int(v) for v in offsets], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+            if _is_cuda_tensor(lengths):
+                d_len = lengths.to(torch.int64).contiguous()
+                lens = [int(v) for v in d_len.cpu()]  # the views are cut on the host: waits for the lengths
+            else:
+                lens = [int(v) for v in lengths]
+                d_len = torch.tensor(lens, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+            r = len(lens)
+            if d_off.numel() != r or any(v < 0 for v in lens):
+                raise ZstdError(INVALID, "SeekableReader.read_ranges")
+            total, max_length = sum(lens), max(lens)
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+            d_ptrs = out.data_ptr() + torch.cumsum(d_len, 0) - d_len  # range i at the sum of the earlier lengths
+            statuses = torch.zeros(r, dtype=torch.int32, device=dev)
+            # temp for the frames an evenly split stream would touch; the full table's on TOO_SMALL
+            avg = max(1, self.size // max(self.num_frames, 1))
+            jobs = min(self.num_frames, total // avg + 2 * r)
+            while True:
+                need = lib().cuda_zstd_seekable_read_ranges_get_temp_size(self.num_frames, r, jobs, self.max_frame)
+                if self._temp is None or self._temp.numel() < need:
+                    self._temp = None
+                    self._temp = torch.empty(need, dtype=torch.uint8, device=dev)
+                for t in (self._buf, self._temp, d_off, d_len):
+                    t.record_stream(s)
+                rc = lib().cuda_zstd_seekable_read_ranges(self._mgr._h, self._buf.data_ptr(), self._buf.numel(), d_off.data_ptr(), d_len.data_ptr(),
+                                                          d_ptrs.data_ptr(), r, max_length, 1 if verify else 0, statuses.data_ptr(), None,
+                                                          self._temp.data_ptr(), self._temp.numel(), s.cuda_stream)
+                if rc != TOO_SMALL or jobs >= self.num_frames:
+                    break
+                jobs = self.num_frames
+            if rc:
+                raise ZstdError(rc, "cuda_zstd_seekable_read_ranges")
+            st = statuses.cpu()  # (the call has waited for the stream)
+            host = out.cpu() if self._host else None
+        if raise_on_error and bool(st.any()):
+            raise ZstdError(int(st[st != 0][0]), "cuda_zstd_seekable_read_ranges")
+        starts = [0] * r
+        for k in range(1, r):
+            starts[k] = starts[k - 1] + lens[k - 1]
+        if self._host:
+            hb = host.numpy().tobytes()
+            views = [hb[a:a + n] for a, n in zip(starts, lens)]
+        else:
+            views = [out[a:a + n] for a, n in zip(starts, lens)]
+        return views if raise_on_error else (views, st)
 
 
 # Adaptive level selection (cuda_zstd_adaptive_*; reference adaptive::AdaptiveLevelSelector,

@@ -438,7 +438,21 @@ int cuda_zstd_extract_metadata(const void *src, size_t size, unsigned int *compr
  * part: nothing is launched; below the part sized by the frames the range covers: no decode is
  * launched), 10 a checksum mismatch with verify_checksums on a checksummed stream, or the first
  * failing frame's decoder code.  read_get_temp_size covers any range; _jobs covers ranges that
- * touch at most max_jobs frames with content. */
+ * touch at most max_jobs frames with content.
+ *
+ * read_ranges: num_ranges ranges of the content in one call.  d_offsets, d_lengths, d_out_ptrs
+ * and d_range_statuses are device arrays of num_ranges; the host never reads the first three.
+ * The table is scanned once, every frame that a range touches is decoded once (into a staging
+ * slot in d_temp) and range r's bytes are copied to d_out_ptrs[r].  Ranges may overlap, repeat
+ * and come in any order; max_length bounds every length.  Blocking: one wait for the number of
+ * frames to decode, one at the end.  The return value is the call's: 2 a bad argument, 6 a
+ * damaged table, 7 a temp buffer below read_ranges_get_temp_size(num_frames, num_ranges, frames
+ * the ranges touch, largest Decompressed_Size); then no status and no destination is written.
+ * Otherwise 0, and d_range_statuses[r] = 0, or 2 for offset + length past the content or
+ * length > max_length, or the code (a decoder code, 6 for a size that disagrees with the table,
+ * 10 for a checksum mismatch with verify_checksums) of the lowest failing frame the range
+ * touches; no byte of a failed range's destination is written.  A length of 0 is valid.
+ * *frames_decoded (host, optional) = the number of frames decoded. */
 size_t cuda_zstd_seekable_max_size(size_t num_frames, size_t max_compressed_chunk_bytes, int with_checksums);
 size_t cuda_zstd_seekable_pack_get_temp_size(size_t num_frames);
 int cuda_zstd_seekable_pack_async(const void *const *d_frame_ptrs, const size_t *d_frame_sizes, const int *d_frame_statuses,
@@ -451,6 +465,10 @@ size_t cuda_zstd_seekable_read_get_temp_size(size_t num_frames, size_t max_frame
 size_t cuda_zstd_seekable_read_get_temp_size_jobs(size_t num_frames, size_t max_jobs, size_t max_frame_uncompressed);
 int cuda_zstd_seekable_read(nvcomp_zstd_batch_manager_t *mgr, const void *d_stream, size_t size, unsigned long long offset, size_t length,
                             void *d_out, size_t *written, int verify_checksums, void *d_temp, size_t temp_bytes, hipStream_t stream);
+size_t cuda_zstd_seekable_read_ranges_get_temp_size(size_t num_frames, size_t num_ranges, size_t max_jobs, size_t max_frame_uncompressed);
+int cuda_zstd_seekable_read_ranges(nvcomp_zstd_batch_manager_t *mgr, const void *d_stream, size_t size, const unsigned long long *d_offsets,
+                                   const size_t *d_lengths, void *const *d_out_ptrs, size_t num_ranges, size_t max_length, int verify_checksums,
+                                   int *d_range_statuses, size_t *frames_decoded, void *d_temp, size_t temp_bytes, hipStream_t stream);
 
 /* ---------------- adaptive level selection ----------------
  * C counterpart of include/cuda_zstd_adaptive.h (reference adaptive::AdaptiveLevelSelector), for
