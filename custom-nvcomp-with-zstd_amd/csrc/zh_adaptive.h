@@ -1,5 +1,5 @@
 // zh_adaptive.h — adaptive level selection: the rule shared by the finalize kernel
-// (zh_adaptive.hip) and the host entries (zh_host.cpp), and the kernels' launch entry.
+// (zh_adaptive.hip) and the host entries (zh_host_adaptive.cpp), and the kernels' launch entry.
 //
 // Statistics of a chunk's first n = min(size, sample_bytes) bytes a[0..n) (DESIGN.md "Adaptive
 // level selection"; the reference's selector, src/cuda_zstd_adaptive.cu, restated as exact

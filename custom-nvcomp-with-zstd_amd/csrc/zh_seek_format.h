@@ -1,5 +1,5 @@
 // zh_seek_format.h — the Zstandard seekable format's seek table: sizes, limits, encode and
-// validate, shared by the device kernels (zh_seek.hip) and the host (zh_host.cpp's info call on
+// validate, shared by the device kernels (zh_seek.hip) and the host (zh_host_seek.cpp's info call on
 // a host buffer).  Plain integer code, no HIP calls.
 //
 //   u32 0x184D2A5E | u32 Frame_Size = N*E + 9 | N x { u32 csize; u32 dsize; [u32 checksum] }

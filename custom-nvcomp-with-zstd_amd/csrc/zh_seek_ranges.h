@@ -1,5 +1,5 @@
 // zh_seek_ranges.h — the arithmetic of a batched range read of a seekable stream, shared by the
-// device kernels (zh_seek.hip), the host (zh_host.cpp) and a stand-alone host check
+// device kernels (zh_seek.hip), the host (zh_host_seek.cpp) and a stand-alone host check
 // (tests/cpp/seek_ranges_check.cpp).  Plain integer code, no HIP calls.
 //
 // The scanned table is two arrays: ld[i], the content offset of entry i inside its tile of

@@ -355,6 +355,18 @@ class Manager:
             raise ZstdError(INVALID, "cuda_zstd_hip_ldm_plan")
         return rec[:got]
 
+    @staticmethod
+    def _batch_arrays(ins, caps):
+        """compress_batch / decompress_batch: one output buffer with a 256-byte aligned slot of caps[k]
+        bytes per item (its offsets), and the C arrays of the batch entries."""
+        n = len(ins)
+        offs = [0]
+        for c in caps:
+            offs.append(offs[-1] + ((max(c, 1) + 255) // 256) * 256)
+        out = _torch().empty(max(offs[-1], 256), dtype=_torch().uint8, device="cuda")
+        return (offs, out, (ctypes.c_void_p * n)(*[t.data_ptr() for t in ins]), (ctypes.c_void_p * n)(*[out.data_ptr() + o for o in offs[:-1]]),
+                (ctypes.c_size_t * n)(*[t.numel() for t in ins]), (ctypes.c_size_t * n)(*caps), (ctypes.c_int * n)())
+
     def compress_batch(self, chunks: Sequence, stream=None) -> List:
         """ZstdBatchManager::compress_batch over a list of uint8 device tensors (host inputs:
         a list of bytes back)."""
@@ -363,17 +375,7 @@ class Manager:
         torch = _torch()
         n = len(chunks)
         ins = [c.contiguous().view(torch.uint8) for c in chunks]
-        sizes = [t.numel() for t in ins]
-        caps = [max_compressed_size(s) for s in sizes]
-        offs = [0]
-        for c in caps:
-            offs.append(offs[-1] + ((c + 255) // 256) * 256)
-        out = torch.empty(offs[-1], dtype=torch.uint8, device="cuda")
-        in_ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ins])
-        out_ptrs = (ctypes.c_void_p * n)(*[out.data_ptr() + o for o in offs[:-1]])
-        in_sz = (ctypes.c_size_t * n)(*sizes)
-        out_sz = (ctypes.c_size_t * n)(*caps)
-        st = (ctypes.c_int * n)()
+        offs, out, in_ptrs, out_ptrs, in_sz, out_sz, st = self._batch_arrays(ins, [max_compressed_size(t.numel()) for t in ins])
         ws_n = lib().cuda_zstd_get_batch_compress_workspace_size(self._h, in_sz, n)
         ws = self._workspace(ws_n)
         rc = lib().cuda_zstd_compress_batch(self._h, in_ptrs, in_sz, n, out_ptrs, out_sz, st, ws.data_ptr(), ws.numel(), _stream_ptr(stream))
@@ -385,7 +387,6 @@ class Manager:
                 raise ZstdError(st[k], f"cuda_zstd_compress_batch item {k}")
             res.append(out[offs[k] : offs[k] + out_sz[k]])
         return res
-
 
     def set_dictionary(self, d: "Dictionary"):
         """ZstdManager::set_dictionary: later compress / decompress calls use `d`."""
@@ -442,15 +443,7 @@ class Manager:
         ins = [f.contiguous().view(torch.uint8) for f in frames]
         if capacities is None:
             capacities = [c for c, _ in self._capacities(ins, stream)]
-        offs = [0]
-        for c in capacities:
-            offs.append(offs[-1] + ((max(c, 1) + 255) // 256) * 256)
-        out = torch.empty(max(offs[-1], 256), dtype=torch.uint8, device="cuda")
-        in_ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ins])
-        out_ptrs = (ctypes.c_void_p * n)(*[out.data_ptr() + o for o in offs[:-1]])
-        in_sz = (ctypes.c_size_t * n)(*[t.numel() for t in ins])
-        out_sz = (ctypes.c_size_t * n)(*capacities)
-        st = (ctypes.c_int * n)()
+        offs, out, in_ptrs, out_ptrs, in_sz, out_sz, st = self._batch_arrays(ins, capacities)
         ws = self._workspace(lib().cuda_zstd_get_batch_decompress_workspace_size(self._h, in_sz, n))
         rc = lib().cuda_zstd_decompress_batch(self._h, in_ptrs, in_sz, n, out_ptrs, out_sz, st, ws.data_ptr(), ws.numel(), _stream_ptr(stream))
         if rc and all(s == OK for s in st):
@@ -1461,6 +1454,49 @@ def adaptive_finalize_host(hist, repeated_pairs: int, max_run_length: int, patte
     return _stats_dict(out)
 
 
+def _one_call_batch(what: str, handle, ins, *, slot: int, rows: dict, index=None, record, temp_bytes: int, call, host: bool, stream) -> List:
+    """The batched one-call functions below, after their argument checks: one pinned int64 table of
+    named rows ("in": the inputs' addresses, "in_size", "out": the output slots, then `rows`), sizes,
+    statuses and temp, call(t, d_index, d_sizes, d_status, temp, stream) with t[name] the device row,
+    and one stacked copy back, the single wait; then `handle` is closed and `out` sliced by slot.
+    index: None, a device int32 tensor, or ints that go up from pinned memory.  record: the tensors
+    the call reads."""
+    torch = _torch()
+    n, s = len(ins), stream
+    with torch.cuda.stream(s):
+        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
+        host_rows = {"in": [t.data_ptr() if t.numel() else 0 for t in ins], "in_size": [t.numel() for t in ins],
+                     "out": [out.data_ptr() + k * slot for k in range(n)], **rows}
+        d_table = torch.tensor(list(host_rows.values()), dtype=torch.int64).pin_memory().to("cuda", non_blocking=True)
+        t = dict(zip(host_rows, d_table))
+        if index is not None and not _is_cuda_tensor(index):
+            index = torch.tensor(index, dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
+        if s != torch.cuda.current_stream():  # (the inputs' allocator stream is the current one)
+            for r in record:
+                r.record_stream(s)
+        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
+        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
+        temp = torch.empty(temp_bytes, dtype=torch.uint8, device="cuda")
+        call(t, index, d_sizes, d_status, temp, s)
+        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()  # the one wait (stream-ordered copy)
+    handle.close()
+    res = []
+    for k in range(n):
+        if got_status[k] != OK:
+            raise ZstdError(got_status[k], f"{what} item {k}")
+        f = out[k * slot : k * slot + got_sizes[k]]
+        res.append(_host_bytes(f) if host else f)
+    return res
+
+
+def _slot(nbytes: int) -> int:
+    return ((nbytes + 255) // 256) * 256
+
+
+def _uploaded(items, torch):
+    return [(_to_device(c) if _is_host(c) else c).contiguous().view(torch.uint8) for c in items]
+
+
 def compress_batch_levels(chunks: Sequence, levels, checksum: bool = False, stream=None) -> List:
     """Compress chunk i (uint8 device tensors) at levels[i] in one stream-ordered call
     (nvcomp_zstd_batched_compress_levels_async_v5) -> the frames in input order, each the bytes
@@ -1473,44 +1509,29 @@ def compress_batch_levels(chunks: Sequence, levels, checksum: bool = False, stre
         return []
     s = stream if stream is not None else torch.cuda.current_stream()
     ins = [c.contiguous().view(torch.uint8) for c in chunks]
-    sizes = [t.numel() for t in ins]
-    max_chunk = max(max(sizes), 1)
-    slot = ((max_compressed_size(max_chunk) + 255) // 256) * 256
+    max_chunk = max(max(t.numel() for t in ins), 1)
+    if _is_cuda_tensor(levels):
+        with torch.cuda.stream(s):
+            levels = levels.to(torch.int32).contiguous()
+    else:
+        levels = [int(v) for v in levels]
+    if (levels.numel() if _is_cuda_tensor(levels) else len(levels)) != n:
+        raise ZstdError(INVALID, "compress_batch_levels: one level per chunk")
     bc = BatchedCompressor(3, checksum=checksum)  # (the level of the handle is not used)
-    with torch.cuda.stream(s):
-        if _is_cuda_tensor(levels):
-            d_levels = levels.to(torch.int32).contiguous()
-        else:
-            d_levels = torch.tensor([int(v) for v in levels], dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
-        if d_levels.numel() != n:
-            raise ZstdError(INVALID, "compress_batch_levels: one level per chunk")
-        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
-        table = torch.tensor([[t.data_ptr() for t in ins], sizes, [out.data_ptr() + k * slot for k in range(n)]], dtype=torch.int64)
-        d_table = table.pin_memory().to("cuda", non_blocking=True)
-        if s != torch.cuda.current_stream():  # (the inputs' allocator stream is the current one)
-            for t in ins:
-                t.record_stream(s)
-        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
-        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
-        temp = torch.empty(bc.temp_size_levels(n, max_chunk), dtype=torch.uint8, device="cuda")
-        bc.compress_levels_async(d_table[0], d_table[1], d_levels, max_chunk, d_table[2], d_sizes, d_status, temp, s)
-        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()  # the one wait (stream-ordered copy)
-    bc.close()
-    res = []
-    for k in range(n):
-        if got_status[k] != OK:
-            raise ZstdError(got_status[k], f"compress_batch_levels item {k}")
-        res.append(out[k * slot : k * slot + got_sizes[k]])
-    return res
+    return _one_call_batch("compress_batch_levels", bc, ins, slot=_slot(max_compressed_size(max_chunk)), rows={}, index=levels, record=ins,
+                           temp_bytes=bc.temp_size_levels(n, max_chunk), host=False, stream=s,
+                           call=lambda t, lv, sz, st, temp, s: bc.compress_levels_async(t["in"], t["in_size"], lv, max_chunk, t["out"], sz, st, temp, s))
 
 
 def _prefix_table(items, prefixes, torch):
-    """Device tensors of the items and their prefixes (hosts are uploaded; None: no prefix)."""
-    ins = [(_to_device(c) if _is_host(c) else c).contiguous().view(torch.uint8) for c in items]
+    """Device tensors of the items and their prefixes (hosts are uploaded; None: no prefix), and
+    the prefixes' table rows."""
+    ins = _uploaded(items, torch)
     if len(prefixes) != len(ins):
         raise ZstdError(INVALID, "one prefix (or None) per item")
-    pre = [None if p is None else (_to_device(p) if _is_host(p) else p).contiguous().view(torch.uint8) for p in prefixes]
-    return ins, pre
+    pre = [None if p is None else _uploaded([p], torch)[0] for p in prefixes]
+    return ins, [p for p in pre if p is not None], {"pre": [0 if p is None or not p.numel() else p.data_ptr() for p in pre],
+                                                    "pre_size": [0 if p is None else p.numel() for p in pre]}
 
 
 def compress_batch_prefix(chunks: Sequence, prefixes: Sequence, level: int = 3, checksum: bool = False, stream=None) -> List:
@@ -1522,35 +1543,14 @@ def compress_batch_prefix(chunks: Sequence, prefixes: Sequence, level: int = 3, 
     n = len(chunks)
     if n == 0:
         return []
-    host = _is_host(chunks[0])
     s = stream if stream is not None else torch.cuda.current_stream()
-    ins, pre = _prefix_table(chunks, prefixes, torch)
-    sizes = [t.numel() for t in ins]
-    max_chunk = max(max(sizes), 1)
+    ins, pre, rows = _prefix_table(chunks, prefixes, torch)
+    max_chunk = max(max(t.numel() for t in ins), 1)
     bc = BatchedCompressor(level, checksum=checksum)
-    slot = ((bc.max_out(max_chunk) + 255) // 256) * 256
-    with torch.cuda.stream(s):
-        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
-        table = torch.tensor([[t.data_ptr() if t.numel() else 0 for t in ins], sizes, [out.data_ptr() + k * slot for k in range(n)],
-                              [0 if p is None or not p.numel() else p.data_ptr() for p in pre],
-                              [0 if p is None else p.numel() for p in pre]], dtype=torch.int64)
-        d_table = table.pin_memory().to("cuda", non_blocking=True)
-        if s != torch.cuda.current_stream():
-            for t in ins + [p for p in pre if p is not None]:
-                t.record_stream(s)
-        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
-        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
-        temp = torch.empty(bc.temp_size_prefix(n, max_chunk), dtype=torch.uint8, device="cuda")
-        bc.compress_prefix_async(d_table[0], d_table[1], d_table[3], d_table[4], max_chunk, d_table[2], d_sizes, d_status, temp, s)
-        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
-    bc.close()
-    res = []
-    for k in range(n):
-        if got_status[k] != OK:
-            raise ZstdError(got_status[k], f"compress_batch_prefix item {k}")
-        f = out[k * slot : k * slot + got_sizes[k]]
-        res.append(_host_bytes(f) if host else f)
-    return res
+    return _one_call_batch("compress_batch_prefix", bc, ins, slot=_slot(bc.max_out(max_chunk)), rows=rows, record=ins + pre,
+                           temp_bytes=bc.temp_size_prefix(n, max_chunk), host=_is_host(chunks[0]), stream=s,
+                           call=lambda t, _, sz, st, temp, s: bc.compress_prefix_async(t["in"], t["in_size"], t["pre"], t["pre_size"], max_chunk, t["out"],
+                                                                                       sz, st, temp, s))
 
 
 def decompress_batch_prefix(frames: Sequence, prefixes: Sequence, capacities=None, stream=None) -> List:
@@ -1561,36 +1561,15 @@ def decompress_batch_prefix(frames: Sequence, prefixes: Sequence, capacities=Non
     n = len(frames)
     if n == 0:
         return []
-    host = _is_host(frames[0])
     s = stream if stream is not None else torch.cuda.current_stream()
-    ins, pre = _prefix_table(frames, prefixes, torch)
+    ins, pre, rows = _prefix_table(frames, prefixes, torch)
     caps = [int(c) for c in capacities] if capacities is not None else [_frame_size(t) for t in ins]
     max_out = max(max(caps), 1)
-    slot = ((max_out + 255) // 256) * 256
     bd = BatchedDecompressor()
-    with torch.cuda.stream(s):
-        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
-        table = torch.tensor([[t.data_ptr() if t.numel() else 0 for t in ins], [t.numel() for t in ins],
-                              [out.data_ptr() + k * slot for k in range(n)], caps,
-                              [0 if p is None or not p.numel() else p.data_ptr() for p in pre],
-                              [0 if p is None else p.numel() for p in pre]], dtype=torch.int64)
-        d_table = table.pin_memory().to("cuda", non_blocking=True)
-        if s != torch.cuda.current_stream():
-            for t in ins + [p for p in pre if p is not None]:
-                t.record_stream(s)
-        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
-        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
-        temp = torch.empty(bd.temp_size(n, max_out), dtype=torch.uint8, device="cuda")
-        bd.decompress_prefix_async(d_table[0], d_table[1], d_table[4], d_table[5], d_table[3], max_out, d_table[2], d_sizes, d_status, temp, s)
-        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
-    bd.close()
-    res = []
-    for k in range(n):
-        if got_status[k] != OK:
-            raise ZstdError(got_status[k], f"decompress_batch_prefix item {k}")
-        f = out[k * slot : k * slot + got_sizes[k]]
-        res.append(_host_bytes(f) if host else f)
-    return res
+    return _one_call_batch("decompress_batch_prefix", bd, ins, slot=_slot(max_out), rows={"cap": caps, **rows}, record=ins + pre,
+                           temp_bytes=bd.temp_size(n, max_out), host=_is_host(frames[0]), stream=s,
+                           call=lambda t, _, sz, st, temp, s: bd.decompress_prefix_async(t["in"], t["in_size"], t["pre"], t["pre_size"], t["cap"], max_out,
+                                                                                         t["out"], sz, st, temp, s))
 
 
 def compress_batch_dicts(chunks: Sequence, dict_set: "DictionarySet", indices: Sequence[int], level: int = 3, checksum: bool = False,
@@ -1605,36 +1584,14 @@ def compress_batch_dicts(chunks: Sequence, dict_set: "DictionarySet", indices: S
         return []
     if len(indices) != n:
         raise ZstdError(INVALID, "one entry index (or -1) per chunk")
-    host = _is_host(chunks[0])
     s = stream if stream is not None else torch.cuda.current_stream()
-    ins = [(_to_device(c) if _is_host(c) else c).contiguous().view(torch.uint8) for c in chunks]
-    sizes = [t.numel() for t in ins]
-    max_chunk = max(max(sizes), 1)
+    ins = _uploaded(chunks, torch)
+    max_chunk = max(max(t.numel() for t in ins), 1)
     bc = BatchedCompressor(level, checksum=checksum, dict_entropy=dict_entropy)
     bc.set_dictionary_set(dict_set)
-    slot = ((bc.max_out(max_chunk) + 255) // 256) * 256
-    with torch.cuda.stream(s):
-        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
-        table = torch.tensor([[t.data_ptr() if t.numel() else 0 for t in ins], sizes, [out.data_ptr() + k * slot for k in range(n)]],
-                             dtype=torch.int64)
-        d_table = table.pin_memory().to("cuda", non_blocking=True)
-        d_index = torch.tensor([int(i) for i in indices], dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
-        if s != torch.cuda.current_stream():
-            for t in ins:
-                t.record_stream(s)
-        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
-        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
-        temp = torch.empty(bc.temp_size_dicts(n, max_chunk), dtype=torch.uint8, device="cuda")
-        bc.compress_dicts_async(d_table[0], d_table[1], d_index, max_chunk, d_table[2], d_sizes, d_status, temp, s)
-        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
-    bc.close()
-    res = []
-    for k in range(n):
-        if got_status[k] != OK:
-            raise ZstdError(got_status[k], f"compress_batch_dicts item {k}")
-        f = out[k * slot : k * slot + got_sizes[k]]
-        res.append(_host_bytes(f) if host else f)
-    return res
+    return _one_call_batch("compress_batch_dicts", bc, ins, slot=_slot(bc.max_out(max_chunk)), rows={}, index=[int(i) for i in indices], record=ins,
+                           temp_bytes=bc.temp_size_dicts(n, max_chunk), host=_is_host(chunks[0]), stream=s,
+                           call=lambda t, ix, sz, st, temp, s: bc.compress_dicts_async(t["in"], t["in_size"], ix, max_chunk, t["out"], sz, st, temp, s))
 
 
 def decompress_batch_dicts(frames: Sequence, dict_set: "DictionarySet", indices: Sequence[int] = None, capacities=None, stream=None) -> List:
@@ -1649,36 +1606,16 @@ def decompress_batch_dicts(frames: Sequence, dict_set: "DictionarySet", indices:
         return []
     if indices is not None and len(indices) != n:
         raise ZstdError(INVALID, "one entry index (or -1) per frame")
-    host = _is_host(frames[0])
     s = stream if stream is not None else torch.cuda.current_stream()
-    ins = [(_to_device(c) if _is_host(c) else c).contiguous().view(torch.uint8) for c in frames]
+    ins = _uploaded(frames, torch)
     caps = [int(c) for c in capacities] if capacities is not None else [_frame_size(t) for t in ins]
     max_out = max(max(caps), 1)
-    slot = ((max_out + 255) // 256) * 256
     bd = BatchedDecompressor()
     bd.set_dictionary_set(dict_set)
-    with torch.cuda.stream(s):
-        out = torch.empty(n * slot, dtype=torch.uint8, device="cuda")
-        table = torch.tensor([[t.data_ptr() if t.numel() else 0 for t in ins], [t.numel() for t in ins],
-                              [out.data_ptr() + k * slot for k in range(n)], caps], dtype=torch.int64)
-        d_table = table.pin_memory().to("cuda", non_blocking=True)
-        d_index = None if indices is None else torch.tensor([int(i) for i in indices], dtype=torch.int32).pin_memory().to("cuda", non_blocking=True)
-        if s != torch.cuda.current_stream():
-            for t in ins:
-                t.record_stream(s)
-        d_sizes = torch.empty(n, dtype=torch.int64, device="cuda")
-        d_status = torch.empty(n, dtype=torch.int32, device="cuda")
-        temp = torch.empty(bd.temp_size(n, max_out), dtype=torch.uint8, device="cuda")
-        bd.decompress_dicts_async(d_table[0], d_table[1], d_index, d_table[3], max_out, d_table[2], d_sizes, d_status, temp, s)
-        got_sizes, got_status = torch.stack([d_sizes, d_status.to(torch.int64)]).cpu().tolist()
-    bd.close()
-    res = []
-    for k in range(n):
-        if got_status[k] != OK:
-            raise ZstdError(got_status[k], f"decompress_batch_dicts item {k}")
-        f = out[k * slot : k * slot + got_sizes[k]]
-        res.append(_host_bytes(f) if host else f)
-    return res
+    return _one_call_batch("decompress_batch_dicts", bd, ins, slot=_slot(max_out), rows={"cap": caps},
+                           index=None if indices is None else [int(i) for i in indices], record=ins, temp_bytes=bd.temp_size(n, max_out),
+                           host=_is_host(frames[0]), stream=s,
+                           call=lambda t, ix, sz, st, temp, s: bd.decompress_dicts_async(t["in"], t["in_size"], ix, t["cap"], max_out, t["out"], sz, st, temp, s))
 
 
 def compress_batch_adaptive(chunks: Sequence, preference: int = BALANCED, stream=None):

@@ -92,6 +92,24 @@ def test_hybrid_engine(cz, libzstd):
     assert cz.hybrid_decompress(cz.hybrid_compress(SMALL)) == SMALL
 
 
+@pytest.mark.parametrize("n", [65536, 65537])
+def test_hybrid_force_gpu_stages_host_buffers_both_ways(cz, libzstd, n):
+    """FORCE_GPU with host input and host output: the engine stages both buffers through device
+    memory around the device pipeline, compressing and decompressing.  65,536 bytes are a frame of one
+    device block; 65,537 bytes the smallest frame of more than one (a plain frame over 64 KiB is cut
+    into 32 KiB blocks, so it has three: no plain frame has exactly two).  The managers' cpu_threshold
+    is 0, so neither takes the libzstd route."""
+    d = T.gen(T.DG_TEXT, 1, 0x5EED0021, n).tobytes()
+    with cz.HybridEngine(cz.HybridConfig(cz.FORCE_GPU, 1 << 20, 0, 3, 0, 0)) as e:
+        c = e.compress(d)
+        assert e.last_result.backend_used == cz.GPU_KERNELS and e.last_result.output_bytes == len(c)
+        assert (e.last_result.input_location, e.last_result.output_location) == (cz.HOST, cz.HOST)
+        assert c == T.oracle_frame(np.frombuffer(d, np.uint8))
+        assert T.zstd_decompress(c, n) == d
+        assert e.decompress(c) == d
+        assert e.last_result.backend_used == cz.GPU_KERNELS and e.last_result.output_bytes == n
+
+
 def test_metadata_frame_on_device(cz):
     import torch
 

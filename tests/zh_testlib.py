@@ -112,7 +112,7 @@ def gen(kind, nchunks, seed, chunk_size=65536, first=0):
 
 
 def level_window_log(level):
-    """Window log of a level (apply_level_parameters, zh_host.cpp; reference src/cuda_zstd_types.cpp:860-950)."""
+    """Window log of a level (apply_level_parameters, zh_host_base.cpp; reference src/cuda_zstd_types.cpp:860-950)."""
     return 18 if level <= 1 else 19 if level <= 3 else 20 if level <= 6 else 22 if level <= 9 else 23
 
 

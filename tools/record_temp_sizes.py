@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Record what every public compress temp-size query of the library returns into
+"""Record what every public compress and decode temp-size query of the library returns into
 tests/golden/temp_sizes.json (tests/test_temp_sizes.py and tests/test_gpu_plan_routes.py compare
 against it).  Run it with the library of the commit whose sizes are the reference
 (CUDA_ZSTD_HIP_LIB selects another build).  It reads nothing but the library.
 
-  python tools/record_temp_sizes.py          the dictionary-less entries (no GPU needed)
+  python tools/record_temp_sizes.py          the dictionary-less entries, compress and decode (no GPU
+                                             needed); merges into the file
   python tools/record_temp_sizes.py --dict   adds the entries of a handle with a dictionary set
                                              (setting one needs a device); merges into the file
 """
@@ -23,6 +24,11 @@ FRAMES = [1, 65536, 65537, 1 << 20, 64 << 20]
 # tests/test_gpu_plan_routes.py: its batch, its dictionary's size and the levels it sets one at
 ROUTE_SIZES = [1, 32767, 32768, 32769, 65536, 65537, 98305, 163840]
 DICT_BYTES = 40 * 1024
+# the decode-side queries: counts and output capacities on both sides of the decoder slot's 64-byte
+# floor and 128 KiB cap
+DEC_COUNTS = [1, 2, 2049]
+DEC_CAPS = [1, 63, 64, 65, 131072, 131073]
+DEC_RANGES = 3  # ranges of a batched seekable read
 DICT_LEVELS = [3, 5]
 
 
@@ -45,6 +51,29 @@ def sizes_of(L):
         out["single_ldm"][str(lv)] = {str(n): L.cuda_zstd_get_compress_workspace_size(m, n) for n in FRAMES}
         L.nvcomp_zstd_batch_destroy_v5(h)
         L.cuda_zstd_destroy_manager(m)
+    return out
+
+
+def decode_sizes_of(L):
+    """The decode-side entries (no level: the decoder's workspace has none): {entry: {shape: bytes}}.
+    dec_single, dec_batch_workspace and dec_batch_temp size for 128 KiB blocks whatever the capacity
+    (they pin that and the count); the other three follow the capacity across the slot's 64-byte floor
+    and 128 KiB cap."""
+    key = lambda n, m: f"{n}x{m}"
+    arr = lambda v: (ctypes.c_size_t * len(v))(*v)
+    shapes = [(n, c) for n in DEC_COUNTS for c in DEC_CAPS]
+    m = L.cuda_zstd_create_manager(3)
+    h = L.nvcomp_zstd_batch_create_v5(3, 65536, 0)
+    out = {
+        "dec_single": {str(c): L.cuda_zstd_get_decompress_workspace_size(m, c) for c in DEC_CAPS},
+        "dec_batch_workspace": {key(n, c): L.cuda_zstd_get_batch_decompress_workspace_size(m, arr([c] * n), n) for n, c in shapes},
+        "dec_batch_temp": {key(n, c): L.nvcomp_zstd_batch_get_decompress_temp_size_v5(h, arr([c] * n), n) for n, c in shapes},
+        "dec_batched_temp": {key(n, c): L.nvcomp_zstd_batched_decompress_get_temp_size_v5(n, c) for n, c in shapes},
+        "seek_read_temp": {key(n, c): L.cuda_zstd_seekable_read_get_temp_size(n, c) for n, c in shapes},
+        "seek_ranges_temp": {key(n, c): L.cuda_zstd_seekable_read_ranges_get_temp_size(n, DEC_RANGES, n, c) for n, c in shapes},
+    }
+    L.nvcomp_zstd_batch_destroy_v5(h)
+    L.cuda_zstd_destroy_manager(m)
     return out
 
 
@@ -71,7 +100,12 @@ def main():
             doc = json.load(f)
         doc["dict_batched_temp"] = dict_sizes_of()
     else:
-        doc = sizes_of(cuda_zstd.lib())
+        doc = {}
+        if os.path.exists(OUT):  # (the --dict entries stay)
+            with open(OUT) as f:
+                doc = json.load(f)
+        doc.update(sizes_of(cuda_zstd.lib()))
+        doc.update(decode_sizes_of(cuda_zstd.lib()))
     with open(OUT, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
