@@ -141,6 +141,11 @@ def lib() -> ctypes.CDLL:
             "cuda_zstd_seekable_read": (i, [vp, vp, sz, ctypes.c_ulonglong, sz, vp, psz, i, vp, sz, vp]),
             "cuda_zstd_seekable_read_ranges_get_temp_size": (sz, [sz, sz, sz, sz]),
             "cuda_zstd_seekable_read_ranges": (i, [vp, vp, sz, vp, vp, vp, sz, sz, i, vp, psz, vp, sz, vp]),
+            "cuda_zstd_seekable_index_get_temp_size": (sz, [sz, sz]),
+            "cuda_zstd_seekable_index": (i, [vp, vp, sz, sz, vp, sz, psz, psz, ctypes.POINTER(ctypes.c_ulonglong), vp, sz, vp]),
+            "cuda_zstd_hip_frames_index_path": (None, [i]),
+            "cuda_zstd_hip_frames_index_last_path": (i, []),
+            "cuda_zstd_hip_frames_index_split": (None, [i, ctypes.POINTER(ctypes.c_float)]),
             "cuda_zstd_set_long_distance": (i, [vp, i, ctypes.c_uint, ctypes.c_uint]),
             "cuda_zstd_set_checksum": (i, [vp, i]),
             "cuda_zstd_set_dict_entropy": (i, [vp, i]),
@@ -1357,6 +1362,57 @@ class SeekableReader:
         else:
             views = [out[a:a + n] for a, n in zip(starts, lens)]
         return views if raise_on_error else (views, st)
+
+    @classmethod
+    def from_frames(cls, data, manager=None, max_frames: int = None, stream=None) -> "SeekableReader":
+        """A reader over concatenated frames that carry no seek table (pzstd output, joined .zst
+        files, frames written back to back): seekable_index builds the table on the device.
+        `manager` also decodes the frames, so its dictionary serves both."""
+        r = cls(seekable_index(data, max_frames, manager, stream), manager)
+        r._host = _is_host(data)
+        return r
+
+
+def seekable_index(data, max_frames: int = None, decoder=None, stream=None):
+    """Concatenated Zstandard (and skippable) frames -> a uint8 device tensor holding the same
+    bytes followed by their seek table (cuda_zstd_seekable_index): a seekable stream for
+    SeekableReader and for stock zstd.  One device copy of the stream into a buffer with room; the
+    frames are found and the table is written on the device.  max_frames bounds the table (None:
+    a guess from the size, and a second call with the stream's own count if it was too low).
+    decoder: a BatchedDecompressor / BatchedCompressor whose dictionary or dictionary set sizes
+    frames that state no content size.  A malformed stream raises ZstdError, with the complete
+    frames before the failing one in .num_frames and its offset in .error_offset."""
+    torch = _torch()
+    src = _to_device(data) if _is_host(data) else data.contiguous().view(torch.uint8).reshape(-1)
+    size = src.numel()
+    if size == 0 or (max_frames is not None and max_frames < 0):
+        raise ZstdError(INVALID, "seekable_index")
+    n = max(1024, size // 4096) if max_frames is None else int(max_frames)
+    s = stream if stream is not None else torch.cuda.current_stream()
+    tb, nf, eo = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_ulonglong(0)
+    with torch.cuda.stream(s):
+        while True:
+            cap = 17 + 8 * n
+            buf = torch.empty(size + cap, dtype=torch.uint8, device=src.device)
+            buf[:size].copy_(src)
+            temp = torch.empty(lib().cuda_zstd_seekable_index_get_temp_size(size, n), dtype=torch.uint8, device=src.device)
+            rc = lib().cuda_zstd_seekable_index(decoder._h if decoder is not None else None, buf.data_ptr(), size, n, buf.data_ptr() + size, cap,
+                                                ctypes.byref(tb), ctypes.byref(nf), ctypes.byref(eo), temp.data_ptr(), temp.numel(), s.cuda_stream)
+            if rc == TOO_SMALL and max_frames is None and nf.value > n:
+                n = nf.value
+                continue
+            break
+    if rc:
+        e = ZstdError(rc, "cuda_zstd_seekable_index")
+        e.num_frames, e.error_offset = nf.value, eo.value
+        raise e
+    return buf[: size + tb.value]
+
+
+def decompress_frames(data, decoder=None, stream=None):
+    """Decode concatenated frames frame-parallel: seekable_index, then one read of everything.
+    Host input gives bytes back, a device tensor a device tensor."""
+    return SeekableReader.from_frames(data, decoder, stream=stream).read_all(stream=stream)
 
 
 # Adaptive level selection (cuda_zstd_adaptive_*; reference adaptive::AdaptiveLevelSelector,

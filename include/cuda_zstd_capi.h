@@ -470,6 +470,41 @@ int cuda_zstd_seekable_read_ranges(nvcomp_zstd_batch_manager_t *mgr, const void 
                                    const size_t *d_lengths, void *const *d_out_ptrs, size_t num_ranges, size_t max_length, int verify_checksums,
                                    int *d_range_statuses, size_t *frames_decoded, void *d_temp, size_t temp_bytes, hipStream_t stream);
 
+/* ---------------- the seek table of concatenated frames that have none ----------------
+ * index: finds the frames of d_stream (size bytes of Zstandard and skippable frames back to back:
+ * pzstd output, joined .zst files, frames written one after another) on the device and writes the
+ * seek table for them to d_table: one entry per frame, skippable frames included with a
+ * Decompressed_Size of 0, descriptor 0 (no checksums).  A frame without a Frame_Content_Size gets
+ * its exact size from the decoder's size pass, with the dictionary or dictionary set of `mgr` (may
+ * be NULL: no dictionary).  d_table may be (char *)d_stream + size when the caller left room: the
+ * size + *table_bytes bytes are then a seekable stream for every cuda_zstd_seekable_* call and for
+ * stock zstd.  Blocking.  *table_bytes, *num_frames and *error_offset are host words, all required.
+ * Codes: 0; 2 a null or empty stream, a null output pointer, or a frame beyond the format's limits
+ * (more than 0x8000000 frames, a size over 0x40000000); 7 a temp buffer below
+ * index_get_temp_size(size, max_frames) (nothing is launched), more than max_frames frames
+ * (*num_frames = the stream's frame count, for a second call) or a table_capacity below
+ * 17 + 8 * frames; 6 a malformed stream, 1 when the first four bytes are no magic (the decoder's
+ * codes for the same bytes); or the size pass's code for the lowest frame it fails on (1 for a
+ * dictionary that is missing or wrong).  On a malformed stream or a failed size *num_frames = the
+ * complete frames before the failing one and *error_offset = its byte offset.  On every non-zero
+ * return no byte of d_table is written, on success none past *table_bytes.
+ * The frames are found speculatively: every position that spells a frame magic is a candidate, and
+ * the temp buffer holds 2 * max_frames + 1024 of them (max_frames counts up to 0x8000000).  A stream
+ * with more (frames nested in raw blocks or skippable payloads) is walked frame after frame by one
+ * wave instead, with the same result.  index_get_temp_size: 0 for stream_bytes == 0.
+ * cuda_zstd_hip_frames_index_path (test hook): 0 the choice above, 1 always the serial walker;
+ * _last_path: which of the two the last call took (-1: no call has launched anything yet).
+ * cuda_zstd_hip_frames_index_split (benchmark hook): on != 0 times the speculative path's kernels
+ * with HIP events; ms (4 floats, optional) = the last such call's candidate write, span, reach and
+ * collect milliseconds. */
+size_t cuda_zstd_seekable_index_get_temp_size(size_t stream_bytes, size_t max_frames);
+int cuda_zstd_seekable_index(nvcomp_zstd_batch_manager_t *mgr /* may be NULL */, const void *d_stream, size_t size, size_t max_frames,
+                             void *d_table, size_t table_capacity, size_t *table_bytes, size_t *num_frames,
+                             unsigned long long *error_offset, void *d_temp, size_t temp_bytes, hipStream_t stream);
+void cuda_zstd_hip_frames_index_path(int path);
+int cuda_zstd_hip_frames_index_last_path(void);
+void cuda_zstd_hip_frames_index_split(int on, float *ms);
+
 /* ---------------- adaptive level selection ----------------
  * C counterpart of include/cuda_zstd_adaptive.h (reference adaptive::AdaptiveLevelSelector), for
  * whole batches: which level a chunk is worth, from statistics of its first
