@@ -305,15 +305,24 @@ __device__ __forceinline__ void insert_repair(u16 *T, u32 tb0, u32 lane, const u
 // A lane's positions are 4-aligned apart (tiles and rows are multiples of 64), so its byte
 // shift is lane & 3 and its dwords sit at one base + immediate offsets; positions past lim read
 // bytes past the block (inside the staging area's pad and the tables: never inserted).
-// One instantiation per table serves every window (code size: K1's hot loops compete for the
-// instruction cache).  skip (a miss-skip window, orc_lz_parse_pre): after the first batch of
+// EDGE: the window may hold positions at or past lim or below pmin -- a block's first window and
+// the one or two that hold lim; every other window (inserter_loop tests it, a scalar) takes the
+// EDGE = false body, whose positions are all inserted: no bounds compare, no selects of the store
+// address and the candidate, no position arithmetic for them (these calls' batch loop is rolled,
+// see below, so the second body costs one more loop of ~90 instructions per table, not a
+// window's worth; zh_lz_kernel now uses all 128 VGPRs, 125 before, still without scratch).
+// skip (a miss-skip window, orc_lz_parse_pre): after the first batch of
 // ZH_SKIP_TILES tiles, on_check gets whether any of its positions has a candidate matching its
 // first ZH_MIN_MATCH_LONG (long table) / ZH_MIN_MATCH_SHORT (short) bytes -- the oracle's "a match
 // among the searched tiles" -- and returns whether the window's search resumes; if not, the rest
 // of the window is neither looked up nor inserted and its candidates are never dumped.
-template <bool LONG, typename Check>
-__device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, u32 lim, u32 lane, u32 (&creg)[NCR],
+template <bool LONG, bool EDGE, typename Check>
+__device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, u32 lim, u32 lane_, u32 (&creg)[NCR],
                                               Check &&on_check, bool skip, u32 pmin) {
+  // opaque lane copy: the lane's addresses and positions are computed per window, not kept in
+  // registers across the step loop for each instantiation (with them the kernel spills)
+  u32 lane;
+  __asm__ volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane_));
   // positions below pmin are already in T (a dictionary's precomputed tables): treated like
   // positions past lim (the junk slot, no candidate)
   constexpr u32 JUNK = LONG ? HL_SIZE : HS_SIZE;
@@ -333,12 +342,15 @@ __device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, 
         for (u32 t = 0; t < 3; t++) wv[b][k][t] = q[(b * ZH_TILE + 64 * k) / 4 + t];
   };
   load_in(wsb + T0 * ZH_TILE);
+  // (the pragma unrolls the first window's call, which has no resume check; in the calls with one
+  // the compiler keeps the loop rolled -- the check's exit is in its first iteration only -- and
+  // writes creg through indexed moves: 8 iterations of one batch body per instantiation)
 #pragma unroll
   for (u32 t0 = T0; t0 < NT; t0 += BT) {
     // opaque per-batch copy of lim: keeps the compiler from hoisting every tile's
-    // bounds checks (64 masks) to the top of the unrolled loop
-    u32 lim_t;
-    __asm__ volatile("v_mov_b32 %0, %1" : "=v"(lim_t) : "v"(lim));
+    // bounds checks (64 masks) to the top of the loop where it is unrolled
+    u32 lim_t = lim;
+    if constexpr (EDGE) __asm__ volatile("v_mov_b32 %0, %1" : "=v"(lim_t) : "v"(lim));
     u32 const tb0 = wsb + t0 * ZH_TILE;
     u32 const p1 = tb0 + lane + 1u;  // the lane's first position of the batch, + 1
     u32 h[BT][TPL], e[BT][TPL], sa[BT][TPL];
@@ -353,7 +365,7 @@ __device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, 
         // LDS addresses: the store goes to the lookup's slot or the junk slot (one select)
         u32 const a = (u32)(uintptr_t)(T + hh);
         e[b][k] = *(const __attribute__((address_space(3))) u16 *)(uintptr_t)a;
-        ok[b][k] = q1 <= lim_t && q1 > pmin;
+        ok[b][k] = !EDGE || (q1 <= lim_t && q1 > pmin);
         sa[b][k] = ok[b][k] ? a : (u32)(uintptr_t)(T + JUNK);
         h[b][k] = ok[b][k] ? hh : JUNK;  // (the check build's slot index)
       }
@@ -400,7 +412,7 @@ __device__ __forceinline__ void insert_window(const u32 *in32, u16 *T, u32 wsb, 
           u32 const p = tb0 + b * ZH_TILE + 64 * k + lane;
           u32 const c = ok[b][k] ? e[b][k] : 0u;
           u32 lo, hi, clo, chi;
-          ld64u(in32, min(p, lim_t), lo, hi);
+          ld64u(in32, EDGE ? min(p, lim_t) : p, lo, hi);
           ld64u(in32, c ? c - 1u : 0u, clo, chi);
           u32 const dx = (lo ^ clo) | ((hi ^ chi) & (LONG ? ~0u : 0xFFu));
           v |= c != 0 && dx == 0;
@@ -634,6 +646,14 @@ __device__ __forceinline__ u32 pk_sub16(u32 a, u32 b) {
   return __builtin_bit_cast(u32, (u16x2)(__builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)));
 }
 
+// min(a, ZH_MAX_MATCH, b) as one v_min3_u32 (the compiler emits two v_min_u32 for it)
+__device__ __forceinline__ u32 min3_cap(u32 a, u32 b) {
+  static_assert(ZH_MAX_MATCH == 64, "an inline constant");
+  u32 r;
+  __asm__("v_min3_u32 %0, %1, 64, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
 // The match lengths of rounds [r_lo, r_hi) (r_hi - r_lo <= NR, the most rounds the call site
 // has): candidates in cinfo -> match info (off << 8 | len, 0 = none) in place.  Semantics of
 // oracle/zstd_oracle.c orc_lz_match_info: lcp capped at ZH_MAX_MATCH and at the block end, long candidates from 8
@@ -781,12 +801,14 @@ __device__ __forceinline__ void span_lengths(const u32 *in32, u32 *ci, u64 *tm, 
     // when lane 63 is a chain end); a carry wraps below zero only where no lane takes it (the
     // position above continues a chain of 8 equal bytes: its lcp is at least 7)
     auto first_run = [](u64 f) { return ~f ? 64u - (u32)__builtin_clzll(~f) : 0u; };
-    u32 const lL = min((u32)ZH_MAX_MATCH, lLr[k] + (lane >= first_run(mFL[k]) ? clL - 6u : 0u));
-    u32 const lS = min((u32)ZH_MAX_MATCH, lSr[k] + (lane >= first_run(mFS[k]) ? clS - 7u : 0u));
-    clL = lane_value(lL, 0);
-    clS = lane_value(lS, 0);
-    u32 const capj = min((u32)ZH_MAX_MATCH, n - min(p, n));
-    u32 const rL = min(lL, capj), rS = min(lS, capj);
+    // (the cap at ZH_MAX_MATCH: on the scalar unit for the carry, which only needs lane 0's length,
+    // and folded into the cap at the block end for the lanes -- one three-way minimum per table)
+    u32 const xL = lLr[k] + (lane >= first_run(mFL[k]) ? clL - 6u : 0u);
+    u32 const xS = lSr[k] + (lane >= first_run(mFS[k]) ? clS - 7u : 0u);
+    clL = min((u32)ZH_MAX_MATCH, lane_value(xL, 0));
+    clS = min((u32)ZH_MAX_MATCH, lane_value(xS, 0));
+    u32 const capn = n - min(p, n);
+    u32 const rL = min3_cap(xL, capn), rS = min3_cap(xS, capn);
     u32 const mL = (cL && rL >= ZH_MIN_MATCH_LONG) ? rL : 0u;
     u32 const mS = (cS && rS >= ZH_MIN_MATCH_SHORT) ? rS : 0u;
     bool const useL = mL && mL >= mS;
@@ -1148,7 +1170,7 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
   u32 creg[NCR];
   if (span_s < span_e) insert_span<LONG>(in32, T, span_s, span_e, lane);
   // (the first window: its own instantiation, with pmin and no resume check)
-  insert_window<LONG>(in32, T, wstart, lim, lane, creg, NoCheck{}, false, pmin);
+  insert_window<LONG, true>(in32, T, wstart, lim, lane, creg, NoCheck{}, false, pmin);
   u32 cwe = lookahead<LONG>(in32, T, min(wstart + (u32)ZH_WINDOW, n), lim, lane);
   bool skipc = false;  // the window whose candidates creg holds is a miss-skip window (not resumed)
 #ifdef ZH_STAMPS
@@ -1184,8 +1206,11 @@ __device__ __forceinline__ bool inserter_loop(const u32 *in32, u16 *T, u8 *ci8, 
       // a miss-skip window's first tiles, then the rest of it if any of them found a match (both
       // inserters' checks combined before either takes a barrier)
       bool resumed = false;
-      insert_window<LONG>(in32, T, nx, lim, lane, creg,
-                          [&](bool h) { return resumed = resume_exchange<LONG, TWO>(misc_, k + 1, h, lane); }, skipc, 0u);
+      auto const on_check = [&](bool h) { return resumed = resume_exchange<LONG, TWO>(misc_, k + 1, h, lane); };
+      // every position of the window below lim (all but a block's last window or two): the body
+      // without the per-lane bounds test
+      if (nx + ZH_WINDOW <= lim) insert_window<LONG, false>(in32, T, nx, lim, lane, creg, on_check, skipc, 0u);
+      else insert_window<LONG, true>(in32, T, nx, lim, lane, creg, on_check, skipc, 0u);
       if (resumed) skipc = false;
       cwe = lookahead<LONG>(in32, T, min(nx + ZH_WINDOW, n), lim, lane);
     }
